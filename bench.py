@@ -7,13 +7,23 @@ row-local block update, all on the GPU with every operand resident in HBM before
 
   metric  = nnz*n mod-p MAC/s : (2 SpMV * nnz * n) * steps / time   (block products are NOT counted)
   value   = whole-job rate over all ranks (strong scaling: the matrix is fixed, rows are partitioned);
-            the timed region (exactly K steps between barrier + synchronize) is repeated 5 times and the
-            MEDIAN region is reported; every region's time is listed under "repeats"
-  roofline= the SpMV kernel (dominant): algorithmic bytes of SURVEY 8(d) / mean launch duration measured
-            with HIP events on the solver's stream inside this run, against the 8 TB/s HBM3E peak
-  cpu_baseline = the oracle's by-rows OpenMP kernels timed on this box's host cores on a bounded sample of
+            the timed region is exactly K = --steps steps between barrier + synchronize, after W = --warmup steps
+  ms_per_step = milliseconds of one timed step
+
+A plain run does only that: set-up, W warm-up steps, one timed region of K steps, the result line.  --full adds what
+the default line carried before (everything below); --repeats, --cpu-seconds, --extras and --live-traffic still switch
+single parts on or off.
+  repeats = (--full) the timed region is repeated 5 times and the MEDIAN region is reported; every
+            region's time is listed under "repeats"
+  roofline= (--full) the SpMV kernel (dominant): algorithmic bytes of SURVEY 8(d) / mean launch duration measured
+            with HIP events on the solver's stream in a further K profiled steps, against the 8 TB/s HBM3E peak
+  cpu_baseline = (--full) the oracle's by-rows OpenMP kernels timed on this box's host cores on a bounded sample of
             the SAME workload, at 16 threads and at all cores; a reported baseline, not the target.
-  extra.workloads = the other single-GPU configs (relat9 and relat8 shapes) in the same line (N = 1 only)
+  extra.workloads = (--full) the other single-GPU configs (relat9 and relat8 shapes) in the same line (N = 1 only)
+  sharded_equals_single_gpu, multi_gpu = (--full, N > 1) the sharded run checked against one GPU, per-collective times
+
+--dump-outputs DIR: what the timed steps computed, read back right after the timed region (see dump_outputs): a fixed,
+seeded sample of block rows of v and p and the whole n x n operands, every 64-bit word as two exact float64 halves.
 
 Real matrices: if $BLZ_MTX_DIR holds GL7d19.mtx / relat9.mtx / relat8.mtx they are loaded instead of the seeded
 synthetic stand-ins of the same shape ("data" says which).
@@ -74,7 +84,9 @@ WORKLOADS = {
 }
 LIVE_BUDGET_S = 200          # no further profiler pass of an EXTRA workload is started once the run has taken this long
 HBM_PEAK_GBPS = 8000.0  # /opt/skills/guides/MI355X_MICROARCH.md: 8 TB/s HBM3E peak
-REPEATS = 5             # timed regions of K steps each; the median one is reported
+REPEATS = 5             # --full: timed regions of K steps each; the median one is reported
+DUMP_ROWS = 65536       # --dump-outputs: block rows sampled per block (at n = 16: 2 x 16 MB)
+DUMP_SEED = 0x44554D50
 
 
 def prime_name(p):
@@ -120,7 +132,10 @@ def self_launch(args):
     """N > 1 asked and no launcher around us: start one process per GPU as a child (this process has made no GPU call
     and imports neither torch nor the library), pass its stderr through, relay its single JSON line and its exit code."""
     import subprocess
-    cmd = launcher_command(sys.argv[1:], args.gpus, free_port())
+    argv = sys.argv[1:]
+    if args.dump_outputs:           # the ranks run in the repository root: they get the directory as an absolute path
+        argv += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
+    cmd = launcher_command(argv, args.gpus, free_port())
     if args.dry_run:
         print(json.dumps({"dry_run": True, "n_gpus": args.gpus, "cmd": cmd}))
         return 0
@@ -208,14 +223,54 @@ def live_gather_ceiling(row_bytes, table_bytes, avg_len):
         return {"error": repr(exc)}
 
 
-def measure(blz, torch, dist, ctx, info, w, steps, warmup, repeats):
+def words_f64(a):
+    """u64 words -> float64 of shape a.shape + (2,): (high 32 bits, low 32 bits), both exact in a double"""
+    import numpy as np
+    a = np.asarray(a, dtype=np.uint64)
+    return np.stack([(a >> np.uint64(32)).astype(np.float64), (a & np.uint64(0xFFFFFFFF)).astype(np.float64)], axis=-1)
+
+
+def dump_outputs(blz, ctx, dist):
+    """What a caller of the timed path receives after its last step: the blocks v and p that the loop carries (tmp is
+    scratch until the solve ends) and the n x n operands vtAv, vtAAv, winv and d of that step.  A block is a fixed, seeded
+    sample of DUMP_ROWS of its rows (every row
+    when it has fewer), the sampled row numbers alongside; words split as words_f64 does.  With several ranks every rank
+    holds only its own rows (the others are zero), so the samples are summed over the ranks; the n x n operands are the
+    same on every rank.  Returns {name: float64 array}."""
+    import numpy as np
+    n, out = ctx.n, {}
+    for name, b in (("v", blz.V), ("p", blz.P)):
+        rows = ctx.rows(b)
+        pick = np.arange(rows) if rows <= DUMP_ROWS else np.sort(np.random.default_rng(DUMP_SEED).choice(rows, DUMP_ROWS, replace=False))
+        got = ctx.get_block(b).reshape(rows, n)[pick]
+        if dist is not None:
+            import torch
+            t = torch.from_numpy(got.view(np.int64).copy())
+            dist.all_reduce(t)              # one rank's word and zeros: exact in int64
+            got = t.numpy().view(np.uint64)
+        out[name] = words_f64(got)
+        out[name + "_rows"] = pick.astype(np.float64)
+    for name, k in (("vtAv", blz.VTAV), ("vtAAv", blz.VTAAV), ("winv", blz.WINV), ("d", blz.D)):
+        s = ctx.get_small(k)
+        out[name] = words_f64(s if k == blz.D else s.reshape(n, n))
+    out["iterations"] = np.array([ctx.iterations], dtype=np.float64)
+    return out
+
+
+def measure(blz, torch, dist, ctx, info, w, steps, warmup, repeats, profile=True, grab=None):
     """Warm up, time `repeats` regions of exactly `steps` steps (barrier + synchronize on both sides, MAX over ranks),
-    then the same steps once more with HIP-event spans per kernel class.  Returns the numbers of one workload."""
+    call grab() (outside the clock) for what the timed steps computed, then with `profile` the same steps once more with
+    HIP-event spans per kernel class.  Returns the numbers of one workload."""
     n, right = w["n"], w["right"]
 
     def barrier():
         if dist is not None:
             dist.barrier()
+
+    def synchronize():
+        ctx.sync()
+        if torch is not None:
+            torch.cuda.synchronize()
 
     def all_max(x):
         if dist is None:
@@ -242,19 +297,27 @@ def measure(blz, torch, dist, ctx, info, w, steps, warmup, repeats):
     check()
     times, dev = [], []
     for _ in range(repeats):
-        ctx.sync()
-        torch.cuda.synchronize()
+        synchronize()
         barrier()
         t0 = time.perf_counter()
         dev_ms = run(steps)
-        ctx.sync()
-        torch.cuda.synchronize()
+        synchronize()
         elapsed = time.perf_counter() - t0
         barrier()
         times.append(all_max(elapsed))
         dev.append(dev_ms)
     check()
     elapsed = statistics.median(times)
+    outputs = grab() if grab is not None else None
+    loc, kind = ctx.locality()
+    res = dict(elapsed=elapsed, times=times, device_ms_per_step=statistics.median(dev) / steps, outputs=outputs,
+               macs_per_step=2 * info["nnz"] * n, value=2 * info["nnz"] * n * steps / elapsed, word=ctx.word_bytes,
+               rows_v=ctx.rows(blz.V), rows_t=ctx.rows(blz.TMP), loc_rows=(ctx.local_rows(blz.V)[1], ctx.local_rows(blz.TMP)[1]),
+               renumbering=dict(lines_per_entry=dict(M=loc[0], Mt=loc[1]), order=("smallest", "file", "mean", "sweeps")[kind]),
+               lds_panel={"spmv1": dict(zip(("rows", "share"), ctx.panel_rows(not right))),
+                          "spmv2": dict(zip(("rows", "share"), ctx.panel_rows(right)))})
+    if not profile:
+        return res
 
     ctx.profile(True)
     run(steps)
@@ -281,15 +344,9 @@ def measure(blz, torch, dist, ctx, info, w, steps, warmup, repeats):
     kernels["block_dot"]["alg_bytes"] = 2 * loc_v * n * word
     kernels["orthogonalize"]["alg_bytes"] = 5 * loc_v * n * word
     t_spmv_ms = prof["spmv1"]["ms_total"] / max(steps, 1)
-    macs_per_step = 2 * info["nnz"] * n
-    loc, kind = ctx.locality()
-    return dict(elapsed=elapsed, times=times, device_ms_per_step=statistics.median(dev) / steps, kernels=kernels, prof=prof,
-                loc_rows=(loc_v, loc_t),
-                t_spmv_ms=t_spmv_ms, alg_bytes=bytes1, achieved=bytes1 / (t_spmv_ms * 1e-3) / 1e9, nnz1=nnz1,
-                macs_per_step=macs_per_step, value=macs_per_step * steps / elapsed, word=word, rows_v=rows_v, rows_t=rows_t,
-                renumbering=dict(lines_per_entry=dict(M=loc[0], Mt=loc[1]), order=("smallest", "file", "mean", "sweeps")[kind]),
-                lds_panel={"spmv1": dict(zip(("rows", "share"), ctx.panel_rows(not right))),
-                           "spmv2": dict(zip(("rows", "share"), ctx.panel_rows(right)))})
+    res.update(kernels=kernels, prof=prof, t_spmv_ms=t_spmv_ms, alg_bytes=bytes1, achieved=bytes1 / (t_spmv_ms * 1e-3) / 1e9,
+               nnz1=nnz1)
+    return res
 
 
 def first_spmv_kernel(name):
@@ -372,20 +429,32 @@ def main():
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--workload", default="gl7d19", choices=sorted(WORKLOADS))
-    ap.add_argument("--repeats", type=int, default=REPEATS, help="timed regions of --steps steps; the median is reported")
-    ap.add_argument("--cpu-seconds", type=float, default=20.0, help="budget of the CPU baseline sample (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: 5 timed regions, the profiled pass (kernels, "
+                         "roofline), the CPU baseline and the reference, the extra workloads, live traffic and ceiling, and "
+                         "with N > 1 the check against one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed steps computed as DIR/<name>.npy (float64; see dump_outputs)")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help=f"timed regions of --steps steps; the median is reported (default 1, with --full {REPEATS})")
+    ap.add_argument("--cpu-seconds", type=float, default=None,
+                    help="budget of the CPU baseline sample (0 = skip; default 0, with --full 20)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="0 = 16 threads and all cores, else this many only")
     ap.add_argument("--ref-iterations", type=int, default=50,
                     help="iterations of the unmodified reference OpenMP binary on a 1/4-scale sample (0 = skip)")
     ap.add_argument("--extras", type=int, default=-1,
                     help="1/0: also run the other single-GPU workloads (relat9, relat8, config-5 quarter shape, structured); "
-                         "default: only with the default workload at N=1")
+                         "default: only with --full and the default workload at N=1")
     ap.add_argument("--live-traffic", type=int, default=-1,
                     help="1/0: measure roofline.traffic in this run (two rocprofv3 --pmc child passes of the same workload); "
-                         "default: only with the default workload at N=1 and not under a profiler")
+                         "only with --full; default: with the default workload at N=1 and not under a profiler")
     ap.add_argument("--dry-run", action="store_true",
                     help="print what would be started (for N > 1 without a launcher: the torch.distributed.run command) and exit")
     args = ap.parse_args()
+    if args.repeats is None:
+        args.repeats = REPEATS if args.full else 1
+    if args.cpu_seconds is None:
+        args.cpu_seconds = 20.0 if args.full else 0.0
 
     launched = "WORLD_SIZE" in os.environ or "RANK" in os.environ
     if args.gpus > 1 and not launched:
@@ -421,18 +490,20 @@ def main():
     import numpy as np
     import blz
     blz.lib()       # load libblz_hip.so (and with it /opt/rocm's HIP runtime) before torch brings its own copy
-    import torch
 
-    dist = None
+    # torch only carries the control plane between ranks: a single process neither needs it nor waits for its import
+    torch, dist = None, None
     if world > 1 or "TORCHELASTIC_RUN_ID" in os.environ or os.environ.get("BLZ_BENCH_DIST") == "1":
         # launched by torch.distributed.run (also with one process: the same code path as N > 1)
+        import torch
         import torch.distributed as dist
         dist.init_process_group(backend="gloo", init_method="env://")
     if blz.device_count() < 1:
         sys.exit("bench.py: no GPU visible -- libblz_hip has no CPU path")
     # one GPU per rank; if the launcher narrowed the visibility to one device per process, that device is number 0
     local_rank %= blz.device_count()
-    torch.cuda.set_device(local_rank)
+    if torch is not None:
+        torch.cuda.set_device(local_rank)
 
     def leave(code, msg):
         """every rank leaves together (a lone sys.exit would leave the others in a barrier until the gloo timeout)"""
@@ -544,13 +615,14 @@ def main():
     t_setup = time.time() - t0
 
     try:
-        r = measure(blz, torch, dist, ctx, info, w, args.steps, args.warmup, max(1, args.repeats))
+        r = measure(blz, torch, dist, ctx, info, w, args.steps, args.warmup, max(1, args.repeats), profile=args.full,
+                    grab=(lambda: dump_outputs(blz, ctx, dist)) if args.dump_outputs else None)
     except Stopped as exc:
         leave(1, str(exc))
-    traffic, traffic_src = spmv_traffic(args.workload, world)      # None for any (workload, N) without a committed PMC run
-    t_spmv_ms = r["t_spmv_ms"]
-    # the first SpMV gathers block rows of v (n words each) out of the whole block
-    ceiling, ceiling_src = gather_ceiling(n * r["word"], r["rows_v"] * n * r["word"])
+    if args.dump_outputs and rank == 0:
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        for name, a in r["outputs"].items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
 
     out = {
         "metric": "nnz*n mod-p MAC/s",
@@ -573,10 +645,23 @@ def main():
             "matrix": (data if data != "synthetic" else
                        ("seeded synthetic WITH structure (extra workload)" if w.get("structured") else
                         "seeded synthetic, uniform columns (SURVEY 8(d)); real .mtx not on the box")),
-            "timing": f"median of {len(r['times'])} regions of {args.steps} steps each, max over ranks per region",
+            "timing": (f"median of {len(r['times'])} regions of {args.steps} steps each" if len(r["times"]) > 1 else
+                       f"one region of {args.steps} steps") + ", max over ranks per region",
         },
         "repeats": {"ms_per_step": [t / args.steps * 1e3 for t in r["times"]]},
-        "roofline": {
+        "host": host_cpu(),
+        "device_ms_per_step": r["device_ms_per_step"],
+        "setup_s": {"generate_or_load": t_gen, "csr_upload_init": t_setup,
+                    "note": "rank 0 prepares once and shares the result through an mmapped cache file when N > 1"},
+        "renumbering": r["renumbering"],
+        "lds_panel": r["lds_panel"],
+    }
+    if args.full:
+        traffic, traffic_src = spmv_traffic(args.workload, world)      # None for any (workload, N) without a committed PMC run
+        t_spmv_ms = r["t_spmv_ms"]
+        # the first SpMV gathers block rows of v (n words each) out of the whole block
+        ceiling, ceiling_src = gather_ceiling(n * r["word"], r["rows_v"] * n * r["word"])
+        out["roofline"] = {
             "kernel": "the first SpMV of each step (tmp = M^T v): k_spmv, or k_spmv_staged / k_spmv_panel where the slab's plan chose them",
             "bound": "hbm",
             "achieved": r["achieved"],
@@ -596,20 +681,13 @@ def main():
             "gathers_per_s": r["nnz1"] / (t_spmv_ms * 1e-3) if t_spmv_ms else None,
             "gather_ceiling_per_s": ceiling,
             "gather_ceiling_source": ceiling_src,
-        },
-        "host": host_cpu(),
-        "device_ms_per_step": r["device_ms_per_step"],
-        "kernels": r["kernels"],
-        "setup_s": {"generate_or_load": t_gen, "csr_upload_init": t_setup,
-                    "note": "rank 0 prepares once and shares the result through an mmapped cache file when N > 1"},
-        "renumbering": r["renumbering"],
-        "lds_panel": r["lds_panel"],
-    }
+        }
+        out["kernels"] = r["kernels"]
     macs_per_step, rows_v, rows_t = r["macs_per_step"], r["rows_v"], r["rows_t"]
 
     # ---- several ranks (or the exchange forced on one): what RCCL saw, how the exchange was cut, what each collective
     # cost and how much of it the products hid -- enough to fit the piece model (t0 per call, gather rate) from ONE run
-    if dist is not None:
+    if dist is not None and args.full:
         seen, me = ctx.comm_info()
         prof, word = r["prof"], r["word"]
         # padded slab rows of each side = the largest rank's share (ncclAllGather moves equal counts)
@@ -743,9 +821,9 @@ def main():
     # ---- several ranks (or the exchange code forced on one): the sharded run must hold the same block as one GPU
     # solving the whole system.  Every rank sums the words of its slab of v; rank 0 repeats the same number of
     # iterations on a plain single-GPU context (tens of milliseconds) and compares the totals mod 2^64.  The verdict is
-    # broadcast: on a mismatch the line carries value = null and EVERY rank exits non-zero.
+    # broadcast: on a mismatch the line carries value = null and EVERY rank exits non-zero.  (--full)
     verdict = 1
-    if dist is not None:
+    if dist is not None and args.full:
         iters_done = ctx.iterations
         mine = 0 if per_rank else int(ctx.get_block(blz.V).sum(dtype=np.uint64))          # rows of other ranks are left at zero
         tot = torch.tensor([mine & 0x7FFFFFFF, (mine >> 31) & 0x7FFFFFFF, mine >> 62], dtype=torch.int64)
@@ -792,7 +870,7 @@ def main():
 
     # ---- the other single-GPU configs in the same line (default run at N = 1): relat9 shape (config 3) and relat8
     # shape (config 2), same measurement, fewer regions
-    want_extras = (args.extras == 1) or (args.extras < 0 and args.workload == "gl7d19" and world == 1 and dist is None)
+    want_extras = (args.extras == 1) or (args.extras < 0 and args.full and args.workload == "gl7d19" and world == 1 and dist is None)
     if want_extras and verdict:
         out["extra"] = {"workloads": {}}
         # relat9 / relat8 shapes = configs 3 / 2; synth5q = ONE GPU's quarter-scale share of config 5 (n = 16, 128-byte block
@@ -829,8 +907,9 @@ def main():
             except Exception as exc:    # an extra never costs the headline line
                 out["extra"]["workloads"][name] = {"error": repr(exc)}
 
-    want_live = (args.live_traffic == 1) or (args.live_traffic < 0 and args.workload == "gl7d19" and world == 1 and dist is None
-                                             and args.cpu_seconds > 0 and not under_profiler())
+    # (annotations of the roofline, which only --full measures)
+    want_live = args.full and ((args.live_traffic == 1) or (args.live_traffic < 0 and args.workload == "gl7d19" and world == 1
+                                                            and dist is None and args.cpu_seconds > 0 and not under_profiler()))
     # ---- the gather ceiling of this box, by the bare loop, for the headline product and for each extra one
     if want_live and verdict and rank == 0 and world == 1:
         rf = out["roofline"]

@@ -113,3 +113,21 @@ def test_a_failed_profiler_pass_is_reported_not_raised():
     got = bench.live_traffic("relat8", limit_s=120)
     assert set(got) == {"error"}, got
     assert got["error"].startswith(("FETCH_SIZE pass", "rocprofv3 not found")), got
+
+
+def test_the_ranks_get_the_dump_directory_as_an_absolute_path():
+    """The ranks run in the repository root: a relative --dump-outputs DIR reaches them as the caller's DIR, made absolute."""
+    d = json.loads(run("--gpus", "2", "--dump-outputs", "out_dir", "--dry-run").stdout)
+    assert d["cmd"][-2:] == ["--dump-outputs", os.path.join(ROOT, "out_dir")]
+
+
+def test_dumped_words_are_two_exact_float64_halves():
+    """--dump-outputs writes float64 only: every u64 word goes out as (high 32 bits, low 32 bits), each exact in a double."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    a = np.array([0, 1, (1 << 32) - 1, 1 << 32, (1 << 61) - 2, (1 << 64) - 1], dtype=np.uint64).reshape(2, 3)
+    f = bench.words_f64(a)
+    assert f.dtype == np.float64 and f.shape == (2, 3, 2)
+    back = (f[..., 0].astype(np.uint64) << np.uint64(32)) | f[..., 1].astype(np.uint64)
+    assert np.array_equal(back, a)

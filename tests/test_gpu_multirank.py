@@ -156,7 +156,7 @@ def test_bench_under_torch_distributed_run_checks_itself(world):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}",
                         "--master-addr", "127.0.0.1", "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", str(world),
-                        "--workload", "tiny", "--steps", "5", "--warmup", "1", "--cpu-seconds", "0"],
+                        "--workload", "tiny", "--steps", "5", "--warmup", "1", "--cpu-seconds", "0", "--full"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]
@@ -175,7 +175,7 @@ def test_bench_starts_its_own_ranks(world):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env["HSA_ENABLE_IPC_MODE_LEGACY"] = "0"
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--workload", "tiny", "--steps", "5",
-                        "--warmup", "1", "--cpu-seconds", "0"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
+                        "--warmup", "1", "--cpu-seconds", "0", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
     assert len(lines) == 1
@@ -196,7 +196,7 @@ def test_bench_per_rank_set_up_path_on_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BLZ_BENCH_PER_RANK="1", BLZ_FORCE_COMM="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                         "--master-addr", "127.0.0.1", "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "1",
-                        "--workload", "tiny5", "--steps", "4", "--warmup", "1", "--cpu-seconds", "0", "--ref-iterations", "0"],
+                        "--workload", "tiny5", "--steps", "4", "--warmup", "1", "--cpu-seconds", "0", "--full", "--ref-iterations", "0"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     d = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -213,7 +213,7 @@ def test_bench_shared_set_up_path_on_one_rank():
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0", BLZ_BENCH_SHARE="1", BLZ_FORCE_COMM="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1",
                         "--master-addr", "127.0.0.1", "--master-port", _free_port(), os.path.join(ROOT, "bench.py"), "--gpus", "1",
-                        "--workload", "tiny", "--steps", "5", "--warmup", "1", "--cpu-seconds", "0", "--ref-iterations", "0"],
+                        "--workload", "tiny", "--steps", "5", "--warmup", "1", "--cpu-seconds", "0", "--full", "--ref-iterations", "0"],
                        capture_output=True, text=True, timeout=900, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1]

@@ -37,7 +37,7 @@ i=0
 while IFS= read -r set; do
 	case "$set" in \#*|"") continue;; esac
 	i=$((i + 1))
-	timeout -k 5 120 rocprofv3 --pmc $set --output-format csv -d "$out/pass$i" -- python3 bench.py "$@" --cpu-seconds 0 --ref-iterations 0 --extras 0 > "$out/bench_pass$i.json" 2> "$out/pass$i.err"
+	timeout -k 5 120 rocprofv3 --pmc $set --output-format csv -d "$out/pass$i" -- python3 bench.py --full "$@" --cpu-seconds 0 --ref-iterations 0 --extras 0 > "$out/bench_pass$i.json" 2> "$out/pass$i.err"
 	rc=$?
 	if [ $rc -ne 0 ]; then
 		echo "pass $i ($set) failed with $rc: stopping here"; tail -3 "$out/pass$i.err"

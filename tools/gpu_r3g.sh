@@ -12,7 +12,7 @@ tail -3 "$out/pytest.log"
 for wl in relat9 gl7d19; do
 for v in "pair8_0:BLZ_PAIR8=0" "pair8_1:BLZ_PAIR8=1" "pair8_1_always:BLZ_PAIR8=1 BLZ_STAGE_ALWAYS=1" "pair8_0_always:BLZ_PAIR8=0 BLZ_STAGE_ALWAYS=1"; do
 	tag=${v%%:*}; envs=${v#*:}
-	env $envs timeout -k 10 300 python3 bench.py --workload $wl --steps 20 --warmup 3 --repeats 3 --cpu-seconds 0 --ref-iterations 0 --extras 0 > "$out/${wl}_$tag.json" 2> "$out/${wl}_$tag.err" || { echo "$tag failed"; tail -5 "$out/${wl}_$tag.err"; exit 1; }
+	env $envs timeout -k 10 300 python3 bench.py --full --workload $wl --steps 20 --warmup 3 --repeats 3 --cpu-seconds 0 --ref-iterations 0 --extras 0 > "$out/${wl}_$tag.json" 2> "$out/${wl}_$tag.err" || { echo "$tag failed"; tail -5 "$out/${wl}_$tag.err"; exit 1; }
 	python3 - "$out/${wl}_$tag.json" "$wl $tag" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]))

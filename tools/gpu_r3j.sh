@@ -12,7 +12,7 @@ timeout -k 10 300 python3 tools/exp_sweeps.py > "$out/exp_band_default.txt" 2>&1
 cat "$out/exp_band_default.txt"
 for v in "panel:BLZ_NO_PANEL=0" "nopanel:BLZ_NO_PANEL=1" "nopanel_cu6:BLZ_NO_PANEL=1 BLZ_SPMV_BLOCKS_PER_CU=6"; do
 	tag=${v%%:*}; envs=${v#*:}
-	env $envs timeout -k 10 300 python3 bench.py --workload relat8 --steps 50 --warmup 5 --repeats 5 --cpu-seconds 0 --ref-iterations 0 --extras 0 > "$out/relat8_$tag.json" 2> "$out/relat8_$tag.err" || { echo "$tag failed"; tail -5 "$out/relat8_$tag.err"; exit 1; }
+	env $envs timeout -k 10 300 python3 bench.py --full --workload relat8 --steps 50 --warmup 5 --repeats 5 --cpu-seconds 0 --ref-iterations 0 --extras 0 > "$out/relat8_$tag.json" 2> "$out/relat8_$tag.err" || { echo "$tag failed"; tail -5 "$out/relat8_$tag.err"; exit 1; }
 	python3 - "$out/relat8_$tag.json" "relat8 $tag" <<'PY'
 import json,sys
 d=json.load(open(sys.argv[1]))
