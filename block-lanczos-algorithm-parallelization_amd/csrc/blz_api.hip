@@ -216,6 +216,12 @@ struct blz_ctx {
 	double hot_share[2] = { 0.0, 0.0 };	/* share of the entries held by the rows / columns numbered first */
 	double locality[2] = { 1.0, 1.0 };	/* lines per gathered entry in windows of rows, product M*x / M^T*x */
 	int order_kind = 0;			/* which order blz_reorder_auto chose */
+	/* blz_block_rref / blz_kernel_basis (allocated on first use) */
+	u64 *rref_stack = nullptr;	/* partial echelons: num_cu * 2 workgroups x n rows x n words */
+	u64 *rref_gath = nullptr;	/* every rank's echelon (nranks x n x n) */
+	u64 *rref_out = nullptr;	/* the RREF, n x n */
+	u64 *rref_z = nullptr;		/* n x n operand of the block product */
+	int *rref_ctl = nullptr;	/* [rank-n flag, stacked rows, rank, pivots[n]] */
 };
 
 /* HIP-event span around one enqueue on the context's stream (only while profiling is on). */
@@ -434,6 +440,9 @@ extern "C" void blz_destroy(blz_ctx *c)
 	for (void *&d : c->snap_dev)
 		if (d) hipFree(d);
 	if (c->small) hipFree(c->small);
+	for (u64 *b : { c->rref_stack, c->rref_gath, c->rref_out, c->rref_z })
+		if (b) hipFree(b);
+	if (c->rref_ctl) hipFree(c->rref_ctl);
 	if (c->dot_send) hipFree(c->dot_send);
 	if (c->dot_recv) hipFree(c->dot_recv);
 	if (c->rs_recv) hipFree(c->rs_recv);
@@ -1532,6 +1541,131 @@ extern "C" int blz_final_check(blz_ctx *c, int *v_nonzero, int *vtm_zero)
 		*v_nonzero = c->host_ctl.flag_v_nonzero != 0;
 	if (vtm_zero)
 		*vtm_zero = c->host_ctl.flag_t_nonzero == 0;
+	return BLZ_OK;
+}
+
+/* ---- canonical RREF of a block's row space, and the kernel basis built on it ---- */
+
+static int rref_alloc(blz_ctx *c)
+{
+	if (c->rref_ctl)
+		return BLZ_OK;
+	const size_t n = (size_t)c->un;
+	HIPCHK(hipMalloc(&c->rref_stack, (size_t)c->cfg.num_cu * 2 * n * n * sizeof(u64)));
+	HIPCHK(hipMalloc(&c->rref_gath, (size_t)c->nranks * n * n * sizeof(u64)));
+	HIPCHK(hipMalloc(&c->rref_out, n * n * sizeof(u64)));
+	HIPCHK(hipMalloc(&c->rref_z, n * n * sizeof(u64)));
+	HIPCHK(hipMalloc(&c->rref_ctl, (3 + n) * sizeof(int)));
+	return BLZ_OK;
+}
+
+/* RREF of `block` (this rank's rows, then, with several ranks, every rank's echelon merged) into rref_out / rref_ctl[2..] */
+static int rref_to_host(blz_ctx *c, int block, uint64_t *E, int *rank, int32_t *pivots)
+{
+	int rc = rref_alloc(c);
+	if (rc != BLZ_OK)
+		return rc;
+	HIPCHK(hipStreamSynchronize(c->stream));
+	HIPCHK(hipStreamSynchronize(c->xstream));
+	const int sd = side_of(block), n = c->un;
+	HIPCHK(hipMemsetAsync(c->rref_ctl, 0, 2 * sizeof(int), c->stream));
+	HIPCHK(launch_rref_partial(c->cfg, slab_ptr(c, block), c->count[sd], c->cfg.n, n, c->rref_stack, c->rref_ctl, c->stream));
+	HIPCHK(launch_rref_merge(c->cfg, c->rref_stack, 0, c->rref_ctl + 1, n, c->rref_out, c->rref_ctl + 2, c->stream));
+	if (c->nranks > 1 && !c->external_exchange) {
+		/* every rank merges the same stack, so every rank holds the same RREF */
+		rc = coll_allgather(c, c->rref_out, c->rref_gath, (size_t)n * n * sizeof(u64), c->stream);
+		if (rc != BLZ_OK)
+			return rc;
+		HIPCHK(launch_rref_merge(c->cfg, c->rref_gath, (int64_t)c->nranks * n, nullptr, n, c->rref_out, c->rref_ctl + 2,
+					 c->stream));
+	}
+	std::vector<int> info((size_t)n + 1);
+	HIPCHK(hipMemcpyAsync(E, c->rref_out, (size_t)n * n * sizeof(u64), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipMemcpyAsync(info.data(), c->rref_ctl + 2, info.size() * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));
+	*rank = info[0];
+	for (int i = 0; i < n; i++)
+		pivots[i] = info[(size_t)i + 1];
+	return BLZ_OK;
+}
+
+extern "C" int blz_block_rref(blz_ctx *c, int block, uint64_t *rref, int *rank, int32_t *pivots)
+{
+	NEED_MATRIX(c);
+	if (block < 0 || block > 3)
+		return blz_fail(BLZ_EINVAL, "blz_block_rref: bad block %d", block);
+	const int n = c->un;
+	std::vector<uint64_t> E((size_t)n * n);
+	std::vector<int32_t> piv((size_t)n);
+	int r = 0;
+	const int rc = rref_to_host(c, block, E.data(), &r, piv.data());
+	if (rc != BLZ_OK)
+		return rc;
+	if (rref)
+		memcpy(rref, E.data(), E.size() * sizeof(uint64_t));
+	if (rank)
+		*rank = r;
+	if (pivots)
+		memcpy(pivots, piv.data(), piv.size() * sizeof(int32_t));
+	return BLZ_OK;
+}
+
+/* V <- V * Z (this rank's rows), Z = n x n host residues */
+static int block_mul(blz_ctx *c, const std::vector<uint64_t> &Z)
+{
+	HIPCHK(hipMemcpyAsync(c->rref_z, Z.data(), Z.size() * sizeof(u64), hipMemcpyHostToDevice, c->stream));
+	HIPCHK(launch_block_mul(c->cfg, slab_ptr(c, BLZ_V), c->count[0], c->cfg.n, c->un, c->rref_z, c->stream));
+	HIPCHK(hipStreamSynchronize(c->stream));	/* Z is a host vector */
+	c->gath_holds[0] = -1;
+	return BLZ_OK;
+}
+
+extern "C" int blz_kernel_basis(blz_ctx *c, int *k, uint64_t *z)
+{
+	NEED_MATRIX(c);
+	const int n = c->un;
+	const u64 p = c->prime;
+	std::vector<uint64_t> E((size_t)n * n), Z0((size_t)n * n, 0), S((size_t)n * n, 0);
+	std::vector<int32_t> piv((size_t)n);
+	/* 1. E1 = RREF(TMP), rank s, pivots P */
+	int s = 0;
+	int rc = rref_to_host(c, BLZ_TMP, E.data(), &s, piv.data());
+	if (rc != BLZ_OK)
+		return rc;
+	/* 2. Z0 = the canonical null basis of E1: one column per free column f, ascending: 1 at f, -E1[i][f] at pivot i */
+	std::vector<char> is_piv((size_t)n, 0);
+	for (int i = 0; i < s; i++)
+		is_piv[(size_t)piv[(size_t)i]] = 1;
+	int jj = 0;
+	for (int f = 0; f < n; f++) {
+		if (is_piv[(size_t)f])
+			continue;
+		Z0[(size_t)f * n + jj] = 1;
+		for (int i = 0; i < s; i++)
+			Z0[(size_t)piv[(size_t)i] * n + jj] = E[(size_t)i * n + f] ? p - E[(size_t)i * n + f] : 0;
+		jj++;
+	}
+	/* 3. Y = V * Z0 (skipped when Z0 = I, i.e. s = 0) */
+	if (s > 0 && (rc = block_mul(c, Z0)) != BLZ_OK)
+		return rc;
+	/* 4. E2 = RREF(Y): the basis is Y's columns at E2's pivots, moved to the front; the rest zeroed */
+	int kk = 0;
+	if ((rc = rref_to_host(c, BLZ_V, E.data(), &kk, piv.data())) != BLZ_OK)
+		return rc;
+	bool identity = kk == n;
+	for (int i = 0; i < kk; i++) {
+		S[(size_t)piv[(size_t)i] * n + i] = 1;
+		identity &= piv[(size_t)i] == i;
+	}
+	if (!identity && (rc = block_mul(c, S)) != BLZ_OK)
+		return rc;
+	if (k)
+		*k = kk;
+	if (z)
+		for (int row = 0; row < n; row++)
+			for (int j = 0; j < n; j++)
+				z[(size_t)row * n + j] = j < kk ? (s > 0 ? Z0[(size_t)row * n + piv[(size_t)j]] : (uint64_t)(row == piv[(size_t)j]))
+								 : 0;
 	return BLZ_OK;
 }
 

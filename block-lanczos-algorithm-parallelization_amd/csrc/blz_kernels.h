@@ -166,6 +166,20 @@ hipError_t launch_sum_buffers(const void *const *src, int nsrc, void *dst, long 
 /* flag |= any(X != 0) over `words` words */
 hipError_t launch_any_nonzero(const KernelCfg &c, const void *X, int64_t words, int *flag, hipStream_t s);
 
+/* Canonical RREF of the row space of a block (rows x n words of the context's width, row stride ld words; n <= 64).
+ * launch_rref_partial: every workgroup appends its echelon rows to `stack` (at most rref_partial_blocks() * n rows of n
+ * u64 words); ctl[0] = rank-n flag (early exit), ctl[1] = rows appended -- both zeroed by the caller.
+ * launch_rref_merge: one workgroup reduces `rows` stacked rows (or *rows_dev of them when rows_dev != nullptr) to the
+ * RREF E (n x n, rows sorted by pivot column, zero from the rank on); info[0] = rank, info[1 + i] = pivot column of
+ * row i (-1 from the rank on). */
+int rref_partial_blocks(const KernelCfg &c, int64_t rows, int n);
+hipError_t launch_rref_partial(const KernelCfg &c, const void *X, int64_t rows, int ld, int n, u64 *stack, int *ctl,
+			       hipStream_t s);
+hipError_t launch_rref_merge(const KernelCfg &c, const u64 *stack, int64_t rows, const int *rows_dev, int n, u64 *E, int *info,
+			     hipStream_t s);
+/* X <- X * Z in place, row by row (rows x n words of the context's width, row stride ld; Z: n x n u64 residues) */
+hipError_t launch_block_mul(const KernelCfg &c, void *X, int64_t rows, int ld, int n, const u64 *Z, hipStream_t s);
+
 static inline size_t small_words(int n) { return (size_t)6 * n * n; }
 
 #endif

@@ -2998,3 +2998,275 @@ hipError_t launch_any_nonzero(const KernelCfg &c, const void *X, int64_t words, 
 				   (long long)words, flag);
 	return hipGetLastError();
 }
+
+/* ------------------------------------------------------------------ row echelon of a block (kernel basis) */
+
+/*
+ * Canonical RREF of the row space of a tall, skinny block X (rows x n, row stride ld words, n <= 64).  Lanes hold one
+ * column each: a wavefront takes 64 / G rows at a time (G = n rounded up to a power of two), RREF_U of them per lane
+ * in a tile.  The workgroup keeps its echelon E (fully reduced, pivots normalised to 1, rows in insertion order) in LDS.
+ *   fast path  every row of the tile is reduced against E in parallel: y = x - sum_j x[piv j] * E_j (one 128-bit
+ *              accumulator per word, one reduction); at a pivot column this is x - x = 0, so no column is special
+ *   insertion  while the tile has a non-zero remainder, its first one goes through LDS to wavefront 0, which
+ *              normalises it and eliminates its pivot column from E; every lane then reduces its words by the new row
+ *              (one product each).  At most n times in the life of a workgroup.
+ * A workgroup whose rank reaches n raises ctl[0]; every workgroup reads the flag once per tile and stops: a block of
+ * full rank is decided after one tile per workgroup, a deficient one is read exactly once.  The partial form appends
+ * its echelon rows to a stack (ctl[1] = rows so far); the merge form (one workgroup) runs the same loop over the stack
+ * and writes E sorted by pivot column -- the unique RREF, whatever the grid, the row order or the split.
+ */
+#define RREF_U 8
+#define RREF_MAXN 64
+
+MODP_DEV u64 submod(u64 a, u64 b, u64 p) { return a >= b ? a - b : a + (p - b); }
+
+template <typename W>
+MODP_DEV u64 shfl_word(u64 x, int src)
+{
+	if (sizeof(W) == 4)
+		return (u64)(u32)__shfl((int)(u32)x, src, 64);
+	return shfl64(x, src);
+}
+
+template <typename W, int MERS, bool MERGE>
+__global__ void __launch_bounds__(BLOCK)
+k_rref(const W *__restrict__ X, long long rows_arg, const int *rows_dev, int ld, int n, int G, ModP m, int *ctl,
+       u64 *__restrict__ out, int *__restrict__ info)
+{
+	__shared__ u64 E[RREF_MAXN * RREF_MAXN];
+	__shared__ u64 s_row[RREF_MAXN];
+	__shared__ int piv[RREF_MAXN];
+	__shared__ int s_rank, s_stop, s_base, s_first, s_q;
+	const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+	const int col = lane & (G - 1), sub = lane / G, rpw = 64 / G;
+	const int TR = (BLOCK / 64) * RREF_U * rpw;
+	const long long rows = rows_dev ? (long long)*rows_dev : rows_arg;
+	if (tid == 0)
+		s_rank = 0;
+	const long long ntiles = (rows + TR - 1) / TR;
+	for (long long tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
+		if (tid == 0)
+			s_stop = s_rank == n || (!MERGE && __hip_atomic_load(&ctl[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0);
+		__syncthreads();
+		if (s_stop)
+			break;
+		const int r = s_rank;
+		const long long base = tile * TR;
+		u64 y[RREF_U];
+#pragma unroll
+		for (int u = 0; u < RREF_U; u++) {
+			const long long row = base + (long long)((wave * RREF_U + u) * rpw + sub);
+			y[u] = (row < rows && col < n) ? (u64)X[row * ld + col] : 0;
+		}
+		if (r > 0) {
+			Acc acc[RREF_U];
+#pragma unroll
+			for (int u = 0; u < RREF_U; u++)
+				acc_set(acc[u], y[u]);
+			u32 cnt = 0;
+			for (int j = 0; j < r; j++) {
+				const u64 e = E[j * RREF_MAXN + col];
+				const u64 ne = (col < n && e) ? m.p - e : 0;	/* - E_j[col] */
+				const int src = sub * G + piv[j];
+#pragma unroll
+				for (int u = 0; u < RREF_U; u++)
+					acc_mac64(acc[u], shfl_word<W>(y[u], src), ne);
+				if (++cnt == m.chunk) {
+#pragma unroll
+					for (int u = 0; u < RREF_U; u++)
+						acc_set(acc[u], acc_reduce<MERS>(acc[u], m));
+					cnt = 0;
+				}
+			}
+#pragma unroll
+			for (int u = 0; u < RREF_U; u++)
+				y[u] = acc_reduce<MERS>(acc[u], m);
+		}
+		/* insert the tile's first non-zero remainder, reduce the tile by it, repeat: at most n times per workgroup */
+		for (;;) {
+			int first = 0x7fffffff;
+#pragma unroll
+			for (int u = RREF_U - 1; u >= 0; u--)
+				if (y[u] != 0)
+					first = (wave * RREF_U + u) * rpw + sub;
+			if (tid == 0)
+				s_first = 0x7fffffff;
+			__syncthreads();
+			if (first != 0x7fffffff)
+				atomicMin(&s_first, first);
+			__syncthreads();
+			const int t = s_first;
+			if (t == 0x7fffffff || s_rank == n)
+				break;
+#pragma unroll
+			for (int u = 0; u < RREF_U; u++)
+				if ((wave * RREF_U + u) * rpw + sub == t && col < n)
+					s_row[col] = y[u];
+			__syncthreads();
+			if (wave == 0) {
+				const int c = lane;
+				const int rr = s_rank;
+				const u64 x = c < n ? s_row[c] : 0;
+				const int q = __ffsll((long long)__ballot(x != 0)) - 1;
+				const u64 row = mulmod<MERS>(x, dev_invmod_any<MERS>(shfl64(x, q), m), m);	/* row[q] = 1 */
+				for (int j = 0; j < rr; j++) {
+					const u64 f = E[j * RREF_MAXN + q];	/* read by every lane before lane q clears it */
+					if (f && c < n)
+						E[j * RREF_MAXN + c] = submod(E[j * RREF_MAXN + c], mulmod<MERS>(f, row, m), m.p);
+				}
+				E[rr * RREF_MAXN + c] = c < n ? row : 0;
+				if (c < n)
+					s_row[c] = row;
+				if (c == 0) {
+					piv[rr] = q;
+					s_q = q;
+					s_rank = rr + 1;
+				}
+			}
+			__syncthreads();
+			/* y <- y - y[q] * row: zero at q, and still zero at the older pivots (row is zero there) */
+			const int src = sub * G + s_q;
+			const u64 nrow = col < n ? s_row[col] : 0;
+#pragma unroll
+			for (int u = 0; u < RREF_U; u++) {
+				const u64 f = shfl_word<W>(y[u], src);
+				y[u] = submod(y[u], mulmod<MERS>(f, nrow, m), m.p);
+			}
+			if (!MERGE && tid == 0 && s_rank == n)
+				__hip_atomic_store(&ctl[0], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+		}
+	}
+	__syncthreads();
+	const int r = s_rank;
+	if (!MERGE) {
+		if (tid == 0)
+			s_base = r ? atomicAdd(&ctl[1], r) : 0;
+		__syncthreads();
+		for (int k = tid; k < r * n; k += BLOCK)
+			out[(size_t)(s_base + k / n) * n + k % n] = E[(k / n) * RREF_MAXN + k % n];
+		return;
+	}
+	/* rows sorted by pivot column; rows r..n-1 zero */
+	for (int k = tid; k < n * n; k += BLOCK) {
+		const int i = k / n, cc = k % n;
+		if (i < r) {
+			int pos = 0;
+			for (int j = 0; j < r; j++)
+				pos += piv[j] < piv[i];
+			out[(size_t)pos * n + cc] = E[i * RREF_MAXN + cc];
+			if (cc == 0)
+				info[1 + pos] = piv[i];
+		} else {
+			out[(size_t)i * n + cc] = 0;
+			if (cc == 0)
+				info[1 + i] = -1;
+		}
+	}
+	if (tid == 0)
+		info[0] = r;
+}
+
+static int rref_group(int n)
+{
+	int G = 1;
+	while (G < n)
+		G <<= 1;
+	return G;
+}
+
+int rref_partial_blocks(const KernelCfg &c, int64_t rows, int n)
+{
+	const int TR = (BLOCK / 64) * RREF_U * (64 / rref_group(n));
+	const int64_t tiles = (rows + TR - 1) / TR;
+	const int64_t b = std::min<int64_t>(tiles, (int64_t)c.num_cu * 2);
+	return (int)std::max<int64_t>(b, 1);
+}
+
+template <typename W, int MERS, bool MERGE>
+static void rref_launch(int blocks, const void *X, int64_t rows, const int *rows_dev, int ld, int n, const ModP &m, int *ctl,
+			u64 *out, int *info, hipStream_t s)
+{
+	hipLaunchKernelGGL((k_rref<W, MERS, MERGE>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, (const W *)X, (long long)rows,
+			   rows_dev, ld, n, rref_group(n), m, ctl, out, info);
+}
+
+hipError_t launch_rref_partial(const KernelCfg &c, const void *X, int64_t rows, int ld, int n, u64 *stack, int *ctl,
+			       hipStream_t s)
+{
+	if (n < 1 || n > RREF_MAXN)
+		return hipErrorInvalidValue;
+	const int b = rref_partial_blocks(c, rows, n);
+	if (c.word == 4)
+		(c.mers == 31 ? rref_launch<u32, 31, false> : rref_launch<u32, 0, false>)(b, X, rows, nullptr, ld, n, c.m, ctl, stack,
+											   nullptr, s);
+	else
+		(c.mers == 61 ? rref_launch<u64, 61, false> : rref_launch<u64, 0, false>)(b, X, rows, nullptr, ld, n, c.m, ctl, stack,
+											   nullptr, s);
+	return hipGetLastError();
+}
+
+hipError_t launch_rref_merge(const KernelCfg &c, const u64 *stack, int64_t rows, const int *rows_dev, int n, u64 *E, int *info,
+			     hipStream_t s)
+{
+	if (n < 1 || n > RREF_MAXN)
+		return hipErrorInvalidValue;
+	auto f = c.mers == 61 ? rref_launch<u64, 61, true> : c.mers == 31 ? rref_launch<u64, 31, true> : rref_launch<u64, 0, true>;
+	f(1, stack, rows, rows_dev, n, n, c.m, nullptr, E, info, s);
+	return hipGetLastError();
+}
+
+/* X <- X * Z in place (rows x n, row stride ld words; Z: n x n u64 residues, row-major), lane = column */
+template <typename W, int MERS>
+__global__ void __launch_bounds__(BLOCK)
+k_block_mul(W *__restrict__ X, long long rows, int ld, int n, int G, const u64 *__restrict__ Z, ModP m)
+{
+	__shared__ u64 Zs[RREF_MAXN * RREF_MAXN];
+	for (int k = threadIdx.x; k < RREF_MAXN * RREF_MAXN; k += BLOCK) {
+		const int j = k / RREF_MAXN, cc = k % RREF_MAXN;
+		Zs[k] = (j < n && cc < n) ? Z[j * n + cc] : 0;
+	}
+	__syncthreads();
+	const int lane = threadIdx.x & 63, col = lane & (G - 1), sub = lane / G, rpw = 64 / G;
+	const long long groups = (rows + rpw - 1) / rpw, waves = (long long)gridDim.x * (BLOCK / 64);
+	for (long long g = (long long)blockIdx.x * (BLOCK / 64) + (threadIdx.x >> 6); g < groups; g += waves) {
+		const long long row = g * rpw + sub;
+		const bool mine = row < rows && col < n;
+		const u64 x = mine ? (u64)X[row * ld + col] : 0;
+		Acc acc;
+		acc_zero(acc);
+		u32 cnt = 0;
+		for (int j = 0; j < n; j++) {
+			acc_mac64(acc, shfl_word<W>(x, sub * G + j), Zs[j * RREF_MAXN + col]);
+			if (++cnt == m.chunk) {
+				acc_set(acc, acc_reduce<MERS>(acc, m));
+				cnt = 0;
+			}
+		}
+		if (mine)
+			X[row * ld + col] = (W)acc_reduce<MERS>(acc, m);
+	}
+}
+
+hipError_t launch_block_mul(const KernelCfg &c, void *X, int64_t rows, int ld, int n, const u64 *Z, hipStream_t s)
+{
+	if (n < 1 || n > RREF_MAXN)
+		return hipErrorInvalidValue;
+	if (rows <= 0)
+		return hipSuccess;
+	const int G = rref_group(n);
+	const int64_t groups = (rows + 64 / G - 1) / (64 / G);
+	const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)c.num_cu * 8));
+	const dim3 grid((unsigned)blocks), blk(BLOCK);
+	if (c.word == 4) {
+		if (c.mers == 31)
+			hipLaunchKernelGGL((k_block_mul<u32, 31>), grid, blk, 0, s, (u32 *)X, (long long)rows, ld, n, G, Z, c.m);
+		else
+			hipLaunchKernelGGL((k_block_mul<u32, 0>), grid, blk, 0, s, (u32 *)X, (long long)rows, ld, n, G, Z, c.m);
+	} else {
+		if (c.mers == 61)
+			hipLaunchKernelGGL((k_block_mul<u64, 61>), grid, blk, 0, s, (u64 *)X, (long long)rows, ld, n, G, Z, c.m);
+		else
+			hipLaunchKernelGGL((k_block_mul<u64, 0>), grid, blk, 0, s, (u64 *)X, (long long)rows, ld, n, G, Z, c.m);
+	}
+	return hipGetLastError();
+}

@@ -2124,6 +2124,115 @@ done:
 	return rc;
 }
 
+/* rank of a kernel block: the RREF of its row space, row by row (the GPU's k_rref restated), stopping at full rank */
+
+static uint64_t host_invmod(uint64_t a, uint64_t p)
+{
+	__int128 t = 0, nt = 1, r = p, nr = a % p;
+	while (nr != 0) {
+		const __int128 q = r / nr, t2 = t - q * nt, r2 = r - q * nr;
+		t = nt;
+		nt = t2;
+		r = nr;
+		nr = r2;
+	}
+	return (uint64_t)(t < 0 ? t + p : t);
+}
+
+int blz_check_independent(const char *kernel_path, uint64_t prime, int *rank, int *cols)
+{
+	if (!kernel_path || prime < 2 || prime >= (1ull << 62))
+		return blz_fail(BLZ_EINVAL, "blz_check_independent: bad argument");
+	int fd = open(kernel_path, O_RDONLY);
+	struct stat st;
+	if (fd < 0 || fstat(fd, &st) != 0 || st.st_size == 0) {
+		if (fd >= 0)
+			close(fd);
+		return blz_fail(BLZ_EIO, "cannot open %s", kernel_path);
+	}
+	char *base = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+	close(fd);
+	if (base == MAP_FAILED)
+		return blz_fail(BLZ_EIO, "mmap %s: %s", kernel_path, strerror(errno));
+	cursor c = { base, base + st.st_size };
+	char line[1100];
+	long long nk = 0, n = 0;
+	uint64_t *x = NULL, *E = NULL;
+	int *piv = NULL, r = 0, rc = BLZ_OK;
+	if (next_line(&c, line, sizeof line) || (rc = check_banner(line, 1)) != BLZ_OK) {
+		if (rc == BLZ_OK)
+			rc = blz_fail(BLZ_EFORMAT, "Could not process Matrix Market banner.");
+		goto done;
+	}
+	do {
+		if (next_line(&c, line, sizeof line)) {
+			rc = blz_fail(BLZ_EIO, "Cannot read kernel vector block size size");
+			goto done;
+		}
+	} while (line[0] == '%');
+	if (sscanf(line, "%lld %lld", &nk, &n) != 2 || nk < 0 || n < 1 || n > (1 << 20)) {
+		rc = blz_fail(BLZ_EIO, "Cannot read kernel vector block size size");
+		goto done;
+	}
+	x = malloc(sizeof *x * (size_t)(nk * n + 1));
+	E = calloc((size_t)(n * n), sizeof *E);
+	piv = calloc((size_t)n, sizeof *piv);
+	if (!x || !E || !piv) {
+		rc = blz_fail(BLZ_ENOMEM, "cannot allocate the kernel block");
+		goto done;
+	}
+	for (long long k = 0; k < n; k++)		/* column-major */
+		for (long long i = 0; i < nk; i++) {
+			long long w;
+			if (next_int(&c, &w)) {
+				rc = blz_fail(BLZ_EIO, "parse error entry %lld, %lld", i, k);
+				goto done;
+			}
+			const uint64_t word = w < 0 ? (uint64_t)(uint32_t)(int32_t)w : (uint64_t)w;
+			if (word >= prime) {
+				rc = blz_fail(BLZ_EINVAL, "entry %lld, %lld out of bound", i, k);
+				goto done;
+			}
+			x[i * n + k] = word;
+		}
+	/* E holds r fully reduced rows with 1 at their pivot: y <- y - sum_j y[piv j] E_j, then insert y if it is not zero */
+	for (long long i = 0; i < nk && r < n; i++) {
+		uint64_t *y = x + i * n;
+		for (int j = 0; j < r; j++) {
+			const uint64_t f = y[piv[j]];
+			if (f)
+				for (long long k = 0; k < n; k++)
+					y[k] = (uint64_t)(((unsigned __int128)y[k] + (unsigned __int128)(prime - f) * E[j * n + k]) % prime);
+		}
+		long long q = 0;
+		while (q < n && y[q] == 0)
+			q++;
+		if (q == n)
+			continue;
+		const uint64_t inv = host_invmod(y[q], prime);
+		for (long long k = 0; k < n; k++)
+			y[k] = (uint64_t)((unsigned __int128)y[k] * inv % prime);
+		for (int j = 0; j < r; j++) {
+			const uint64_t f = E[j * n + q];
+			if (f)
+				for (long long k = 0; k < n; k++)
+					E[j * n + k] = (uint64_t)(((unsigned __int128)E[j * n + k] + (unsigned __int128)(prime - f) * y[k]) % prime);
+		}
+		memcpy(E + (long long)r * n, y, (size_t)n * sizeof *E);
+		piv[r++] = (int)q;
+	}
+	if (rank)
+		*rank = r;
+	if (cols)
+		*cols = (int)n;
+done:
+	free(x);
+	free(E);
+	free(piv);
+	munmap(base, (size_t)st.st_size);
+	return rc;
+}
+
 /* -------------------------------------------------------------------------- checkpoints */
 
 typedef struct {

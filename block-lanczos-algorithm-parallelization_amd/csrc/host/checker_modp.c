@@ -2,6 +2,7 @@
  * checker_modp -- drop-in for the reference's verifier (checker_modp.c) with residues widened to 64 bits, so
  * that kernels computed modulo primes above 2^31-1 can be checked too.  Same flags (:43-76), same verdict
  * lines and exit codes: "OK" + exit 0, or a KO message + exit 1.  Plain C, no GPU.
+ * --independent (no reference counterpart) also asks that the kernel vectors be linearly independent mod P.
  */
 #define _GNU_SOURCE
 #include <err.h>
@@ -16,11 +17,11 @@ int main(int argc, char **argv)
 	struct option longopts[] = {
 		{"matrix", required_argument, NULL, 'm'}, {"kernel", required_argument, NULL, 'k'},
 		{"prime", required_argument, NULL, 'p'}, {"right", no_argument, NULL, 'r'},
-		{"left", no_argument, NULL, 'l'}, {NULL, 0, NULL, 0}
+		{"left", no_argument, NULL, 'l'}, {"independent", no_argument, NULL, 'i'}, {NULL, 0, NULL, 0}
 	};
 	char *matrix = NULL, *kernel = NULL;
 	unsigned long long prime = 0;
-	int right = 0, ch;
+	int right = 0, independent = 0, ch;
 	while ((ch = getopt_long(argc, argv, "", longopts, NULL)) != -1) {
 		switch (ch) {
 		case 'm': matrix = optarg; break;
@@ -28,6 +29,7 @@ int main(int argc, char **argv)
 		case 'p': prime = strtoull(optarg, NULL, 10); break;
 		case 'r': right = 1; break;
 		case 'l': right = 0; break;
+		case 'i': independent = 1; break;
 		default: errx(1, "Unknown option\n");
 		}
 	}
@@ -39,6 +41,7 @@ int main(int argc, char **argv)
 		printf("--prime P                   compute modulo P (up to 2**62)\n");
 		printf("--right                     check right kernel vectors\n");
 		printf("--left                      check left kernel vectors [default]\n");
+		printf("--independent               also check that the kernel vectors are linearly independent\n");
 		exit(0);
 	}
 	printf("Reading Matrix from %s and kernel from %s\n", matrix, kernel);
@@ -47,6 +50,14 @@ int main(int argc, char **argv)
 	const int rc = blz_check_kernel(matrix, kernel, prime, right, (int64_t *)&row, &col);
 	if (rc == 0) {
 		printf("OK\n");
+		if (independent) {
+			int rank = 0, cols = 0;
+			if (blz_check_independent(kernel, prime, &rank, &cols) != BLZ_OK)
+				errx(1, "%s", blz_last_error());
+			if (rank < cols)
+				errx(1, "KO: kernel vectors are linearly dependent (rank %d < %d)", rank, cols);
+			printf("OK: %d independent vectors\n", cols);
+		}
 		exit(EXIT_SUCCESS);
 	}
 	if (rc == 1)

@@ -29,7 +29,7 @@
 static long n = 1;
 static uint64_t prime;
 static char *matrix_filename, *kernel_filename;
-static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache;
+static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis;
 static int stop_after = -1, checkpoint_timer = 60, device, gpus = 1;
 
 static double wtime(void)
@@ -72,12 +72,15 @@ static void usage(char **argv)
 	printf("--cache                     keep the renumbered CSR(M), CSR(M^T) and the row partition next to the matrix\n");
 	printf("                            (FILENAME.<key>.blzcache, keyed by content hash, prime, n, orientation, GPUs);\n");
 	printf("                            a later run with the same arguments skips the renumbering and the CSR builds\n");
+	printf("--basis                     reduce the final block to independent kernel vectors (exact elimination mod P\n");
+	printf("                            on the GPU) and store only those with --output-file\n");
 	printf("--device D                  first HIP device to run on [default 0]\n");
 	printf("--gpus G                    row-partition the matrix over G GPUs of this node (devices D..D+G-1), RCCL\n");
 	printf("                            all-gather of the block before each product [default 1]\n");
 	printf("\n");
 	printf("The --matrix and --prime arguments are required\n");
 	printf("The --stop-after and --output-file arguments mutually exclusive\n");
+	printf("The --stop-after and --basis arguments mutually exclusive\n");
 	exit(0);
 }
 
@@ -90,7 +93,7 @@ static void process_command_line_options(int argc, char **argv)
 		{"stop-after", required_argument, NULL, 's'}, {"checkpoint", optional_argument, NULL, 'c'},
 		{"load-checkpoint", no_argument, NULL, 'L'}, {"device", required_argument, NULL, 'd'},
 		{"gpus", required_argument, NULL, 'g'}, {"verify", no_argument, NULL, 'V'},
-		{"cache", no_argument, NULL, 'C'}, {"help", no_argument, NULL, 'h'}, {NULL, 0, NULL, 0}
+		{"cache", no_argument, NULL, 'C'}, {"basis", no_argument, NULL, 'B'}, {"help", no_argument, NULL, 'h'}, {NULL, 0, NULL, 0}
 	};
 	int ch;
 	while ((ch = getopt_long(argc, argv, "", longopts, NULL)) != -1) {
@@ -114,6 +117,7 @@ static void process_command_line_options(int argc, char **argv)
 		case 'g': gpus = atoi(optarg); break;
 		case 'V': verify = true; break;
 		case 'C': use_cache = true; break;
+		case 'B': basis = true; break;
 		case 'h': usage(argv); break;
 		default: errx(1, "Unknown option\n");
 		}
@@ -121,6 +125,8 @@ static void process_command_line_options(int argc, char **argv)
 	if (matrix_filename == NULL || prime == 0)	/* sequential/lanczos_modp.c:183-187 */
 		usage(argv);
 	if (kernel_filename != NULL && stop_after > 0)
+		usage(argv);
+	if (basis && stop_after > 0)
 		usage(argv);
 	if (prime >= (1ull << 62))
 		errx(1, "p is capped at 2**62 - 1.");
@@ -206,7 +212,7 @@ static void correctness_tests(blz_ctx *ctx)
  * blz_comm_init / blz_iterate / blz_final_check must be entered by all ranks concurrently).  With --gpus 1 the
  * operation runs on the calling thread.
  */
-enum { OP_CREATE, OP_COMM, OP_MATRIX, OP_INIT, OP_SET_VP, OP_ITERATE, OP_GET, OP_FINAL, OP_SNAP, OP_DESTROY };
+enum { OP_CREATE, OP_COMM, OP_MATRIX, OP_INIT, OP_SET_VP, OP_ITERATE, OP_GET, OP_FINAL, OP_BASIS, OP_SNAP, OP_DESTROY };
 
 static struct {
 	blz_ctx *ctx[64];
@@ -216,7 +222,7 @@ static struct {
 	int op, todo, block;
 	uint64_t *host, *host2;
 	int64_t its;
-	int done[64], stopped[64], nonzero[64], zero[64], rc[64];
+	int done[64], stopped[64], nonzero[64], zero[64], rank_vtm[64], k[64], rc[64];
 	float ms[64];
 	char err[64][512];
 } team;
@@ -256,6 +262,11 @@ static void *team_worker(void *arg)
 		break;
 	case OP_FINAL:
 		rc = blz_final_check(team.ctx[g], &team.nonzero[g], &team.zero[g]);
+		break;
+	case OP_BASIS:		/* both collective */
+		rc = blz_block_rref(team.ctx[g], BLZ_TMP, NULL, &team.rank_vtm[g], NULL);
+		if (rc == BLZ_OK)
+			rc = blz_kernel_basis(team.ctx[g], &team.k[g], NULL);
 		break;
 	case OP_SNAP:
 		rc = blz_snapshot_begin(team.ctx[g]);
@@ -520,7 +531,25 @@ int main(int argc, char **argv)
 	}
 	printf("  - Terminated in %.1fs after %d iterations\n", wtime() - start, n_iterations);
 
-	if (kernel_filename) {
+	int k = (int)n;
+	if (basis) {		/* no reference counterpart: blz_kernel_basis, include/blz.h */
+		team_run(OP_BASIS);
+		k = team.k[0];
+		printf("Kernel basis:\n");
+		if (k > 0)
+			printf("  - %d independent kernel vectors of %ld (rank of vt*M: %d)\n", k, n, team.rank_vtm[0]);
+		else
+			printf("  - KO: no kernel vector\n");
+	}
+	if (kernel_filename && k == 0) {
+		printf("Not saving result (no kernel vector)\n");
+	} else if (kernel_filename && k < n) {
+		team_get(BLZ_V, v);
+		for (int64_t i = 0; i < nrows; i++)	/* the basis is in columns 0..k-1 */
+			memmove(v + i * k, v + i * n, (size_t)k * sizeof *v);
+		printf("Saving result in %s\n", kernel_filename);
+		CHECK(blz_save_block(kernel_filename, nrows, k, v));
+	} else if (kernel_filename) {
 		team_get(BLZ_V, v);
 		printf("Saving result in %s\n", kernel_filename);
 		CHECK(blz_save_block(kernel_filename, nrows, (int)n, v));

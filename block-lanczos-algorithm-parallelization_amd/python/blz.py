@@ -328,6 +328,13 @@ def check_kernel(matrix_path, kernel_path, prime, right=False):
     return rc
 
 
+def check_independent(kernel_path, prime):
+    """blz_check_independent(): (rank, columns) of a kernel block file mod prime (host only)."""
+    rank, cols = C.c_int(0), C.c_int(0)
+    check(lib().blz_check_independent(kernel_path.encode(), C.c_uint64(prime), C.byref(rank), C.byref(cols)))
+    return int(rank.value), int(cols.value)
+
+
 def checkpoint_save(path, prime, n, right, nrows, iterations, v, p):
     check(lib().blz_checkpoint_save(path.encode(), C.c_uint64(prime), C.c_int(n), C.c_int(int(right)),
                                     C.c_int64(nrows), C.c_int64(iterations), ptr(u64(v)), ptr(u64(p))))
@@ -506,6 +513,22 @@ class Context:
         check(lib().blz_final_check(self.h, C.byref(a), C.byref(b)))
         return bool(a.value), bool(b.value)
 
+    def block_rref(self, block):
+        """blz_block_rref(): (E as an n x n array, rank, pivot columns) of the row space of `block`, all ranks merged."""
+        E = np.zeros(self.n * self.n, dtype=np.uint64)
+        rank = C.c_int(0)
+        piv = np.zeros(self.n, dtype=np.int32)
+        check(lib().blz_block_rref(self.h, C.c_int(block), ptr(E), C.byref(rank),
+                                   piv.ctypes.data_as(C.POINTER(C.c_int32))))
+        return E.reshape(self.n, self.n), int(rank.value), [int(q) for q in piv[:rank.value]]
+
+    def kernel_basis(self):
+        """blz_kernel_basis(): (k, z as an n x n array); V then holds the k basis vectors in its first k columns."""
+        k = C.c_int(0)
+        z = np.zeros(self.n * self.n, dtype=np.uint64)
+        check(lib().blz_kernel_basis(self.h, C.byref(k), ptr(z)))
+        return int(k.value), z.reshape(self.n, self.n)
+
     def time_kernel(self, which, reps):
         ms = C.c_float(0)
         check(lib().blz_time_kernel(self.h, C.c_int(which), C.c_int(reps), C.byref(ms)))
@@ -554,8 +577,12 @@ def comm_unique_id():
     return bytes(buf)
 
 
-def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0):
-    """block_lanczos(), sequential/lanczos_modp.c:585-669, on one GPU.  Returns dict(v, tmp, iterations)."""
+def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0, basis=False):
+    """block_lanczos(), sequential/lanczos_modp.c:585-669, on one GPU.  Returns dict(v, tmp, iterations).
+    basis=True (not with stop_after): also reduce the final block to independent kernel vectors (blz_kernel_basis) --
+    adds basis (rows x k array), k and z to the result; v, tmp and p stay those of the plain solve."""
+    if basis and stop_after > 0:
+        raise ValueError("basis=True needs a run to the end (stop_after < 0)")
     with Context(prime, n, device) as ctx:
         ctx.set_matrix(M, right)
         ctx.init_v()
@@ -568,5 +595,9 @@ def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0):
             _, stopped, _ = ctx.iterate(todo)
             if stopped:
                 break
-        return dict(v=ctx.get_block(V), tmp=ctx.get_block(TMP), p=ctx.get_block(P), iterations=ctx.iterations,
-                    final_check=ctx.final_check())
+        out = dict(v=ctx.get_block(V), tmp=ctx.get_block(TMP), p=ctx.get_block(P), iterations=ctx.iterations,
+                   final_check=ctx.final_check())
+        if basis:
+            k, z = ctx.kernel_basis()
+            out.update(k=k, z=z, basis=ctx.get_block(V).reshape(-1, n)[:, :k].copy())
+        return out

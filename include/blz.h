@@ -208,6 +208,11 @@ int blz_save_block(const char *path, int64_t nrows, int n, const uint64_t *v);
 int blz_check_kernel(const char *matrix_path, const char *kernel_path, uint64_t prime, int right,
 		     int64_t *bad_row, int *bad_col);
 
+/* Rank of a kernel block file (MatrixMarket "array integer general", column-major, as blz_save_block writes it) mod
+ * prime: *rank = rank of its *cols columns, found by a row-by-row reduced echelon that stops once the rank equals the
+ * column count.  No reference counterpart (checker_modp.c only tests v != 0 and x^T M = 0).  Host only, no GPU. */
+int blz_check_independent(const char *kernel_path, uint64_t prime, int *rank, int *cols);
+
 /* Checkpoints (openMP/lanczos_modp.c:571-676, :933-940, :1013-1022).  blz_checkpoint_save writes
  * one binary file atomically (tmp + rename): v, p, iteration count, prime, n, shape.
  * The *_ref_text pair reads/writes the reference's five text files (v.txt tmp.txt Av.txt p.txt
@@ -318,6 +323,24 @@ int blz_set_iterations(blz_ctx *ctx, int64_t iterations);	/* --load-checkpoint *
 
 /* final_check(), :560-582, on V and on TMP (= M^T v of the last iteration). */
 int blz_final_check(blz_ctx *ctx, int *v_nonzero, int *vtm_zero);
+
+/* Canonical reduced row echelon form of the row space of a block (any of the four; with several ranks every rank's rows,
+ * merged through one all-gather of n x n words: collective, like blz_final_check).  rref = n x n words, row-major, rows
+ * sorted by pivot column, rows from the rank on zero; *rank; pivots[i] = pivot column of row i, -1 from the rank on.  Any
+ * output may be NULL.  The RREF is unique, so the words do not depend on the row order, the solver's renumbering, repeated
+ * rows or the split over ranks.  A block of full rank is decided after one tile per workgroup (microseconds); a deficient
+ * one is read once.  No reference counterpart; the nearest is final_check(), sequential/lanczos_modp.c:560-582. */
+int blz_block_rref(blz_ctx *ctx, int block, uint64_t *rref, int *rank, int32_t *pivots);
+
+/* Independent kernel vectors from the final block, in the state blz_iterate leaves on stop (TMP = the product of V):
+ *   1. E1 = RREF(TMP), rank s, pivots P
+ *   2. Z0 = the canonical null basis of E1: one column per free column f (not in P), ascending, with 1 at f, -E1[i][f] at
+ *      pivot P[i], 0 elsewhere (Z0 = I when s = 0)
+ *   3. Y = V Z0 (row by row, in place)
+ *   4. E2 = RREF(Y): the basis is Y's columns at E2's pivots, k = rank(E2)
+ * Leaves the basis in columns 0..k-1 of V and zeroes the others; z (n x n, may be NULL) gets the combination of the
+ * original columns of V that gives each basis vector (column j; zero for j >= k).  Collective with several ranks. */
+int blz_kernel_basis(blz_ctx *ctx, int *k, uint64_t *z);
 
 /* Asynchronous snapshot of (v, p, iteration count) for checkpoints (openMP/lanczos_modp.c:1013-1022 stops its loop
  * for them).  blz_snapshot_begin, called between two blz_iterate calls, enqueues the device-to-host copies of this
