@@ -2,7 +2,7 @@
 sequential/lanczos_modp.c:189-193) no reference output can exist.  Here the
 oracle's SAME code path (already pinned to the reference at small p by
 test_oracle_golden.py) is cross-checked at p = 2^61-1 and other wide primes against
-an independent restatement in exact Python integers, and against the reference's
+an independent restatement in exact Python integers (tests/exact_ref.py), and against the reference's
 own in-loop invariants (correctness_tests / final_check,
 sequential/lanczos_modp.c:532-582).
 """
@@ -12,80 +12,11 @@ import numpy as np
 import pytest
 
 import oracle as orc
+from exact_ref import iteration as py_iteration
 
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 P61 = (1 << 61) - 1
 WIDE_PRIMES = [P61, (1 << 31) - 1, 4294967311, 2305843009213693907, (1 << 62) - 57]
-
-
-def py_spmv(M, x, transpose, n, p):
-    rows_out = M.ncols if transpose else M.nrows
-    y = [0] * (rows_out * n)
-    for i, j, a in zip(M.i.tolist(), M.j.tolist(), M.x.tolist()):
-        r, c = (j, i) if transpose else (i, j)
-        for l in range(n):
-            y[r * n + l] = (y[r * n + l] + a * x[c * n + l]) % p
-    return y
-
-
-def py_semi_inverse(M_, n, p):
-    def sweep(a, w, d):
-        cnt = 0
-        for j in range(n):
-            piv = next((i for i in range(j, n) if a[i * n + j] != 0), None)
-            if piv is None:
-                continue
-            d[j] = 1
-            cnt += 1
-            inv = pow(a[piv * n + j], -1, p)
-            for k in range(n):
-                a[piv * n + k] = a[piv * n + k] * inv % p
-                if w is not None:
-                    w[piv * n + k] = w[piv * n + k] * inv % p
-            for k in range(n):
-                a[j * n + k], a[piv * n + k] = a[piv * n + k], a[j * n + k]
-                if w is not None:
-                    w[j * n + k], w[piv * n + k] = w[piv * n + k], w[j * n + k]
-            for i in range(n):
-                if i == j:
-                    continue
-                m = a[i * n + j]
-                for k in range(n):
-                    a[i * n + k] = (a[i * n + k] - m * a[j * n + k]) % p
-                    if w is not None:
-                        w[i * n + k] = (w[i * n + k] - m * w[j * n + k]) % p
-        return cnt
-
-    a = list(M_)
-    sel = [0] * n
-    sweep(a, None, sel)
-    a = [M_[i * n + j] if sel[i] and sel[j] else 0 for i in range(n) for j in range(n)]
-    w = [1 if i == j and sel[i] else 0 for i in range(n) for j in range(n)]
-    d = [0] * n
-    return sweep(a, w, d), w, d
-
-
-def py_iteration(M, n, p, right, v, pb):
-    nrows = M.ncols if right else M.nrows
-    tmp = py_spmv(M, v, not right, n, p)
-    Av = py_spmv(M, tmp, right, n, p)
-    vtAv = [sum(v[r * n + a] * Av[r * n + b] for r in range(nrows)) % p for a in range(n) for b in range(n)]
-    vtAAv = [sum(Av[r * n + a] * Av[r * n + b] for r in range(nrows)) % p for a in range(n) for b in range(n)]
-    npiv, winv, d = py_semi_inverse(vtAv, n, p)
-    if npiv == 0:
-        return npiv, v, pb, tmp, (vtAv, vtAAv, winv, d)
-    spl = [vtAAv[i * n + j] if d[j] else vtAv[i * n + j] for i in range(n) for j in range(n)]
-    c = [(-sum(winv[i * n + k] * spl[k * n + j] for k in range(n))) % p for i in range(n) for j in range(n)]
-    vd = [(-vtAv[i * n + j]) % p if d[j] else 0 for i in range(n) for j in range(n)]
-    nv, npb = [0] * (nrows * n), [0] * (nrows * n)
-    for r in range(nrows):
-        for j in range(n):
-            t = Av[r * n + j] if d[j] else v[r * n + j]
-            t += sum(v[r * n + k] * c[k * n + j] + pb[r * n + k] * vd[k * n + j] for k in range(n))
-            nv[r * n + j] = t % p
-            q = 0 if d[j] else pb[r * n + j]
-            npb[r * n + j] = (q + sum(v[r * n + k] * winv[k * n + j] for k in range(n))) % p
-    return npiv, nv, npb, tmp, (vtAv, vtAAv, winv, d)
 
 
 @pytest.mark.parametrize("p", WIDE_PRIMES)
