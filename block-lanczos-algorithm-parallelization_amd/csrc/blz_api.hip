@@ -888,6 +888,70 @@ extern "C" int64_t blz_panel_rows(const blz_ctx *c, int transpose, double *share
 	return c->csr[t].empty() ? 0 : c->csr[t][0].panel_rows;
 }
 
+/* does blz_iterate give the second product the inner products as its epilogue? (enqueue_iteration asks the same) */
+static inline bool iteration_fuses(const blz_ctx *c)
+{
+	return c->fuse_dot && !c->fuse_local_off && spmv_dot_supported(c->cfg) && c->count[0] > 0 && !c->short_side[c->right];
+}
+
+static void plan_launch(const SpmvGrids &g, blz_plan_launch *o)
+{
+	o->form = g.form == SPMV_FORM_PANEL ? BLZ_FORM_PANEL : (g.form == SPMV_FORM_STAGED ? BLZ_FORM_STAGED : BLZ_FORM_SPMV);
+	o->xcd_ranges = g.xcd;
+	o->split_log2 = g.split_log2;
+	o->st_gathers = g.gathers;
+	o->grid_stream = g.blocks;
+	o->grid_heavy = g.hb;
+	o->grid_combine = g.cb;
+	o->grid_medium = g.mb;
+}
+
+extern "C" int blz_slab_plan(const blz_ctx *c, int transpose, int piece, blz_plan *out)
+{
+	if (!c || !out || !c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "blz_slab_plan: no context, no matrix or out is NULL");
+	const int t = transpose ? 1 : 0;
+	const bool sh = c->short_side[t];
+	if (piece < 0 || piece >= (sh ? 1 : (int)c->csr[t].size()))
+		return blz_fail(BLZ_EINVAL, "blz_slab_plan: piece %d of %d", piece, sh ? 1 : (int)c->csr[t].size());
+	const DevCsr &A = sh ? c->csr_short[t] : c->csr[t][(size_t)piece];
+	memset(out, 0, sizeof *out);
+	out->rows = A.rows;
+	out->cols = A.cols;
+	out->nnz = A.nnz;
+	out->pieces = sh ? 1 : (int)c->csr[t].size();
+	out->width = c->cfg.n;
+	out->chunk = (int32_t)c->cfg.m.chunk;
+	out->num_cu = c->cfg.num_cu;
+	out->max_dot_blocks = c->max_dot_blocks;
+	out->tail_batch = A.tail_batch;
+	out->xcd_ranges = A.xcd_ranges;
+	out->heavy_thr = A.heavy_thr;
+	out->n_medium = A.n_medium;
+	out->n_heavy = A.n_heavy;
+	out->n_multi = A.n_multi;
+	out->st_ok = A.st_ok;
+	out->st_tr = A.st_tr;
+	out->st_pair = A.st_pair;
+	out->st_dyn = A.st_dyn;
+	out->st_deep = A.st_deep;
+	out->st_interleave = A.st_interleave;
+	out->st_capw = A.st_capw;
+	out->st_per_cu = A.st_per_cu;
+	out->panel_rows = A.panel_rows;
+	out->packed = A.palette ? 1 : (A.val ? 2 : 0);
+	out->dot_supported = spmv_dot_supported(c->cfg);
+	out->fuse_local_off = c->fuse_local_off;
+	out->short_side = sh;
+	out->locality = A.locality;
+	plan_launch(spmv_grids(c->cfg, A, false, 0), &out->plain);
+	if (out->dot_supported && !sh)
+		plan_launch(spmv_grids(c->cfg, A, true, c->max_dot_blocks), &out->dot);
+	/* the epilogue rides on the last piece of the second product */
+	out->fused = t == (c->right ? 1 : 0) && iteration_fuses(c) && piece == out->pieces - 1;
+	return BLZ_OK;
+}
+
 extern "C" int64_t blz_matrix_stream_bytes(const blz_ctx *c, int transpose)
 {
 	if (!c || !c->have_matrix)
@@ -1439,7 +1503,7 @@ static int enqueue_iteration(blz_ctx *c)
 {
 	int rc;
 	if ((rc = enqueue_product(c, !c->right, BLZ_V, BLZ_TMP, false, nullptr)) != BLZ_OK) return rc;	/* :635 */
-	if (c->fuse_dot && !c->fuse_local_off && spmv_dot_supported(c->cfg) && c->count[0] > 0 && !c->short_side[c->right]) {
+	if (iteration_fuses(c)) {
 		int nb = 0;							/* :636 + :640 in one kernel */
 		if ((rc = enqueue_product(c, c->right, BLZ_TMP, BLZ_AV, true, &nb)) != BLZ_OK) return rc;
 		{

@@ -103,6 +103,20 @@ void spmv_plan_panel(const KernelCfg &c, const u32 *row_ptr, DevCsr &D, int64_t 
 /* rows of a slab with more entries than this get a workgroup each (DevCsr::heavy) */
 u32 spmv_heavy_threshold(const KernelCfg &c, int64_t rows, int64_t nnz);
 
+/* The launches of one product of a slab: what launch_spmv (dot = false) / launch_spmv_dot (dot = true, with room for
+ * max_blocks partial rows) will do.  The dispatch functions take their grids from the same functions. */
+enum { SPMV_FORM_STREAM = 0, SPMV_FORM_STAGED = 1, SPMV_FORM_PANEL = 2 };
+struct SpmvGrids {
+	int form;		/* k_spmv / k_spmv_dot, k_spmv_staged, k_spmv_panel */
+	long long blocks;	/* workgroups of that launch (0: nothing is launched) */
+	long long hb, cb, mb;	/* workgroups of k_spmv_heavy, k_spmv_heavy_combine, k_spmv_wave (0: not launched) */
+	int split_log2;		/* k_spmv: 2^split_log2 lane groups share a row */
+	bool xcd;		/* k_spmv / k_spmv_dot walk per-XCD row ranges (the other two forms always do) */
+	int gathers;		/* k_spmv_staged: gathers in flight per lane, 4 or 8 */
+	bool ok;		/* false: the launch is refused (no room for its partial rows) */
+};
+SpmvGrids spmv_grids(const KernelCfg &c, const DevCsr &A, bool dot, int max_blocks);
+
 /* Y[rows x n] = A * X, X addressed through A.col_idx (row-major, n words per row).
  * sequential/lanczos_modp.c:266-287 */
 hipError_t launch_spmv(const KernelCfg &c, const DevCsr &A, const void *X, void *Y, int accum, const DevCtl *ctl,

@@ -386,30 +386,34 @@ u32 spmv_heavy_threshold(const KernelCfg &c, int64_t rows, int64_t nnz)
 	return base << spmv_split_log2(c, rows, nnz);
 }
 
-/* the same product with the matrix stream staged through LDS (further down: it shares DotState with k_spmv_dot) */
-template <typename W, int MERS, bool DOT>
-static hipError_t staged_dispatch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum,
-				  u64 *partial, int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s);
+/* ------------------------------------------------------------------ grids of a product (launches and blz_slab_plan)
+ * What the dispatch functions below launch for a slab, computed in one place: they call these, and so does the
+ * read-only plan hook (spmv_grids), so a test that reads the plan reads the launch. */
 
-/* ... and with the densest block rows of the operand resident in LDS (k_spmv_panel, below) */
-template <typename W, int MERS, bool DOT>
-static hipError_t panel_dispatch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum,
-				 u64 *partial, int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s);
-
-template <typename W, int MERS>
-static hipError_t spmv_dispatch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, int accum, const DevCtl *ctl,
-				hipStream_t s)
+static inline int lane_group(const KernelCfg &c)
 {
-	if (A.rows == 0)
-		return hipSuccess;
-	heavy_fork(c, A, s);
-	if (A.panel_rows > 0 && c.panel)
-		return panel_dispatch<W, MERS, false>(c, A, X, Y, (const W *)nullptr, accum, (u64 *)nullptr, 0, (int *)nullptr, ctl, s);
-	if (A.st_ok && c.staged)
-		return staged_dispatch<W, MERS, false>(c, A, X, Y, (const W *)nullptr, accum, (u64 *)nullptr, 0, (int *)nullptr, ctl, s);
 	int G = 1;
 	while (G < c.n)
 		G <<= 1;
+	return G;
+}
+
+/* the outlier launches of a fused product: one partial row per workgroup of each */
+static inline void outlier_grids(const KernelCfg &c, const DevCsr &A, bool dot, int max_blocks, SpmvGrids &g)
+{
+	g.hb = heavy_blocks(c, A, dot ? max_blocks / 4 : 1 << 30);
+	g.cb = A.n_multi ? combine_blocks(A, lane_group(c)) : 0;
+	g.mb = A.n_medium ? medium_blocks(c, A) : 0;
+}
+
+/* k_spmv */
+static SpmvGrids stream_grids(const KernelCfg &c, const DevCsr &A)
+{
+	SpmvGrids g{};
+	g.form = SPMV_FORM_STREAM;
+	g.ok = true;
+	outlier_grids(c, A, false, 0, g);
+	const int G = lane_group(c);
 	const long long groups_per_block = BLOCK / G;
 	/* measured on MI355X (tools/tune_spmv.py): rows of >= ~12 entries run best with 4 resident blocks per CU,
 	 * short rows want 8; few long rows are split over up to 64/G groups */
@@ -428,14 +432,162 @@ static hipError_t spmv_dispatch(const KernelCfg &c, const DevCsr &A, const W *X,
 	const long long cap = (long long)c.num_cu * per_cu;
 	if (blocks > cap)
 		blocks = cap;
-	XcdRows xr;
-	xr.begin[0] = -1;
 	if (A.xcd_ranges && split_log2 == 0 && blocks >= 64) {
-		for (int x = 0; x < 9; x++)
-			xr.begin[x] = A.xr_rows[x];
+		g.xcd = true;
 		blocks = (blocks + 7) & ~7ll;
 	}
-#define SPMV_CASE(GG)                                                                                             \
+	g.blocks = blocks;
+	g.split_log2 = split_log2;
+	return g;
+}
+
+/* k_spmv_dot */
+static SpmvGrids stream_dot_grids(const KernelCfg &c, const DevCsr &A, int max_blocks)
+{
+	SpmvGrids g{};
+	g.form = SPMV_FORM_STREAM;
+	g.ok = true;
+	const long long gpb = BLOCK / c.n;
+	long long blocks = (A.rows + gpb - 1) / gpb;
+	/* the accumulators cost registers: 4 resident blocks per CU at n = 8, so size the grid for that */
+	const long long per_cu = c.n >= 8 ? 4 : 6;
+	/* partial rows: one per block of the streaming kernel, then one per block of the outlier-row launch */
+	outlier_grids(c, A, true, max_blocks, g);
+	const long long room = max_blocks - g.hb - g.cb - g.mb;
+	const long long cap = (long long)c.num_cu * per_cu < room ? (long long)c.num_cu * per_cu : room;
+	blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
+	if (A.xcd_ranges && blocks >= 64 && (blocks & ~7ll) >= 64) {
+		g.xcd = true;
+		blocks &= ~7ll;		/* whole rounds of the XCDs, still within the room for partial rows */
+	}
+	g.blocks = blocks;
+	return g;
+}
+
+/* gathers in flight per lane of the staged form: 8 where a wavefront holds few lane groups (G >= 16) or the registers
+ * allow (the plain form at G = 8), else 4; BLZ_STAGE_U overrides between the two where both exist */
+static int staged_gathers(const KernelCfg &c, const DevCsr &A, int G, bool dot, bool wide)
+{
+	if ((G == 16 || G == 8) && !dot && wide && A.st_pair)	/* G / 2 lanes of two words per row */
+		return (G == 16 || A.st_deep) ? 8 : 4;
+	bool deep = G >= 16 || (G == 8 && !dot && A.st_deep);
+	if (c.stage_u > 0)
+		deep = c.stage_u >= 8;
+	return (G >= 8 && !dot && deep) ? 8 : 4;
+}
+
+/* k_spmv_staged */
+static SpmvGrids staged_grids(const KernelCfg &c, const DevCsr &A, bool dot, int max_blocks)
+{
+	SpmvGrids g{};
+	g.form = SPMV_FORM_STAGED;
+	g.ok = true;
+	g.gathers = staged_gathers(c, A, lane_group(c), dot, c.word == 8);
+	const long long TR = A.st_tr, nt = (A.rows + TR - 1) / TR;
+	long long blocks = (nt + BLOCK / 64 - 1) / (BLOCK / 64);
+	long long cap = (long long)c.num_cu * A.st_per_cu;
+	outlier_grids(c, A, dot, max_blocks, g);
+	if (dot) {	/* one partial row per block of every launch that feeds the inner products */
+		const long long room = ((long long)max_blocks - g.hb - g.cb - g.mb) & ~7ll;
+		cap = cap < room ? cap : room;
+	}
+	blocks = blocks > cap ? cap : blocks;
+	blocks = (blocks + 7) & ~7ll;		/* whole rounds of the eight XCDs */
+	if (blocks == ((cap + 7) & ~7ll) && blocks >= 64) {
+		/* A wavefront walks its XCD's tiles with a fixed stride, so the launch takes ceil(T / waves) rounds of tiles
+		 * and the last round is partly empty (GL7d19 shape: 9954 tiles per XCD over 512 wavefronts = 19.4 rounds: the
+		 * twentieth runs with 43 % of the chip, measured +3 % on the launch).  Give up to 15 % of the wavefronts away
+		 * so that the rounds come out (nearly) full: the fabric, not the number of resident waves, bounds the kernel. */
+		long long T = 0;
+		for (int x = 0; x < 8; x++)
+			T = std::max(T, A.st_tiles[x + 1] - A.st_tiles[x]);
+		const long long W4 = BLOCK / 64, bmax = blocks / 8, bmin = std::max<long long>(1, bmax * 85 / 100);
+		long long best = bmax;
+		double best_fill = 0.0;
+		for (long long b = bmax; b >= bmin; b--) {
+			const long long rounds = (T + b * W4 - 1) / (b * W4);
+			const double fill = (double)T / (double)(rounds * b * W4);
+			if (fill > best_fill + 1e-9) {
+				best_fill = fill;
+				best = b;
+			}
+		}
+		blocks = best * 8;
+	}
+	g.blocks = blocks;
+	return g;
+}
+
+/* k_spmv_panel */
+static SpmvGrids panel_grids(const KernelCfg &c, const DevCsr &A, bool dot, int max_blocks)
+{
+	SpmvGrids g{};
+	g.form = SPMV_FORM_PANEL;
+	g.blocks = ((long long)c.num_cu + 7) & ~7ll;	/* one workgroup of 1024 per CU, whole rounds of the XCDs */
+	outlier_grids(c, A, dot, max_blocks, g);
+	g.ok = !dot || g.blocks + g.hb + g.cb + g.mb <= max_blocks;
+	return g;
+}
+
+/* which form a product of the slab takes (the order the dispatch functions test in) */
+static inline int spmv_form(const KernelCfg &c, const DevCsr &A, bool dot)
+{
+	if (A.panel_rows > 0 && c.panel)
+		return SPMV_FORM_PANEL;
+	if (A.st_ok && c.staged && !(dot && A.st_dyn))	/* (a slab planned for dynamic rows has tiles the lockstep form cannot walk) */
+		return SPMV_FORM_STAGED;
+	return SPMV_FORM_STREAM;
+}
+
+SpmvGrids spmv_grids(const KernelCfg &c, const DevCsr &A, bool dot, int max_blocks)
+{
+	if (A.rows == 0 && !dot) {	/* spmv_dispatch launches nothing */
+		SpmvGrids g{};
+		g.ok = true;
+		return g;
+	}
+	switch (spmv_form(c, A, dot)) {
+	case SPMV_FORM_PANEL:
+		return panel_grids(c, A, dot, max_blocks);
+	case SPMV_FORM_STAGED:
+		return staged_grids(c, A, dot, max_blocks);
+	default:
+		return dot ? stream_dot_grids(c, A, max_blocks) : stream_grids(c, A);
+	}
+}
+
+/* the same product with the matrix stream staged through LDS (further down: it shares DotState with k_spmv_dot) */
+template <typename W, int MERS, bool DOT>
+static hipError_t staged_dispatch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum,
+				  u64 *partial, int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s);
+
+/* ... and with the densest block rows of the operand resident in LDS (k_spmv_panel, below) */
+template <typename W, int MERS, bool DOT>
+static hipError_t panel_dispatch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum,
+				 u64 *partial, int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s);
+
+template <typename W, int MERS>
+static hipError_t spmv_dispatch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, int accum, const DevCtl *ctl,
+				hipStream_t s)
+{
+	if (A.rows == 0)
+		return hipSuccess;
+	heavy_fork(c, A, s);
+	const int form = spmv_form(c, A, false);
+	if (form == SPMV_FORM_PANEL)
+		return panel_dispatch<W, MERS, false>(c, A, X, Y, (const W *)nullptr, accum, (u64 *)nullptr, 0, (int *)nullptr, ctl, s);
+	if (form == SPMV_FORM_STAGED)
+		return staged_dispatch<W, MERS, false>(c, A, X, Y, (const W *)nullptr, accum, (u64 *)nullptr, 0, (int *)nullptr, ctl, s);
+	const int G = lane_group(c);
+	const SpmvGrids g = stream_grids(c, A);
+	const long long blocks = g.blocks;
+	const int split_log2 = g.split_log2;
+	XcdRows xr;
+	xr.begin[0] = -1;
+	if (g.xcd)
+		for (int x = 0; x < 9; x++)
+			xr.begin[x] = A.xr_rows[x];
+#define SPMV_CASE(GG)                                                                                           \
 	case GG:                                                                                                  \
 		if (A.tail_batch)                                                                                 \
 			hipLaunchKernelGGL((k_spmv<W, GG, MERS, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, A.row_ptr,  \
@@ -447,7 +599,7 @@ static hipError_t spmv_dispatch(const KernelCfg &c, const DevCsr &A, const W *X,
 					   A.heavy_thr, c.m, xr, ctl);                                                     \
 		if (A.n_heavy || A.n_medium)                                                                      \
 			launch_heavy<W, GG, MERS, false>(c, A, X, Y, (const W *)nullptr, accum, (u64 *)nullptr, 0,   \
-							 heavy_blocks(c, A, 1 << 30), ctl, s);                        \
+							 g.hb, ctl, s);                                               \
 		break;
 	switch (G) {
 		SPMV_CASE(1)
@@ -939,27 +1091,18 @@ static hipError_t spmv_dot_dispatch(const KernelCfg &c, const DevCsr &A, const W
 				    u64 *partial, int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s)
 {
 	heavy_fork(c, A, s);
-	if (A.panel_rows > 0 && c.panel)
+	const int form = spmv_form(c, A, true);
+	if (form == SPMV_FORM_PANEL)
 		return panel_dispatch<W, MERS, true>(c, A, X, Y, Vd, accum, partial, max_blocks, nblocks, ctl, s);
-	if (A.st_ok && c.staged && !A.st_dyn)	/* (a slab planned for dynamic rows has tiles the lockstep form cannot walk) */
+	if (form == SPMV_FORM_STAGED)
 		return staged_dispatch<W, MERS, true>(c, A, X, Y, Vd, accum, partial, max_blocks, nblocks, ctl, s);
-	const long long gpb = BLOCK / c.n;
-	long long blocks = (A.rows + gpb - 1) / gpb;
-	/* the accumulators cost registers: 4 resident blocks per CU at n = 8, so size the grid for that */
-	const long long per_cu = c.n >= 8 ? 4 : 6;
-	/* partial rows: one per block of the streaming kernel, then one per block of the outlier-row launch */
-	const long long hb = heavy_blocks(c, A, max_blocks / 4), cb = A.n_multi ? combine_blocks(A, c.n) : 0;
-	const long long mb = A.n_medium ? medium_blocks(c, A) : 0;
-	const long long room = max_blocks - hb - cb - mb;
-	const long long cap = (long long)c.num_cu * per_cu < room ? (long long)c.num_cu * per_cu : room;
-	blocks = blocks < 1 ? 1 : (blocks > cap ? cap : blocks);
+	const SpmvGrids g = stream_dot_grids(c, A, max_blocks);
+	const long long blocks = g.blocks, hb = g.hb, cb = g.cb, mb = g.mb;
 	XcdRows xr;
 	xr.begin[0] = -1;
-	if (A.xcd_ranges && blocks >= 64 && (blocks & ~7ll) >= 64) {
+	if (g.xcd)
 		for (int x = 0; x < 9; x++)
 			xr.begin[x] = A.xr_rows[x];
-		blocks &= ~7ll;		/* whole rounds of the XCDs, still within the room for partial rows */
-	}
 	*nblocks = (int)(blocks + hb + cb + mb);
 #define SPMV_DOT(NN)                                                                                                \
 	case NN:                                                                                                    \
@@ -1480,12 +1623,8 @@ static void staged_launch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y,
 		xt.begin[x] = A.st_tiles[x];
 	xt.interleave = A.st_interleave;
 	const size_t lds = (size_t)(BLOCK / 64) * 2 * A.st_ns * A.st_capw * sizeof(u32);
-	/* gathers in flight per lane: 8 where a wavefront holds few lane groups (G >= 16) or the registers allow (the
-	 * plain form at G = 8), else 4; BLZ_STAGE_U overrides between the two where both exist */
-	bool deep = G >= 16 || (G == 8 && !DOT && A.st_deep);
-	if (c.stage_u > 0)
-		deep = c.stage_u >= 8;
-#define STAGED_GO(UU, DD)                                                                                               \
+	const bool deep = staged_gathers(c, A, G, DOT, sizeof(W) == 8) == 8;	/* gathers in flight per lane: 8 or 4 */
+#define STAGED_GO(UU, DD)                                                                                              \
 	hipLaunchKernelGGL((k_spmv_staged<W, G, MERS, DOT, VALS, UU, DD>), dim3((unsigned)blocks), dim3(BLOCK), lds, s, A.row_ptr, \
 			   (const u32 *)A.col_idx, A.val, A.palette, X, Y, Vd, (long long)A.rows, c.n, A.st_tr, A.st_capw, accum, \
 			   A.heavy_thr, c.m, partial, xt, ctl)
@@ -1495,7 +1634,7 @@ static void staged_launch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y,
 	hipLaunchKernelGGL((k_spmv_staged<W, G / 2, MERS, false, VALS, UU, false, 2>), dim3((unsigned)blocks), dim3(BLOCK), lds, s, \
 			   A.row_ptr, (const u32 *)A.col_idx, A.val, A.palette, X, Y, Vd, (long long)A.rows, c.n, A.st_tr, A.st_capw, \
 			   accum, A.heavy_thr, c.m, partial, xt, ctl)
-			if (G == 16 || A.st_deep)
+			if (deep)
 				STAGED_PAIR(8);
 			else
 				STAGED_PAIR(4);
@@ -1525,45 +1664,11 @@ template <typename W, int MERS, bool DOT>
 static hipError_t staged_dispatch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum,
 				  u64 *partial, int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s)
 {
-	int G = 1;
-	while (G < c.n)
-		G <<= 1;
-	const long long TR = A.st_tr, nt = (A.rows + TR - 1) / TR;
-	long long blocks = (nt + BLOCK / 64 - 1) / (BLOCK / 64);
-	long long cap = (long long)c.num_cu * A.st_per_cu;
-	long long hb = heavy_blocks(c, A, 1 << 30), cb = 0, mb = 0;
-	if (DOT) {	/* one partial row per block of every launch that feeds the inner products */
-		hb = heavy_blocks(c, A, max_blocks / 4);
-		cb = A.n_multi ? combine_blocks(A, c.n) : 0;
-		mb = A.n_medium ? medium_blocks(c, A) : 0;
-		const long long room = ((long long)max_blocks - hb - cb - mb) & ~7ll;
-		cap = cap < room ? cap : room;
-	}
-	blocks = blocks > cap ? cap : blocks;
-	blocks = (blocks + 7) & ~7ll;		/* whole rounds of the eight XCDs */
-	if (blocks == ((cap + 7) & ~7ll) && blocks >= 64) {
-		/* A wavefront walks its XCD's tiles with a fixed stride, so the launch takes ceil(T / waves) rounds of tiles
-		 * and the last round is partly empty (GL7d19 shape: 9954 tiles per XCD over 512 wavefronts = 19.4 rounds: the
-		 * twentieth runs with 43 % of the chip, measured +3 % on the launch).  Give up to 15 % of the wavefronts away
-		 * so that the rounds come out (nearly) full: the fabric, not the number of resident waves, bounds the kernel. */
-		long long T = 0;
-		for (int x = 0; x < 8; x++)
-			T = std::max(T, A.st_tiles[x + 1] - A.st_tiles[x]);
-		const long long W4 = BLOCK / 64, bmax = blocks / 8, bmin = std::max<long long>(1, bmax * 85 / 100);
-		long long best = bmax;
-		double best_fill = 0.0;
-		for (long long b = bmax; b >= bmin; b--) {
-			const long long rounds = (T + b * W4 - 1) / (b * W4);
-			const double fill = (double)T / (double)(rounds * b * W4);
-			if (fill > best_fill + 1e-9) {
-				best_fill = fill;
-				best = b;
-			}
-		}
-		blocks = best * 8;
-	}
+	const int G = lane_group(c);
+	const SpmvGrids g = staged_grids(c, A, DOT, max_blocks);
+	const long long blocks = g.blocks, hb = g.hb;
 	if (DOT)
-		*nblocks = (int)(blocks + hb + cb + mb);
+		*nblocks = (int)(blocks + hb + g.cb + g.mb);
 	const int vals = A.palette ? V_PACKED : (A.val ? V_ARRAY : V_ONES);
 #define STAGED_G(GG)                                                                                              \
 	case GG:                                                                                                  \
@@ -1773,15 +1878,12 @@ static hipError_t panel_dispatch(const KernelCfg &c, const DevCsr &A, const W *X
 				 u64 *partial, int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s)
 {
 	const int G = c.n;	/* spmv_panel_capacity: a power of two */
-	long long blocks = ((long long)c.num_cu + 7) & ~7ll;	/* one workgroup of 1024 per CU, whole rounds of the XCDs */
-	long long hb = heavy_blocks(c, A, 1 << 30), cb = 0, mb = 0;
+	const SpmvGrids g = panel_grids(c, A, DOT, max_blocks);
+	const long long blocks = g.blocks, hb = g.hb;
 	if (DOT) {
-		hb = heavy_blocks(c, A, max_blocks / 4);
-		cb = A.n_multi ? combine_blocks(A, c.n) : 0;
-		mb = A.n_medium ? medium_blocks(c, A) : 0;
-		if (blocks + hb + cb + mb > max_blocks)
+		if (!g.ok)
 			return hipErrorInvalidValue;
-		*nblocks = (int)(blocks + hb + cb + mb);
+		*nblocks = (int)(blocks + hb + g.cb + g.mb);
 	}
 	const int vals = A.palette ? V_PACKED : (A.val ? V_ARRAY : V_ONES);
 #define PANEL_G(GG)                                                                                              \

@@ -38,6 +38,26 @@ class Csr(C.Structure):
                 ("val", C.POINTER(C.c_uint32))]
 
 
+class PlanLaunch(C.Structure):
+    """blz_plan_launch of include/blz.h."""
+    _fields_ = [(k, C.c_int32) for k in ("form", "xcd_ranges", "split_log2", "st_gathers")] + \
+               [(k, C.c_int64) for k in ("grid_stream", "grid_heavy", "grid_combine", "grid_medium")]
+
+
+class Plan(C.Structure):
+    """blz_plan of include/blz.h."""
+    _fields_ = [(k, C.c_int64) for k in ("rows", "cols", "nnz")] + \
+               [(k, C.c_int32) for k in ("pieces", "width", "chunk", "num_cu", "max_dot_blocks", "tail_batch", "xcd_ranges")] + \
+               [("heavy_thr", C.c_uint32)] + \
+               [(k, C.c_int32) for k in ("n_medium", "n_heavy", "n_multi", "st_ok", "st_tr", "st_pair", "st_dyn", "st_deep",
+                                         "st_interleave", "st_capw", "st_per_cu", "panel_rows", "packed", "dot_supported",
+                                         "fused", "fuse_local_off", "short_side")] + \
+               [("locality", C.c_double), ("plain", PlanLaunch), ("dot", PlanLaunch)]
+
+
+FORMS = ("spmv", "staged", "panel")
+
+
 def lib():
     """Load libblz_hip.so.  Raises if it has not been built: there is no Python/CPU substitute."""
     global _lib
@@ -452,6 +472,20 @@ class Context:
         share = C.c_double(0.0)
         rows = int(lib().blz_panel_rows(self.h, C.c_int(int(transpose)), C.byref(share)))
         return rows, float(share.value)
+
+    def plan(self, transpose, piece=0):
+        """blz_slab_plan(): what the launches of product M*x (False) / M^T*x (True), column piece `piece`, will be, as
+        a dict; "plain" and "dot" are dicts of their own (form: "spmv" / "staged" / "panel", the four grids, ...)."""
+        out = Plan()
+        check(lib().blz_slab_plan(self.h, C.c_int(int(transpose)), C.c_int(piece), C.byref(out)))
+        res = {}
+        for name, _ in Plan._fields_:
+            val = getattr(out, name)
+            if isinstance(val, PlanLaunch):
+                val = {k: getattr(val, k) for k, _ in PlanLaunch._fields_}
+                val["form"] = FORMS[val["form"]]
+            res[name] = val
+        return res
 
     def owner_of_row(self, block, row):
         return int(lib().blz_owner_of_row(self.h, C.c_int(block), C.c_int64(row)))

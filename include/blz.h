@@ -270,6 +270,45 @@ int64_t blz_panel_rows(const blz_ctx *c, int transpose, double *share);
  * 1 the file's order, 2 rows by the mean of their columns. */
 int blz_locality(const blz_ctx *c, double locality[2], int *order_kind);
 
+/* Read-only view of the plan of one slab (tests): what the launches of product `transpose` (0: M * x, 1: M^T * x), column
+ * piece `piece` (0 unless the product is cut up for the exchange), WILL be -- taken from the same functions the launches
+ * take their grids from.  Nothing is launched and nothing changes.  `plain` describes the product as blz_spmv and the
+ * first product of an iteration run it, `dot` the same product with the inner products v^T Av, Av^T Av as its epilogue
+ * (widths 1, 2, 4, 8; zero elsewhere); `fused` says whether blz_iterate uses `dot` for this piece. */
+enum { BLZ_FORM_SPMV = 0, BLZ_FORM_STAGED = 1, BLZ_FORM_PANEL = 2 };
+typedef struct blz_plan_launch {
+	int32_t form;			/* BLZ_FORM_*: k_spmv / k_spmv_dot, k_spmv_staged, k_spmv_panel */
+	int32_t xcd_ranges;		/* k_spmv / k_spmv_dot walk per-XCD row ranges: as applied, after the test on the grid size */
+	int32_t split_log2;		/* k_spmv: 2^split_log2 lane groups share a row */
+	int32_t st_gathers;		/* k_spmv_staged: gathers in flight per lane (4 / 8); 0 in the other forms */
+	int64_t grid_stream;		/* workgroups of the streaming launch (256 threads; 1024 in the panel form) */
+	int64_t grid_heavy;		/* ... of k_spmv_heavy (one per segment of a long row, bounded), 0: not launched */
+	int64_t grid_combine;		/* ... of k_spmv_heavy_combine (one lane group per split row) */
+	int64_t grid_medium;		/* ... of k_spmv_wave (one wavefront per medium row, 4 per workgroup) */
+} blz_plan_launch;
+typedef struct blz_plan {
+	int64_t rows, cols, nnz;	/* of the piece */
+	int32_t pieces;			/* column pieces of the product */
+	int32_t width;			/* block width in HBM (the caller's n rounded up to a power of two unless BLZ_NO_PAD=1) */
+	int32_t chunk;			/* products a dense sum takes between two reductions (make_modp) */
+	int32_t num_cu;			/* compute units the grids are sized by */
+	int32_t max_dot_blocks;		/* room for partial rows of the inner products */
+	int32_t tail_batch;		/* k_spmv / k_spmv_dot instantiation: row tails as one predicated batch */
+	int32_t xcd_ranges;		/* as planned (blz_plan_launch has it as applied) */
+	uint32_t heavy_thr;		/* rows of MORE entries leave the streaming launch */
+	int32_t n_medium, n_heavy, n_multi;	/* rows of k_spmv_wave, segments of k_spmv_heavy, split rows of the combine launch */
+	int32_t st_ok, st_tr, st_pair, st_dyn, st_deep, st_interleave, st_capw, st_per_cu;	/* plan of the staged form */
+	int32_t panel_rows;		/* block rows of the operand kept in LDS */
+	int32_t packed;			/* values: 0 all ones, 1 packed palette, 2 separate array */
+	int32_t dot_supported;		/* the width has the fused form at all */
+	int32_t fused;			/* blz_iterate runs this piece as `dot` */
+	int32_t fuse_local_off;		/* this matrix: inner products as their own kernel although the width could fuse */
+	int32_t short_side;		/* the product runs in its short-side form: this describes that slab, piece 0 only */
+	double locality;		/* lines of the operand per gathered entry (1: no reuse) */
+	blz_plan_launch plain, dot;
+} blz_plan;
+int blz_slab_plan(const blz_ctx *c, int transpose, int piece, blz_plan *out);
+
 /* Short-side exchange: 1 when product `transpose` (0: M * x, 1: M^T * x) runs in its short-side form on this context
  * -- several ranks, 64-bit words, operand side at least 8 times longer than the output side (BLZ_SHORT_SIDE=0/1
  * overrides): the rank multiplies the transpose of its own rows of the other orientation by its own slab and a

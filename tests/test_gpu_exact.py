@@ -25,6 +25,9 @@ C. SpMV with every value 2^32-1 mod p (p-1 where p divides 2^32-1) and every ope
 D. block_rref and kernel_basis (k_rref, k_block_mul) at the 57-62-bit Barrett primes, at widths the kernel-basis
    tests skip, padded and exact, against kbasis_ref; and the edge nranks * p <= 2^64 of the all-reduce on loopback
    ranks.
+
+block_dot() above is the stand-alone kernel; the same products as the epilogue of the second SpMV (widths 1 ... 8, six
+kernels) are held to exact integers by tests/test_gpu_fused_dot.py.
 """
 import ctypes as C
 import glob
