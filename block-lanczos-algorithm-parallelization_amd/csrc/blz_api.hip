@@ -28,6 +28,7 @@
 
 #include "blz_internal.h"
 #include "blz_kernels.h"
+#include "blz_border.h"
 
 #define HIPCHK(expr)                                                                                     \
 	do {                                                                                             \
@@ -222,6 +223,11 @@ struct blz_ctx {
 	u64 *rref_out = nullptr;	/* the RREF, n x n */
 	u64 *rref_z = nullptr;		/* n x n operand of the block product */
 	int *rref_ctl = nullptr;	/* [rank-n flag, stacked rows, rank, pivots[n]] */
+	/* the border of a solve with a right-hand side (blz_set_rhs): the matrix has one extra empty row / column and b is
+	 * applied behind each product (enqueue_border) */
+	void *rhs = nullptr;		/* b: one word of the context's width per row of side 1, solver's numbering */
+	int64_t border = -1;		/* the border row of side 0 in the solver's numbering (perm[0][last]) */
+	u64 *border_partial = nullptr;	/* partial rows of the border dot */
 };
 
 /* HIP-event span around one enqueue on the context's stream (only while profiling is on). */
@@ -443,6 +449,8 @@ extern "C" void blz_destroy(blz_ctx *c)
 	for (u64 *b : { c->rref_stack, c->rref_gath, c->rref_out, c->rref_z })
 		if (b) hipFree(b);
 	if (c->rref_ctl) hipFree(c->rref_ctl);
+	if (c->rhs) hipFree(c->rhs);
+	if (c->border_partial) hipFree(c->border_partial);
 	if (c->dot_send) hipFree(c->dot_send);
 	if (c->dot_recv) hipFree(c->dot_recv);
 	if (c->rs_recv) hipFree(c->rs_recv);
@@ -665,6 +673,11 @@ extern "C" int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int ra
 	c->rank = rank;
 	c->nranks = nranks;
 	c->fuse_local_off = false;
+	if (c->rhs) {		/* a border belongs to the matrix it was set for */
+		hipFree(c->rhs);
+		c->rhs = nullptr;
+	}
+	c->border = -1;
 	/* side 0 = rows of v: rows of M for a left kernel, columns of M for a right kernel
 	 * (sequential/lanczos_modp.c:592-593). */
 	c->glob_rows[0] = right ? P->ncols : P->nrows;
@@ -840,6 +853,88 @@ extern "C" int blz_set_matrix(blz_ctx *c, const blz_coo *M, int right, int rank,
 	blz_prepared_free(P);
 	return rc;
 }
+
+/* ---- a right-hand side: M x = b / x M = b as kernel vectors of the bordered operator [M | b] / [M ; b] ---- */
+
+static int put_words(blz_ctx *c, void *dst, const uint64_t *src, int64_t words);
+
+static int rhs_refuse_ranks(const blz_ctx *c, const char *who, bool matrix_is_set)
+{
+	/* (the one-call form sets its own one-rank matrix: what an earlier matrix was set for does not count) */
+	if ((matrix_is_set && c->nranks > 1) || c->comm || c->loop || c->force_comm)
+		return blz_fail(BLZ_EINVAL, "%s: a right-hand side needs a single rank without a communicator (the border row is not "
+				"distributed: see DESIGN.md section 11)", who);
+	return BLZ_OK;
+}
+
+extern "C" int blz_set_rhs(blz_ctx *c, const uint64_t *b)
+{
+	if (!c || !c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "no matrix loaded (blz_set_matrix)");
+	HIPCHK(hipSetDevice(c->device));
+	if (!b)
+		return blz_fail(BLZ_EINVAL, "blz_set_rhs: b is NULL");
+	int rc = rhs_refuse_ranks(c, "blz_set_rhs", true);
+	if (rc != BLZ_OK)
+		return rc;
+	if (c->csr[0].size() != 1 || c->csr[1].size() != 1 || c->short_side[0] || c->short_side[1] || c->glob_rows[0] < 1)
+		return blz_fail(BLZ_EINVAL, "blz_set_rhs: the matrix was not set for a single rank in one piece");
+	HIPCHK(hipStreamSynchronize(c->stream));
+	const int64_t last = c->glob_rows[0] - 1, len = c->glob_rows[1];
+	const int64_t border = c->perm[0].empty() ? last : c->perm[0][(size_t)last];
+	{	/* the border row / column of the matrix itself must be empty: the product whose rows live on side 0 says so */
+		const DevCsr &A = c->csr[c->row_side[0] == 0 ? 0 : 1][0];
+		u32 rp[2] = { 0, 0 };
+		if (A.rows != c->glob_rows[0])
+			return blz_fail(BLZ_EINVAL, "blz_set_rhs: unexpected slab shape");
+		HIPCHK(hipMemcpy(rp, A.row_ptr + border, sizeof rp, hipMemcpyDeviceToHost));
+		if (rp[0] != rp[1])
+			return blz_fail(BLZ_EINVAL, "blz_set_rhs: the last %s of the matrix must be empty (it stands for the right-hand side)",
+					c->right ? "column" : "row");
+	}
+	std::vector<uint64_t> bs((size_t)std::max<int64_t>(len, 1), 0);
+	for (int64_t r = 0; r < len; r++) {
+		if (b[r] >= c->prime)
+			return blz_fail(BLZ_EINVAL, "blz_set_rhs: b[%lld] is not below p", (long long)r);
+		bs[(size_t)(c->perm[1].empty() ? r : c->perm[1][(size_t)r])] = b[r];
+	}
+	if (c->rhs)
+		hipFree(c->rhs);
+	c->rhs = nullptr;
+	HIPCHK(hipMalloc(&c->rhs, bs.size() * c->cfg.word));
+	if ((rc = put_words(c, c->rhs, bs.data(), (int64_t)bs.size())) != BLZ_OK)
+		return rc;
+	if (!c->border_partial)
+		HIPCHK(hipMalloc(&c->border_partial, (size_t)border_dot_max_blocks(c->cfg) * BLZ_BORDER_MAXN * sizeof(u64)));
+	c->border = border;
+	/* the fused inner products would read the border row of Av before the border dot has written it: the second product
+	 * runs plain and block_dot as its own kernel */
+	c->fuse_local_off = true;
+	if (c->iter_graph) {
+		hipGraphExecDestroy(c->iter_graph);
+		c->iter_graph = nullptr;
+	}
+	return BLZ_OK;
+}
+
+extern "C" int blz_set_matrix_rhs(blz_ctx *c, const blz_coo *M, int right, const uint64_t *b)
+{
+	if (!c || !M || !b)
+		return blz_fail(BLZ_EINVAL, "blz_set_matrix_rhs: NULL argument");
+	int rc = rhs_refuse_ranks(c, "blz_set_matrix_rhs", false);
+	if (rc != BLZ_OK)
+		return rc;
+	blz_coo Mb = *M;	/* the same triplets under a dimension raised by one: an empty row (x M = b) / column (M x = b) */
+	if (right)
+		Mb.ncols++;
+	else
+		Mb.nrows++;
+	if ((rc = blz_set_matrix(c, &Mb, right, 0, 1)) != BLZ_OK)
+		return rc;
+	return blz_set_rhs(c, b);
+}
+
+extern "C" int blz_has_rhs(const blz_ctx *c) { return c && c->have_matrix && c->rhs != nullptr; }
 
 extern "C" int64_t blz_rows(const blz_ctx *c, int block)
 {
@@ -1323,6 +1418,24 @@ static inline u64 *dot_out(blz_ctx *c) { return exchanging(c) ? c->dot_send : c-
 static inline const u64 *dot_sums(blz_ctx *c) { return exchanging(c) ? c->dot_recv : c->small; }
 
 /*
+ * The border of M' = [M | b] resp. [M ; b] behind product `transpose` (one rank; the matrix holds an empty row / column
+ * in b's place).  The product that writes side 1 gets  dst[r, :] += b[r] * src[border, :],  the one that writes side 0
+ *  dst[border, :] = sum_r b[r] * src[r, :]  (the SpMV has written zeros there).  Enqueued on the context's stream behind
+ * launch_spmv, which has joined its outlier launches' side stream by the time it returns.
+ */
+static int enqueue_border(blz_ctx *c, int transpose, int src, int dst, const DevCtl *ctl)
+{
+	const size_t row_bytes = (size_t)c->cfg.n * c->cfg.word;
+	if (c->row_side[transpose] == 1)
+		HIPCHK(launch_border_update(c->cfg, slab_ptr(c, dst), c->rhs, slab_ptr(c, src) + (size_t)c->border * row_bytes, c->count[1],
+					    ctl, c->stream));
+	else
+		HIPCHK(launch_border_dot(c->cfg, slab_ptr(c, src), c->rhs, c->count[1], c->border_partial,
+					 slab_ptr(c, dst) + (size_t)c->border * row_bytes, ctl, c->stream));
+	return BLZ_OK;
+}
+
+/*
  * One product of the iteration: slab[dst] = (transpose ? M^T : M)[this rank's rows] * block `src`, with the
  * exchange of `src` pipelined against it.  The exchange stream all-gathers piece k of every rank's slab into
  * gath[side]; the compute stream waits for piece k only, then multiplies by csr[transpose][k] (entries whose
@@ -1330,8 +1443,10 @@ static inline const u64 *dot_sums(blz_ctx *c) { return exchanging(c) ? c->dot_re
  * all but 1/K of itself behind the exchange; K = 1 is one all-gather followed by one product.
  * with_dot: the last piece carries block_dot_products as its epilogue (second product only); *nb = partial rows.
  */
-static int enqueue_product(blz_ctx *c, int transpose, int src, int dst, bool with_dot, int *nb)
+static int enqueue_product(blz_ctx *c, int transpose, int src, int dst, bool with_dot, int *nb, const DevCtl *ctl = nullptr)
 {
+	if (!ctl)
+		ctl = c->ctl;	/* (blz_solution runs its check past the stop, on control words of its own) */
 	const bool xchg = exchanging(c);
 	const int cls = transpose == !c->right ? PK_SPMV1 : PK_SPMV2;
 	if (c->short_side[transpose]) {
@@ -1342,7 +1457,7 @@ static int enqueue_product(blz_ctx *c, int transpose, int src, int dst, bool wit
 			return blz_fail(BLZ_EINVAL, "enqueue_product: the short-side form has no fused inner products");
 		{
 			Span sp(c, cls);
-			HIPCHK(launch_spmv(c->cfg, c->csr_short[transpose], slab_ptr(c, src), c->part, 0, c->ctl, c->stream));
+			HIPCHK(launch_spmv(c->cfg, c->csr_short[transpose], slab_ptr(c, src), c->part, 0, ctl, c->stream));
 		}
 		if (xchg) {
 			{
@@ -1353,7 +1468,7 @@ static int enqueue_product(blz_ctx *c, int transpose, int src, int dst, bool wit
 			}
 			/* out of place and stop-aware: past the stop `part` is stale (possibly the OTHER product's), the collective
 			 * runs all the same, and slab[dst] must keep the last real product (blz_final_check reads TMP) */
-			HIPCHK(launch_reduce_modp(c->cfg, c->slab[dst], c->rs_recv, c->count[rs_t] * c->cfg.n, c->ctl, c->stream));
+			HIPCHK(launch_reduce_modp(c->cfg, c->slab[dst], c->rs_recv, c->count[rs_t] * c->cfg.n, ctl, c->stream));
 		}
 		return BLZ_OK;
 	}
@@ -1389,9 +1504,13 @@ static int enqueue_product(blz_ctx *c, int transpose, int src, int dst, bool wit
 		const DevCsr &A = c->csr[transpose][(size_t)k];
 		if (with_dot && k == K - 1)
 			HIPCHK(launch_spmv_dot(c->cfg, A, X, slab_ptr(c, dst), slab_ptr(c, BLZ_V), k > 0, c->partial,
-					       c->max_dot_blocks, nb, c->ctl, c->stream));
+					       c->max_dot_blocks, nb, ctl, c->stream));
 		else
-			HIPCHK(launch_spmv(c->cfg, A, X, slab_ptr(c, dst), k > 0, c->ctl, c->stream));
+			HIPCHK(launch_spmv(c->cfg, A, X, slab_ptr(c, dst), k > 0, ctl, c->stream));
+	}
+	if (c->rhs) {
+		Span sp(c, cls);
+		return enqueue_border(c, transpose, src, dst, ctl);
 	}
 	return BLZ_OK;
 }
@@ -1730,6 +1849,79 @@ extern "C" int blz_kernel_basis(blz_ctx *c, int *k, uint64_t *z)
 			for (int j = 0; j < n; j++)
 				z[(size_t)row * n + j] = j < kk ? (s > 0 ? Z0[(size_t)row * n + piv[(size_t)j]] : (uint64_t)(row == piv[(size_t)j]))
 								 : 0;
+	return BLZ_OK;
+}
+
+/* a^-1 mod p (extended Euclid on the host, p prime, 0 < a < p) */
+static uint64_t host_inverse(uint64_t a, uint64_t p)
+{
+	__int128 t = 0, nt = 1, r = p, nr = a % p;
+	while (nr != 0) {
+		const __int128 q = r / nr, t2 = t - q * nt, r2 = r - q * nr;
+		t = nt;
+		nt = t2;
+		r = nr;
+		nr = r2;
+	}
+	return (uint64_t)(t < 0 ? t + p : t);
+}
+
+extern "C" int blz_solution(blz_ctx *c, uint64_t *x, int *status)
+{
+	NEED_MATRIX(c);
+	if (!c->rhs || !x || !status)
+		return blz_fail(BLZ_EINVAL, "blz_solution: %s", !c->rhs ? "the context has no right-hand side (blz_set_matrix_rhs)" : "NULL argument");
+	const int n = c->un, np = c->cfg.n;
+	const u64 p = c->prime;
+	int k = 0;
+	int rc = blz_kernel_basis(c, &k, nullptr);
+	if (rc != BLZ_OK)
+		return rc;
+	/* the first basis vector with a non-zero border word: v = (y, w), M' v = 0  <=>  M y + w b = 0 */
+	std::vector<uint64_t> brow((size_t)np);
+	if ((rc = get_words(c, brow.data(), slab_ptr(c, BLZ_V) + (size_t)c->border * np * c->cfg.word, np)) != BLZ_OK)
+		return rc;
+	int j = 0;
+	while (j < k && brow[(size_t)j] == 0)
+		j++;
+	if (j >= k) {
+		*status = 1;
+		return BLZ_OK;
+	}
+	/* column 0 <- -w^-1 * column j (border word p - 1, i.e. -1), the other columns zero: one-column selection matrix */
+	std::vector<uint64_t> Z((size_t)n * n, 0);
+	const uint64_t winv = host_inverse(brow[(size_t)j], p);
+	Z[(size_t)j * n] = winv ? p - winv : 0;
+	if ((rc = block_mul(c, Z)) != BLZ_OK)
+		return rc;
+	/* the check, on the GPU like blz_final_check: the side-1 product of that column with the border applied is
+	 * M y - b and must be zero.  The stop flag is up by now, so the product runs on control words of its own. */
+	{
+		DevCtl *idle = nullptr;
+		HIPCHK(hipMalloc(&idle, sizeof(DevCtl)));
+		hipError_t e = hipMemsetAsync(idle, 0, sizeof(DevCtl), c->stream);
+		rc = e == hipSuccess ? enqueue_product(c, !c->right, BLZ_V, BLZ_TMP, false, nullptr, idle) : BLZ_OK;
+		if (e == hipSuccess)
+			e = hipStreamSynchronize(c->stream);
+		hipFree(idle);
+		HIPCHK(e);
+		if (rc != BLZ_OK)
+			return rc;
+	}
+	HIPCHK(hipMemsetAsync(&c->ctl->flag_t_nonzero, 0, sizeof(int), c->stream));
+	HIPCHK(launch_any_nonzero(c->cfg, slab_ptr(c, BLZ_TMP), c->count[1] * c->cfg.n, &c->ctl->flag_t_nonzero, c->stream));
+	if ((rc = fetch_ctl(c)) != BLZ_OK)
+		return rc;
+	if (c->host_ctl.flag_t_nonzero) {
+		*status = 2;
+		return BLZ_OK;
+	}
+	std::vector<uint64_t> v((size_t)c->glob_rows[0] * n);
+	if ((rc = blz_get_block(c, BLZ_V, v.data())) != BLZ_OK)
+		return rc;
+	for (int64_t i = 0; i + 1 < c->glob_rows[0]; i++)	/* the border row is the last one in the original numbering */
+		x[i] = v[(size_t)i * n];
+	*status = 0;
 	return BLZ_OK;
 }
 

@@ -2124,6 +2124,129 @@ done:
 	return rc;
 }
 
+/* ---------------------------------------------------------------- right-hand sides and solutions */
+
+/* A len x 1 "array integer general" file into out[0..len).  true_residue != 0: signed entries reduced as integers
+ * (blz_rhs_load); 0: blz_save_block's inverse, a negative entry being the "%d" of a u32, and entries must be below prime. */
+static int load_column(const char *path, uint64_t prime, int64_t len, int true_residue, uint64_t *out)
+{
+	int fd = open(path, O_RDONLY);
+	struct stat st;
+	if (fd < 0 || fstat(fd, &st) != 0 || st.st_size == 0) {
+		if (fd >= 0)
+			close(fd);
+		return blz_fail(BLZ_EIO, "cannot open %s", path);
+	}
+	char *base = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+	close(fd);
+	if (base == MAP_FAILED)
+		return blz_fail(BLZ_EIO, "mmap %s: %s", path, strerror(errno));
+	cursor c = { base, base + st.st_size };
+	char line[1100];
+	long long nk = 0, n = 0;
+	int rc = BLZ_OK;
+	if (next_line(&c, line, sizeof line) || (rc = check_banner(line, 1)) != BLZ_OK) {
+		if (rc == BLZ_OK)
+			rc = blz_fail(BLZ_EFORMAT, "Could not process Matrix Market banner.");
+		goto done;
+	}
+	do {
+		if (next_line(&c, line, sizeof line)) {
+			rc = blz_fail(BLZ_EIO, "%s: cannot read the size line", path);
+			goto done;
+		}
+	} while (line[0] == '%');
+	if (sscanf(line, "%lld %lld", &nk, &n) != 2 || nk != len || n != 1) {
+		rc = blz_fail(BLZ_EIO, "%s: expected a %lld x 1 array, the size line says \"%.40s\"", path, (long long)len, line);
+		goto done;
+	}
+	for (int64_t i = 0; i < len; i++) {
+		const char *q = c.p;
+		while (q < c.end && is_blank(*q))
+			q++;
+		if (q < c.end && (*q == '-' || *q == '+'))
+			q++;
+		const char *d0 = q;
+		while (q < c.end && *q >= '0' && *q <= '9')
+			q++;
+		/* sign and magnitude apart: 19 digits fit a u64 (10^19 - 1 < 2^64) but not always a long long */
+		if (q == d0 || q - d0 > 19) {
+			rc = blz_fail(BLZ_EIO, "%s: parse error at entry %lld", path, (long long)i);
+			goto done;
+		}
+		const int neg = d0 > c.p && d0[-1] == '-';
+		uint64_t mag = 0;
+		for (const char *d = d0; d < q; d++)
+			mag = mag * 10 + (uint64_t)(*d - '0');
+		c.p = q;
+		if (true_residue) {
+			const uint64_t r = mag % prime;
+			out[i] = (neg && r) ? prime - r : r;
+		} else {
+			/* a negative entry is blz_save_block's "%d" of a u32 from 2^31 on */
+			const uint64_t word = !neg ? mag : (mag >= 1 && mag <= 0x80000000ull ? 0x100000000ull - mag : UINT64_MAX);
+			if (word >= prime) {
+				rc = blz_fail(BLZ_EINVAL, "%s: entry %lld out of bound", path, (long long)i);
+				goto done;
+			}
+			out[i] = word;
+		}
+	}
+	while (c.p < c.end && is_blank(*c.p))
+		c.p++;
+	if (c.p < c.end)
+		rc = blz_fail(BLZ_EIO, "%s: more than %lld entries", path, (long long)len);
+done:
+	munmap(base, (size_t)st.st_size);
+	return rc;
+}
+
+int blz_rhs_load(const char *path, uint64_t prime, int64_t len, uint64_t *b)
+{
+	if (!path || prime < 2 || prime >= (1ull << 62) || len < 0 || (!b && len > 0))
+		return blz_fail(BLZ_EINVAL, "blz_rhs_load: bad argument");
+	return load_column(path, prime, len, 1, b);
+}
+
+int blz_check_solution(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+		       int64_t *bad_row)
+{
+	if (!matrix_path || !rhs_path || !x_path || prime < 2 || prime >= (1ull << 62))
+		return blz_fail(BLZ_EINVAL, "blz_check_solution: bad argument");
+	blz_coo M;
+	int rc = blz_mm_load(matrix_path, prime, &M);
+	if (rc != BLZ_OK)
+		return rc;
+	const int64_t xlen = right ? M.ncols : M.nrows, blen = right ? M.nrows : M.ncols;
+	uint64_t *x = malloc(sizeof *x * (size_t)(xlen + 1)), *b = malloc(sizeof *b * (size_t)(blen + 1));
+	unsigned __int128 *y = calloc((size_t)(blen + 1), sizeof *y);
+	if (!x || !b || !y)
+		rc = blz_fail(BLZ_ENOMEM, "cannot allocate the vectors");
+	if (rc == BLZ_OK)
+		rc = load_column(x_path, prime, xlen, 0, x);
+	if (rc == BLZ_OK)
+		rc = load_column(rhs_path, prime, blen, 1, b);
+	if (rc == BLZ_OK) {
+		/* unreduced 128-bit sums, one reduction per word: value < 2^32, x < 2^62, entries per row or column < 2^34 */
+		for (int64_t u = 0; u < M.nnz; u++) {
+			const int64_t i = right ? M.j[u] : M.i[u], j = right ? M.i[u] : M.j[u];
+			y[j] += (unsigned __int128)M.x[u] * x[i];
+		}
+		for (int64_t j = 0; j < blen; j++)
+			if ((uint64_t)(y[j] % prime) != b[j]) {
+				if (bad_row)
+					*bad_row = j;
+				rc = 2;
+				break;
+			}
+	}
+	free(x);
+	free(b);
+	free(y);
+	blz_coo_free(&M);
+	return rc;
+}
+
 /* rank of a kernel block: the RREF of its row space, row by row (the GPU's k_rref restated), stopping at full rank */
 
 static uint64_t host_invmod(uint64_t a, uint64_t p)

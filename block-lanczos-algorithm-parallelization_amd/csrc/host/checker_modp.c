@@ -3,6 +3,8 @@
  * that kernels computed modulo primes above 2^31-1 can be checked too.  Same flags (:43-76), same verdict
  * lines and exit codes: "OK" + exit 0, or a KO message + exit 1.  Plain C, no GPU.
  * --independent (no reference counterpart) also asks that the kernel vectors be linearly independent mod P.
+ * --rhs FILE (no reference counterpart) checks a solution instead: --kernel names the file of x, and M*x == b (--right)
+ * or x*M == b (--left) is asked for the vector b of FILE.
  */
 #define _GNU_SOURCE
 #include <err.h>
@@ -17,9 +19,10 @@ int main(int argc, char **argv)
 	struct option longopts[] = {
 		{"matrix", required_argument, NULL, 'm'}, {"kernel", required_argument, NULL, 'k'},
 		{"prime", required_argument, NULL, 'p'}, {"right", no_argument, NULL, 'r'},
-		{"left", no_argument, NULL, 'l'}, {"independent", no_argument, NULL, 'i'}, {NULL, 0, NULL, 0}
+		{"left", no_argument, NULL, 'l'}, {"independent", no_argument, NULL, 'i'},
+		{"rhs", required_argument, NULL, 'b'}, {NULL, 0, NULL, 0}
 	};
-	char *matrix = NULL, *kernel = NULL;
+	char *matrix = NULL, *kernel = NULL, *rhs = NULL;
 	unsigned long long prime = 0;
 	int right = 0, independent = 0, ch;
 	while ((ch = getopt_long(argc, argv, "", longopts, NULL)) != -1) {
@@ -30,6 +33,7 @@ int main(int argc, char **argv)
 		case 'r': right = 1; break;
 		case 'l': right = 0; break;
 		case 'i': independent = 1; break;
+		case 'b': rhs = optarg; break;
 		default: errx(1, "Unknown option\n");
 		}
 	}
@@ -42,7 +46,23 @@ int main(int argc, char **argv)
 		printf("--right                     check right kernel vectors\n");
 		printf("--left                      check left kernel vectors [default]\n");
 		printf("--independent               also check that the kernel vectors are linearly independent\n");
+		printf("--rhs FILENAME              check a solution: --kernel holds x, FILENAME holds b, and M*x == b (--right)\n");
+		printf("                            or x*M == b (--left) is verified\n");
 		exit(0);
+	}
+	if (rhs) {
+		printf("Reading Matrix from %s, solution from %s and right-hand side from %s\n", matrix, kernel, rhs);
+		int64_t bad = 0;
+		const int rcs = blz_check_solution(matrix, rhs, kernel, prime, right, &bad);
+		if (rcs == 0) {
+			printf("OK\n");
+			exit(EXIT_SUCCESS);
+		}
+		if (rcs == 2) {
+			printf("KO: %s != b (row %lld)\n", right ? "M*x" : "x*M", (long long)bad);
+			exit(EXIT_FAILURE);
+		}
+		errx(1, "%s", blz_last_error());
 	}
 	printf("Reading Matrix from %s and kernel from %s\n", matrix, kernel);
 	long long row = 0;

@@ -28,7 +28,7 @@
 
 static long n = 1;
 static uint64_t prime;
-static char *matrix_filename, *kernel_filename;
+static char *matrix_filename, *kernel_filename, *rhs_filename;
 static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis;
 static int stop_after = -1, checkpoint_timer = 60, device, gpus = 1;
 
@@ -74,6 +74,9 @@ static void usage(char **argv)
 	printf("                            a later run with the same arguments skips the renumbering and the CSR builds\n");
 	printf("--basis                     reduce the final block to independent kernel vectors (exact elimination mod P\n");
 	printf("                            on the GPU) and store only those with --output-file\n");
+	printf("--rhs FILENAME              solve M*x = b (--right) or x*M = b (--left) for the vector b of FILENAME (MatrixMarket\n");
+	printf("                            array, one column; signed entries are reduced mod P, so -1 means P-1): the matrix\n");
+	printf("                            gets b as a dense border and --output-file receives the solution x\n");
 	printf("--device D                  first HIP device to run on [default 0]\n");
 	printf("--gpus G                    row-partition the matrix over G GPUs of this node (devices D..D+G-1), RCCL\n");
 	printf("                            all-gather of the block before each product [default 1]\n");
@@ -81,6 +84,8 @@ static void usage(char **argv)
 	printf("The --matrix and --prime arguments are required\n");
 	printf("The --stop-after and --output-file arguments mutually exclusive\n");
 	printf("The --stop-after and --basis arguments mutually exclusive\n");
+	printf("The --rhs argument excludes --stop-after and --gpus above 1, and --basis (the solution is taken from the\n");
+	printf("kernel basis of the bordered matrix, which --rhs computes itself; it is one vector, not a block)\n");
 	exit(0);
 }
 
@@ -93,7 +98,8 @@ static void process_command_line_options(int argc, char **argv)
 		{"stop-after", required_argument, NULL, 's'}, {"checkpoint", optional_argument, NULL, 'c'},
 		{"load-checkpoint", no_argument, NULL, 'L'}, {"device", required_argument, NULL, 'd'},
 		{"gpus", required_argument, NULL, 'g'}, {"verify", no_argument, NULL, 'V'},
-		{"cache", no_argument, NULL, 'C'}, {"basis", no_argument, NULL, 'B'}, {"help", no_argument, NULL, 'h'}, {NULL, 0, NULL, 0}
+		{"cache", no_argument, NULL, 'C'}, {"basis", no_argument, NULL, 'B'}, {"rhs", required_argument, NULL, 'R'},
+		{"help", no_argument, NULL, 'h'}, {NULL, 0, NULL, 0}
 	};
 	int ch;
 	while ((ch = getopt_long(argc, argv, "", longopts, NULL)) != -1) {
@@ -118,6 +124,7 @@ static void process_command_line_options(int argc, char **argv)
 		case 'V': verify = true; break;
 		case 'C': use_cache = true; break;
 		case 'B': basis = true; break;
+		case 'R': rhs_filename = optarg; break;
 		case 'h': usage(argv); break;
 		default: errx(1, "Unknown option\n");
 		}
@@ -127,6 +134,8 @@ static void process_command_line_options(int argc, char **argv)
 	if (kernel_filename != NULL && stop_after > 0)
 		usage(argv);
 	if (basis && stop_after > 0)
+		usage(argv);
+	if (rhs_filename != NULL && (stop_after > 0 || basis || gpus > 1))
 		usage(argv);
 	if (prime >= (1ull << 62))
 		errx(1, "p is capped at 2**62 - 1.");
@@ -379,6 +388,21 @@ int main(int argc, char **argv)
 	fprintf(stderr, "  - [matrix coordinate integer general] %ld x %ld with %ld nz\n", (long)M.nrows, (long)M.ncols,
 		(long)M.nnz);
 	fprintf(stderr, "  - Read in %.2fs\n", wtime() - t_load);
+	uint64_t *rhs = NULL;
+	if (rhs_filename) {
+		/* M*x = b / x*M = b as kernel vectors of [M | b] / [M ; b]: the matrix gets one empty column / row (so the cache
+		 * key, the blocks and the checkpoints are those of the bordered operator) and b goes to the device as its border */
+		const int64_t len = right_kernel ? M.nrows : M.ncols;
+		printf("Loading right-hand side from %s\n", rhs_filename);
+		rhs = malloc(sizeof *rhs * (size_t)(len + 1));
+		if (!rhs)
+			errx(1, "cannot allocate the right-hand side");
+		CHECK(blz_rhs_load(rhs_filename, prime, len, rhs));
+		if (right_kernel)
+			M.ncols++;
+		else
+			M.nrows++;
+	}
 
 	{
 		const char *lb = getenv("BLZ_LOOPBACK");
@@ -422,6 +446,9 @@ int main(int argc, char **argv)
 	}
 	team.P = P;
 	team_run(OP_MATRIX);
+	if (rhs)
+		CHECK(blz_set_rhs(ctx, rhs));
+	free(rhs);
 	blz_prepared_free(P);
 	const int64_t nrows = right_kernel ? M.ncols : M.nrows;
 	const int64_t ncols = right_kernel ? M.nrows : M.ncols;
@@ -541,7 +568,25 @@ int main(int argc, char **argv)
 		else
 			printf("  - KO: no kernel vector\n");
 	}
-	if (kernel_filename && k == 0) {
+	if (rhs_filename) {		/* no reference counterpart: blz_solution, include/blz.h */
+		int status = 0;
+		CHECK(blz_solution(ctx, v, &status));
+		printf("Solve:\n");
+		if (status == 0)
+			printf(right_kernel ? "  - OK: M*x == b\n" : "  - OK: x*M == b\n");
+		else if (status == 1)
+			printf("  - KO: no solution found\n");
+		else
+			errx(1, "the solution failed its verification on the GPU");
+		if (status != 0) {
+			printf("Not saving result (no solution)\n");
+		} else if (kernel_filename) {
+			printf("Saving result in %s\n", kernel_filename);
+			CHECK(blz_save_block(kernel_filename, nrows - 1, 1, v));
+		} else {
+			printf("Not saving result (no --output given)\n");
+		}
+	} else if (kernel_filename && k == 0) {
 		printf("Not saving result (no kernel vector)\n");
 	} else if (kernel_filename && k < n) {
 		team_get(BLZ_V, v);

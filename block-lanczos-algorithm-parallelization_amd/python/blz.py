@@ -355,6 +355,24 @@ def check_independent(kernel_path, prime):
     return int(rank.value), int(cols.value)
 
 
+def rhs_load(path, prime, length):
+    """blz_rhs_load(): the `length` words of a right-hand side file, signed entries reduced as true residues."""
+    b = np.zeros(max(length, 1), dtype=np.uint64)
+    check(lib().blz_rhs_load(path.encode(), C.c_uint64(prime), C.c_int64(length), ptr(b)))
+    return b[:length]
+
+
+def check_solution(matrix_path, rhs_path, x_path, prime, right=False):
+    """blz_check_solution(): (0, None) when M x == b (right) / x M == b, else (2, first differing row); raises on
+    file / format errors."""
+    row = C.c_int64(-1)
+    rc = lib().blz_check_solution(matrix_path.encode(), rhs_path.encode(), x_path.encode(), C.c_uint64(prime),
+                                  C.c_int(int(right)), C.byref(row))
+    if rc < 0:
+        check(rc)
+    return rc, (int(row.value) if rc == 2 else None)
+
+
 def checkpoint_save(path, prime, n, right, nrows, iterations, v, p):
     check(lib().blz_checkpoint_save(path.encode(), C.c_uint64(prime), C.c_int(n), C.c_int(int(right)),
                                     C.c_int64(nrows), C.c_int64(iterations), ptr(u64(v)), ptr(u64(p))))
@@ -421,6 +439,31 @@ class Context:
         r = C.c_int(0)
         check(lib().blz_prepared_describe(P.h, C.byref(r), None, None))
         self.right = bool(r.value)
+
+    def set_matrix_rhs(self, M, b, right=False):
+        """blz_set_matrix_rhs(): M x = b (right; b has M.nrows words) or x M = b (b has M.ncols words) as the bordered
+        operator; rows(V) then counts the border row."""
+        b = u64(b)
+        assert b.size == (M.nrows if right else M.ncols), (b.size, M.nrows, M.ncols, right)
+        check(lib().blz_set_matrix_rhs(self.h, C.byref(M.c), C.c_int(int(right)), ptr(b)))
+        self.right = bool(right)
+
+    def set_rhs(self, b):
+        """blz_set_rhs(): the border for a matrix already set with the extra empty last row / column."""
+        b = u64(b)
+        assert b.size == self.rows(TMP), (b.size, self.rows(TMP))
+        check(lib().blz_set_rhs(self.h, ptr(b)))
+
+    @property
+    def has_rhs(self):
+        return bool(lib().blz_has_rhs(self.h))
+
+    def solution(self):
+        """blz_solution(): (status, x) -- x is None unless status == 0 (1: no solution found, 2: verification failed)."""
+        x = np.zeros(max(self.rows(V) - 1, 1), dtype=np.uint64)
+        status = C.c_int(-1)
+        check(lib().blz_solution(self.h, ptr(x), C.byref(status)))
+        return int(status.value), (x[:self.rows(V) - 1] if status.value == 0 else None)
 
     def rows(self, block):
         return int(lib().blz_rows(self.h, C.c_int(block)))
@@ -609,6 +652,18 @@ def comm_unique_id():
     buf = (C.c_char * 128)()
     check(lib().blz_comm_unique_id(buf, C.c_size_t(128)))
     return bytes(buf)
+
+
+def solve_rhs(M, b, prime, n, right=False, batch=16, device=0):
+    """M x = b (right) / x M = b on one GPU: dict(status, x, iterations, final_check)."""
+    with Context(prime, n, device) as ctx:
+        ctx.set_matrix_rhs(M, b, right)
+        ctx.init_v()
+        while not ctx.iterate(batch)[1]:
+            pass
+        fc = ctx.final_check()
+        status, x = ctx.solution()
+        return dict(status=status, x=x, iterations=ctx.iterations, final_check=fc)
 
 
 def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0, basis=False):

@@ -213,6 +213,22 @@ int blz_check_kernel(const char *matrix_path, const char *kernel_path, uint64_t 
  * column count.  No reference counterpart (checker_modp.c only tests v != 0 and x^T M = 0).  Host only, no GPU. */
 int blz_check_independent(const char *kernel_path, uint64_t prime, int *rank, int *cols);
 
+/* A right-hand side for blz_set_matrix_rhs (no reference counterpart: the reference finds kernel vectors only).  Reads a
+ * MatrixMarket "array integer general" file of len x 1 entries, the format blz_save_block writes, into b[0..len).
+ * Entries are signed decimal integers taken as TRUE residues: -1 becomes p - 1.  This is deliberately NOT the matrix
+ * loader's wrap through a u32 (blz_mm_load, above), which restates a quirk of the reference's parser and has no meaning
+ * for a vector of residues below p < 2^62 -- and not blz_save_block's "%d" rendering of words from 2^31 to 2^32 - 1
+ * either: write such words as plain decimals.  A banner that is not "array integer general" is BLZ_EFORMAT; a size line
+ * other than len x 1, an entry that does not parse or has 20 digits or more, and trailing entries are BLZ_EIO. */
+int blz_rhs_load(const char *path, uint64_t prime, int64_t len, uint64_t *b);
+
+/* Host check of a solution file against a right-hand side file: x (len x 1, as blz_save_block writes it, entries below
+ * prime) and b (as blz_rhs_load reads it) with M x == b (right != 0: x has M's column count, b its row count) or
+ * x M == b (right == 0) mod prime, by unreduced 128-bit sums like blz_check_kernel.  Returns 0 = equal, 2 = not equal
+ * (*bad_row, may be NULL = the first word of the product that differs from b), or a negative BLZ_E* code. */
+int blz_check_solution(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+		       int64_t *bad_row);
+
 /* Checkpoints (openMP/lanczos_modp.c:571-676, :933-940, :1013-1022).  blz_checkpoint_save writes
  * one binary file atomically (tmp + rename): v, p, iteration count, prime, n, shape.
  * The *_ref_text pair reads/writes the reference's five text files (v.txt tmp.txt Av.txt p.txt
@@ -252,6 +268,25 @@ int blz_prepare_for(const blz_ctx *c, const blz_coo *M, int right, int nranks, b
 uint64_t blz_prepare_key(const blz_ctx *c, uint64_t content_hash, int64_t mrows, int64_t mcols, int64_t nnz, int right,
 			 int nranks);
 int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank);
+/* Solve M x = b (right != 0; b has M->nrows words) or x M = b (right == 0; b has M->ncols words), all words below p, as
+ * kernel vectors of the bordered operator M' = [M | b] resp. [M ; b] with a non-zero last coordinate.  b is NOT stored
+ * in the matrix (its values are u32; b holds residues below p < 2^62): M is prepared with the dimension raised by one --
+ * an empty column resp. row, so every layout is sized for it and blz_rows(ctx, BLZ_V) reports one more row, the border
+ * row, last in the original numbering -- and b stays on the device as a dense border that two kernels apply behind
+ * each product (blz_spmv included):  tmp[r, :] += b[r] * v[border, :]  after the product that writes the rows of tmp,
+ * Av[border, :] = sum_r b[r] * tmp[r, :]  after the other.  Iterations, checkpoints, blz_final_check, blz_kernel_basis
+ * work as on any matrix; the second product runs without the fused inner products (blz_slab_plan reports fused == 0).
+ * One rank only: with nranks > 1, a communicator or a loopback group attached the call fails with BLZ_EINVAL.
+ *   blz_set_matrix_rhs  the one-call form (prepare, upload, set the border)
+ *   blz_set_rhs         sets the border on a context whose matrix the CALLER has set with the extra empty last row
+ *                       (right == 0) / column (right != 0), e.g. through blz_prepare_for / blz_prepared_load /
+ *                       blz_set_matrix_prepared (the CLI's --cache); b has blz_rows(ctx, BLZ_TMP) words
+ *   blz_has_rhs         1 when the context carries a border
+ * Setting a matrix again drops the border. */
+int blz_set_matrix_rhs(blz_ctx *ctx, const blz_coo *M, int right, const uint64_t *b);
+int blz_set_rhs(blz_ctx *ctx, const uint64_t *b);
+int blz_has_rhs(const blz_ctx *ctx);
+
 /* The solver renumbers rows internally (blz_reorder; BLZ_NO_REORDER=1 disables it).  Nothing of it is visible
  * through this ABI: blz_set_block / blz_get_block / blz_init_v / checkpoints all speak the ORIGINAL row numbering,
  * and results are bit-identical either way.  With nranks > 1 a rank's slab is a set of original rows that need
@@ -380,6 +415,14 @@ int blz_block_rref(blz_ctx *ctx, int block, uint64_t *rref, int *rank, int32_t *
  * Leaves the basis in columns 0..k-1 of V and zeroes the others; z (n x n, may be NULL) gets the combination of the
  * original columns of V that gives each basis vector (column j; zero for j >= k).  Collective with several ranks. */
 int blz_kernel_basis(blz_ctx *ctx, int *k, uint64_t *z);
+
+/* The solution of a context with a right-hand side, in the state blz_iterate leaves on stop.  Runs blz_kernel_basis,
+ * takes the first basis column whose border word is non-zero, scales it on the device so that the border word becomes
+ * p - 1 (V keeps it in column 0, the other columns zero), recomputes the product of that column with the border applied
+ * into TMP and checks on the GPU that it is zero (M x - b), then writes x (blz_rows(ctx, BLZ_V) - 1 words, original
+ * numbering, the border row left out).  *status: 0 = solved and verified; 1 = no kernel vector with a non-zero border
+ * word (an inconsistent system, or an unlucky start), x untouched; 2 = the verification failed (a bug), x untouched. */
+int blz_solution(blz_ctx *ctx, uint64_t *x, int *status);
 
 /* Asynchronous snapshot of (v, p, iteration count) for checkpoints (openMP/lanczos_modp.c:1013-1022 stops its loop
  * for them).  blz_snapshot_begin, called between two blz_iterate calls, enqueues the device-to-host copies of this

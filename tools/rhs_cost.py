@@ -1,0 +1,94 @@
+"""What the dense border of a right-hand-side solve costs per iteration.
+
+    python tools/rhs_cost.py [--workload gl7d19] [--steps 20] [--warmup 3] [--repeats 5]
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/rhs_cost.py --trace-only
+
+Three contexts on bench.py's synthetic matrix of the workload, in one process, timed in alternation (one region of
+`steps` iterations each per round, `repeats` rounds, medians): the plain solve, the plain solve with BLZ_NO_FUSE=1
+(the second product without the fused inner products, which a bordered context cannot use), and the bordered solve
+with a seeded right-hand side.  bordered - nofuse isolates the two border kernels; nofuse - plain is the loss of the
+fusion.  Prints one JSON line with the times and the bytes the border moves (the model the times are held against).
+--trace-only runs the bordered context alone, for a kernel trace: k_border_update / k_border_dot / k_border_finalize
+appear there by name.
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "block-lanczos-algorithm-parallelization_amd", "python"))
+
+
+def border_bytes(rows0, rows1, width, word):
+    """bytes per iteration the border adds: (update, dot, the unfused block_dot's two block reads)"""
+    tmp = rows1 * width * word
+    return dict(update=2 * tmp + rows1 * word, dot=tmp + rows1 * word, block_dot=2 * rows0 * width * word)
+
+
+def main():
+    import bench
+    import blz
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--workload", default="gl7d19", choices=sorted(bench.WORKLOADS))
+    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--trace-only", action="store_true")
+    args = ap.parse_args()
+    w = bench.WORKLOADS[args.workload]
+    p, n, right = w["prime"], w["n"], w["right"]
+    M = blz.Matrix.synth(w["rows"], w["cols"], w["nnz"], w["seed"], p, pattern=w["pattern"])
+    b = np.random.default_rng(0x52485300).integers(0, p, size=M.nrows if right else M.ncols, dtype=np.uint64)
+
+    def make(kind):
+        if kind == "nofuse":
+            os.environ["BLZ_NO_FUSE"] = "1"         # read once, when the context is created
+        try:
+            ctx = blz.Context(p, n)
+        finally:
+            os.environ.pop("BLZ_NO_FUSE", None)
+        if kind == "bordered":
+            ctx.set_matrix_rhs(M, b, right)
+        else:
+            ctx.set_matrix(M, right)
+        ctx.init_v()
+        return ctx
+
+    kinds = ("bordered",) if args.trace_only else ("plain", "nofuse", "bordered")
+    ctxs = {k: make(k) for k in kinds}
+    for ctx in ctxs.values():
+        done, stopped, _ = ctx.iterate(args.warmup)
+        assert done == args.warmup and not stopped
+    times = {k: [] for k in kinds}
+    for _ in range(1 if args.trace_only else args.repeats):
+        for k in kinds:
+            ctx = ctxs[k]
+            ctx.sync()
+            t0 = time.perf_counter()
+            done, stopped, _ = ctx.iterate(args.steps)
+            ctx.sync()
+            times[k].append((time.perf_counter() - t0) / args.steps * 1e3)
+            assert done == args.steps and not stopped
+    ctx = ctxs["bordered"]
+    word, width = ctx.word_bytes, ctx.plan(False)["width"]
+    out = dict(workload=args.workload, n=n, prime=p, steps=args.steps, repeats=len(times["bordered"]),
+               fused={k: bool(ctxs[k].plan(right)["fused"]) for k in kinds},
+               ms_per_step={k: statistics.median(v) for k, v in times.items()},
+               ms_per_step_all={k: [round(t, 4) for t in v] for k, v in times.items()},
+               border_bytes=border_bytes(ctx.rows(blz.V), ctx.rows(blz.TMP), width, word))
+    if not args.trace_only:
+        kern = {}
+        for k in ("nofuse", "bordered"):            # the same products and block_dot alone (blz_time_kernel), for the split
+            kern[k] = {name: ctxs[k].time_kernel(which, 20) for which, name in ((0, "spmv1"), (1, "spmv2"), (2, "block_dot"))}
+        out["kernel_ms"] = kern
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
