@@ -194,6 +194,11 @@ struct blz_ctx {
 	bool fuse_local_off = false;	/* this matrix: the second product runs the staged form and block_dot its own kernel (gathers that hit) */
 	int un = 0;			/* the caller's block width; cfg.n is the width in HBM (below) */
 	bool use_graph = false;		/* BLZ_GRAPH=1: single-GPU iterations are replayed from a captured hipGraph */
+	bool explicit_p = false;	/* BLZ_EXPLICIT_P=1: the iteration writes p every step (A/B against the rotating form) */
+	/* the rotating form of the iteration (enqueue_iteration) leaves p as X * E: X = slab[BLZ_P] (the v of the step before,
+	 * untouched), E n x n in `small`.  Set while that may be so; materialize_p() makes slab[BLZ_P] = p again */
+	bool p_implicit = false;
+	long long rot_swaps = 0;	/* swaps of slab[BLZ_V] / slab[BLZ_P] by the batch being enqueued (blz_iterate) */
 	hipGraphExec_t iter_graph = nullptr;
 	bool external_exchange = false;
 	bool force_comm = false;	/* BLZ_FORCE_COMM=1: issue the collectives even on one rank (plumbing test) */
@@ -267,6 +272,31 @@ static inline char *slab_ptr(const blz_ctx *c, int block) { return (char *)c->sl
 static inline const void *operand_ptr(const blz_ctx *c, int block)
 {
 	return c->nranks == 1 ? c->slab[block] : c->gath[side_of(block)];
+}
+
+/* p is slab[BLZ_P] as it stands: E <- I, flags down.  (Synchronous: outside the loop only.) */
+static int explicit_p_state(blz_ctx *c)
+{
+	const int np = c->cfg.n;
+	std::vector<u64> tail((size_t)(small_words(np) - small_E(np)), 0);
+	for (int i = 0; i < np; i++)
+		tail[(size_t)i * np + i] = 1;
+	HIPCHK(hipStreamSynchronize(c->stream));
+	HIPCHK(hipMemcpy(c->small + small_E(np), tail.data(), tail.size() * sizeof(u64), hipMemcpyHostToDevice));
+	c->p_implicit = false;
+	return BLZ_OK;
+}
+
+/* slab[BLZ_P] <- X * E = p and E <- I, before anything outside the loop looks at p.  E is read from device memory (the
+ * host never learns it) and the pass does not look at the stop flag: p is the same block before and after the stop. */
+static int materialize_p(blz_ctx *c)
+{
+	if (!c->p_implicit)
+		return BLZ_OK;
+	const int np = c->cfg.n;
+	HIPCHK(hipSetDevice(c->device));
+	HIPCHK(launch_block_mul(c->cfg, c->slab[BLZ_P], c->count[0], np, np, c->small + small_E(np), c->stream));
+	return explicit_p_state(c);
 }
 
 static void free_csr(DevCsr &A)
@@ -376,6 +406,8 @@ extern "C" int blz_create(blz_ctx **out, int device, uint64_t prime, int n)
 	c->fuse_dot = !(nf && nf[0] == '1');
 	const char *ug = getenv("BLZ_GRAPH");
 	c->use_graph = ug && ug[0] == '1';
+	const char *xp = getenv("BLZ_EXPLICIT_P");
+	c->explicit_p = xp && xp[0] == '1';
 	if (const char *ac = getenv("BLZ_AG_CHUNKS"))
 		if (atoi(ac) >= 1 && atoi(ac) <= 64)
 			c->ag_chunks = atoi(ac);
@@ -386,6 +418,11 @@ extern "C" int blz_create(blz_ctx **out, int device, uint64_t prime, int n)
 	HIPCHK(hipEventCreate(&c->ev1));
 	HIPCHK(hipMalloc(&c->small, small_words(np_) * sizeof(u64)));
 	HIPCHK(hipMemset(c->small, 0, small_words(np_) * sizeof(u64)));
+	{
+		int rc_ = explicit_p_state(c);
+		if (rc_ != BLZ_OK)
+			return rc_;
+	}
 	HIPCHK(hipMalloc(&c->dot_send, (size_t)2 * np_ * np_ * sizeof(u64)));
 	HIPCHK(hipMemset(c->dot_send, 0, (size_t)2 * np_ * np_ * sizeof(u64)));
 	HIPCHK(hipMalloc(&c->dot_recv, (size_t)2 * np_ * np_ * sizeof(u64)));
@@ -833,6 +870,11 @@ extern "C" int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int ra
 	}
 	HIPCHK(hipMemset(c->ctl, 0, sizeof(DevCtl)));
 	c->host_ctl = DevCtl{};
+	{
+		int rc_ = explicit_p_state(c);		/* p = 0 as it stands */
+		if (rc_ != BLZ_OK)
+			return rc_;
+	}
 	c->have_matrix = true;
 	return BLZ_OK;
 }
@@ -1173,6 +1215,11 @@ extern "C" int blz_set_block(blz_ctx *c, int block, const uint64_t *host)
 		src = tmp.data();
 	}
 	HIPCHK(hipStreamSynchronize(c->xstream));
+	if (block == BLZ_P) {	/* p is what the caller says from here on */
+		int rc_ = explicit_p_state(c);
+		if (rc_ != BLZ_OK)
+			return rc_;
+	}
 	/* this rank's rows */
 	int rc = put_rows(c, c->slab[block], src + c->first[sd] * n, c->count[sd]);
 	if (rc != BLZ_OK || c->nranks == 1 || !c->gath[sd])
@@ -1202,6 +1249,11 @@ extern "C" int blz_get_block(blz_ctx *c, int block, uint64_t *host)
 	NEED_MATRIX(c);
 	if (block < 0 || block > 3 || !host)
 		return blz_fail(BLZ_EINVAL, "blz_get_block: bad argument");
+	if (block == BLZ_P) {
+		int rc_ = materialize_p(c);
+		if (rc_ != BLZ_OK)
+			return rc_;
+	}
 	HIPCHK(hipStreamSynchronize(c->stream));
 	HIPCHK(hipStreamSynchronize(c->xstream));
 	const int sd = side_of(block), n = c->un;
@@ -1294,6 +1346,11 @@ extern "C" int blz_init_v(blz_ctx *c)
 	c->gath_holds[0] = c->gath_holds[1] = -1;
 	HIPCHK(hipMemset(c->ctl, 0, sizeof(DevCtl)));
 	c->host_ctl = DevCtl{};
+	{
+		int rc_ = explicit_p_state(c);		/* p = 0 as it stands */
+		if (rc_ != BLZ_OK)
+			return rc_;
+	}
 	/* :624-625: one sequential stream over the whole block in ORIGINAL row order; a rank keeps the rows it owns. */
 	const int n = c->un;
 	const int64_t keep = c->count[0] * n, lo = c->first[0], hi = c->first[0] + c->count[0];
@@ -1559,7 +1616,10 @@ extern "C" int blz_spmv(blz_ctx *c, int transpose, int src_block, int dst_block)
 			return blz_fail(BLZ_EINVAL, "blz_spmv: on several ranks product %d reads a block of side %d and writes one of side %d",
 					t, 1 - c->row_side[t], c->row_side[t]);
 	}
-	int rc = enqueue_spmv(c, transpose ? 1 : 0, src_block, dst_block);
+	int rc = (src_block == BLZ_P || dst_block == BLZ_P) ? materialize_p(c) : BLZ_OK;
+	if (rc != BLZ_OK)
+		return rc;
+	rc = enqueue_spmv(c, transpose ? 1 : 0, src_block, dst_block);
 	if (rc != BLZ_OK)
 		return rc;
 	HIPCHK(hipStreamSynchronize(c->stream));
@@ -1610,7 +1670,10 @@ extern "C" int blz_semi_inverse(blz_ctx *c, int *npiv, uint64_t *winv, uint64_t 
 extern "C" int blz_orthogonalize(blz_ctx *c)
 {
 	NEED_MATRIX(c);
-	int rc = enqueue_ortho(c);
+	int rc = materialize_p(c);	/* the stand-alone update is the explicit one, in place */
+	if (rc != BLZ_OK)
+		return rc;
+	rc = enqueue_ortho(c);
 	if (rc != BLZ_OK)
 		return rc;
 	HIPCHK(hipStreamSynchronize(c->stream));
@@ -1637,11 +1700,30 @@ static int enqueue_iteration(blz_ctx *c)
 	/* the semi-inverse kernel also writes the coefficient image when the block update runs on the matrix cores
 	 * (round 2: a launch of its own between the two) */
 	const bool img = ortho_uses_mfma(c->cfg, c->count[0]);
+	/* The rotating form (matrix-core update, no captured graph: a graph's launches have fixed arguments).  While every d[j]
+	 * is non-zero -- every step but a few -- p' = v * winv does not depend on p, so it is not written: the update reads v,
+	 * X and Av (p = X * E), writes v' into X's buffer, and the next step's (X, E) is (this v, untouched, winv).  When some
+	 * d[j] = 0 the update also writes p' = X * (E (1 - D)) + v * winv into v's buffer and E <- I: at n = 8 out of the same
+	 * image, at n = 16 after a pass that makes X = p first (a launch that returns at once on every other step).  Either way
+	 * the two buffers have changed places: slab[BLZ_V] is v' for every later consumer. */
+	const bool rot = img && !c->use_graph && !c->explicit_p;
 	{
 		Span sp(c, PK_SEMI);
-		HIPCHK(launch_semi_inverse(c->cfg, dot_sums(c), c->small, c->ctl, 1, img, c->stream));	/* :644 */
+		HIPCHK(launch_semi_inverse(c->cfg, dot_sums(c), c->small, c->ctl, 1, img, c->stream, rot ? c->un : 0));	/* :644 */
 	}
-	return enqueue_ortho(c, img);							/* :652-656 */
+	if (!rot)
+		return enqueue_ortho(c, img);						/* :652-656 */
+	const int np = c->cfg.n;
+	Span sp(c, PK_ORTHO);
+	if (np == 16)
+		HIPCHK(launch_block_mul_gated(c->cfg, c->slab[BLZ_P], c->count[0], np, np, c->small + small_Emat(np), c->ctl,
+					      c->small + small_materialize(np), c->stream));
+	HIPCHK(launch_orthogonalize_rotate(c->cfg, slab_ptr(c, BLZ_V), slab_ptr(c, BLZ_AV), slab_ptr(c, BLZ_P), c->count[0],
+					   c->small, c->ctl, c->stream));
+	std::swap(c->slab[BLZ_V], c->slab[BLZ_P]);
+	c->p_implicit = true;
+	c->rot_swaps++;
+	return BLZ_OK;
 }
 
 extern "C" int blz_iterate(blz_ctx *c, int max_iters, int *done, int *stopped, float *ms)
@@ -1652,6 +1734,7 @@ extern "C" int blz_iterate(blz_ctx *c, int max_iters, int *done, int *stopped, f
 	if (c->external_exchange && c->nranks > 1)
 		return blz_fail(BLZ_EINVAL, "blz_iterate: the context is in external-exchange mode");
 	const long long before = c->host_ctl.iterations;
+	c->rot_swaps = 0;
 	HIPCHK(hipEventRecord(c->ev0, c->stream));
 	const bool graph = c->use_graph && c->nranks == 1 && !c->force_comm && !c->profiling && max_iters > 1;
 	if (graph && !c->iter_graph) {
@@ -1667,19 +1750,31 @@ extern "C" int blz_iterate(blz_ctx *c, int max_iters, int *done, int *stopped, f
 		HIPCHK(hipGraphInstantiate(&c->iter_graph, g, nullptr, nullptr, 0));
 		hipGraphDestroy(g);
 	}
+	int enq_rc = BLZ_OK;
 	for (int it = 0; it < max_iters; it++) {
 		if (graph) {
 			HIPCHK(hipGraphLaunch(c->iter_graph, c->stream));
 			continue;
 		}
-		int rc = enqueue_iteration(c);
-		if (rc != BLZ_OK)
-			return rc;
+		enq_rc = enqueue_iteration(c);
+		if (enq_rc != BLZ_OK)
+			break;		/* what was enqueued still runs: the swaps below are reconciled with it before the error goes out */
 	}
 	HIPCHK(hipEventRecord(c->ev1, c->stream));
 	int rc = fetch_ctl(c);
+	/* fetch_ctl fails on a device error only: how many steps ran is then unknown, the swaps below cannot be reconciled, and
+	 * the context is unusable from here on (destroy it) */
 	if (rc != BLZ_OK)
-		return rc;
+		return enq_rc != BLZ_OK ? enq_rc : rc;
+	/* The rotating form swapped slab[BLZ_V] and slab[BLZ_P] once per ENQUEUED iteration, the device exchanged the roles of
+	 * the two buffers once per iteration that RAN.  Invariant: ctl->iterations advances exactly when the block update runs
+	 * (k_semi_inverse* increments it iff npiv > 0, and raises the stop flag otherwise, which turns the update and every
+	 * later kernel of the batch into a no-op).  So (enqueued - run) swaps were one too many each: undo them, i.e. swap back
+	 * once if that number is odd.  (A batch of the explicit form swapped nothing.) */
+	if (c->rot_swaps > 0 && ((c->rot_swaps - (c->host_ctl.iterations - before)) & 1))
+		std::swap(c->slab[BLZ_V], c->slab[BLZ_P]);
+	if (enq_rc != BLZ_OK)
+		return enq_rc;
 	if (ms)
 		HIPCHK(hipEventElapsedTime(ms, c->ev0, c->ev1));
 	if (done)
@@ -1690,6 +1785,8 @@ extern "C" int blz_iterate(blz_ctx *c, int max_iters, int *done, int *stopped, f
 }
 
 extern "C" int64_t blz_iterations(const blz_ctx *c) { return c ? c->host_ctl.iterations : -1; }
+
+extern "C" int blz_p_implicit(const blz_ctx *c) { return c && c->p_implicit ? 1 : 0; }
 
 extern "C" int blz_set_iterations(blz_ctx *c, int64_t iterations)
 {
@@ -1781,7 +1878,10 @@ extern "C" int blz_block_rref(blz_ctx *c, int block, uint64_t *rref, int *rank, 
 	std::vector<uint64_t> E((size_t)n * n);
 	std::vector<int32_t> piv((size_t)n);
 	int r = 0;
-	const int rc = rref_to_host(c, block, E.data(), &r, piv.data());
+	int rc = block == BLZ_P ? materialize_p(c) : BLZ_OK;
+	if (rc != BLZ_OK)
+		return rc;
+	rc = rref_to_host(c, block, E.data(), &r, piv.data());
 	if (rc != BLZ_OK)
 		return rc;
 	if (rref)
@@ -1930,6 +2030,11 @@ extern "C" int blz_time_kernel(blz_ctx *c, int which, int reps, float *ms_mean)
 	NEED_MATRIX(c);
 	if (reps < 1 || !ms_mean || which < 0 || which > 3)
 		return blz_fail(BLZ_EINVAL, "blz_time_kernel: bad argument");
+	if (which == 3) {	/* the explicit block update, in place on v and p */
+		int rc = materialize_p(c);
+		if (rc != BLZ_OK)
+			return rc;
+	}
 	HIPCHK(hipEventRecord(c->ev0, c->stream));
 	for (int r = 0; r < reps; r++) {
 		int rc = BLZ_OK;
@@ -2023,6 +2128,11 @@ extern "C" int blz_snapshot_begin(blz_ctx *c)
 			}
 		}
 		c->snap_bytes = bytes;
+	}
+	{
+		int rc = materialize_p(c);
+		if (rc != BLZ_OK)
+			return rc;
 	}
 	const bool staged = c->snap_dev[0] && c->snap_dev[1];
 	if (staged) {

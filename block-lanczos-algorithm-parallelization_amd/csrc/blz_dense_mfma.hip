@@ -26,6 +26,12 @@
  *
  * n = 16: two chains per 16-row tile, [v | p] x [c ; vtAvd] (K' = 256, 4 MFMAs per t) and v x winv (K' = 128, 2 per t).
  * n = 8:  one chain, [v | p] x [[c | winv] ; [vtAvd | 0]] (K' = 128, 2 per t): columns 0..7 of the tile are v', 8..15 p'.
+ *
+ * Inside the iteration the kernels also run "rotating" (DESIGN.md section 12): p is kept as X * E (X = the block v of the step
+ * before), the image holds E * vtAvd in vtAvd's place, v' goes into X's buffer, and while every d[j] is non-zero p' is not
+ * written at all (one flag in `small`, uniform over the device; at n = 16 the v x winv chain is skipped with it).  At n = 8 a
+ * step with some d[j] = 0 takes its p' from the same chain, [v | X] x [[c | winv] ; [E vtAvd | E (1 - D)]]: the image's
+ * fourth quarter carries the term (d ? 0 : p), which the kernel then does not add (at n = 16 X has been made p beforehand).
  */
 #include "blz_kernels.h"
 #include "ortho_img.h"
@@ -157,12 +163,18 @@ MODP_DEV void ortho_tile_load(OrthoTile<NT> &R, const u64 *V, const u64 *AV, con
 }
 
 template <int NT, bool ST>
-__global__ void __launch_bounds__((OG<NT, ST>::THREADS))
-k_ortho_mfma(u64 *__restrict__ V, const u64 *__restrict__ AV, u64 *__restrict__ Pb, long long rows,
-	     const u64 *__restrict__ small, const unsigned char *__restrict__ img, const DevCtl *__restrict__ ctl)
+__global__ void __launch_bounds__((OG<NT, ST>::THREADS)) __attribute__((amdgpu_waves_per_eu(OG<NT, ST>::WAVES_PER_SIMD)))
+k_ortho_mfma(const u64 *V, const u64 *__restrict__ AV, const u64 *Pb, u64 *Vout, u64 *Pout, long long rows,
+	     const u64 *__restrict__ small, const unsigned char *__restrict__ img, const DevCtl *__restrict__ ctl,
+	     const u64 *__restrict__ skip_p)
 {
+	/* V / Pb are read, Vout / Pout written: the same two buffers, in place (Vout = V, Pout = Pb) or crossed (Vout = Pb,
+	 * Pout = V: the rotating form of the iteration) -- hence no __restrict__ on them.  Either way a wavefront has read its
+	 * tile's rows of both before it writes them, and no other wavefront touches those rows. */
 	if (ctl->stop)
 		return;
+	/* device-uniform: every d[j] is non-zero and the caller keeps p implicit (p' = v * winv is never looked at): no p' */
+	const bool skip = skip_p && *skip_p != 0;
 	using G = OG<NT, ST>;
 	constexpr bool PF = G::PREFETCH;
 	constexpr int NN = NT * NT;
@@ -190,7 +202,8 @@ k_ortho_mfma(u64 *__restrict__ V, const u64 *__restrict__ AV, u64 *__restrict__ 
 	/* which output this lane's tile column is, and its selector d */
 	const int jout = NT == 16 ? col : (col & 7);
 	const bool is_p = NT == 8 && col >= 8;
-	const bool dj = small[3 * NN + jout] != 0;
+	/* the term that is no product, (d ? Av : v) or (d ? 0 : p): `dj` picks it per lane.  n = 8, rotating: p's is in the image */
+	const bool dj = small[3 * NN + jout] != 0 || (is_p && skip_p != nullptr);
 	OrthoTile<NT> R;
 	if (PF && wave < ntiles)
 		ortho_tile_load<NT, ST>(R, V, AV, Pb, rows, wave, lane, h, jout, is_p, dj);
@@ -247,7 +260,7 @@ k_ortho_mfma(u64 *__restrict__ V, const u64 *__restrict__ AV, u64 *__restrict__ 
 			for (int ks = 0; ks < G::KS1; ks++)
 				acc1 = __builtin_amdgcn_mfma_i32_16x16x64_i8(A[ks], Bl[(ks * G::ND + s) * 64 + lane], acc1, 0, 0, 0);
 			v4i acc2 = { 0, 0, 0, 0 };
-			if (NT == 16) {
+			if (NT == 16 && !skip) {
 				const int i2 = init[(1 * G::ND + s) * 16 + col];
 				acc2 = (v4i){ i2, i2, i2, i2 };
 #pragma unroll
@@ -317,8 +330,9 @@ k_ortho_mfma(u64 *__restrict__ V, const u64 *__restrict__ AV, u64 *__restrict__ 
 				const long long rr = r0 + o / ROWB;
 				if (rr < rows) {
 					const size_t to = (size_t)rr * ROWB + (o % ROWB);
-					*(v4i *)((unsigned char *)V + to) = xv;
-					*(v4i *)((unsigned char *)Pb + to) = yv;
+					*(v4i *)((unsigned char *)Vout + to) = xv;
+					if (!skip)
+						*(v4i *)((unsigned char *)Pout + to) = yv;
 				}
 			}
 			__builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -335,15 +349,17 @@ k_ortho_mfma(u64 *__restrict__ V, const u64 *__restrict__ AV, u64 *__restrict__ 
 			x = addmod(x, fconst, PR);
 			x = addmod(x, base1[reg], PR);
 			if (NT == 16) {
-				V[at] = x;
-				u64 y = fold61(L2[reg], H2[reg]);
-				y = addmod(y, fconst, PR);
-				y = addmod(y, base2[reg], PR);
-				Pb[at] = y;
-			} else if (is_p) {
-				Pb[at] = x;
-			} else {
-				V[at] = x;
+				Vout[at] = x;
+				if (!skip) {
+					u64 y = fold61(L2[reg], H2[reg]);
+					y = addmod(y, fconst, PR);
+					y = addmod(y, base2[reg], PR);
+					Pout[at] = y;
+				}
+			} else if (!is_p) {
+				Vout[at] = x;
+			} else if (!skip) {
+				Pout[at] = x;
 			}
 		}
 	}
@@ -399,7 +415,7 @@ static void ortho_mfma_shape(int *threads, int *per_cu)
 
 template <int NT, bool ST>
 static void ortho_mfma_go(const KernelCfg &c, void *V, const void *AV, void *P, int64_t rows, const u64 *small, const DevCtl *ctl,
-			  hipStream_t s, bool img_ready)
+			  hipStream_t s, bool img_ready, void *Vout, void *Pout, const u64 *skip_p)
 {
 	int threads = 0, per_cu = 0;
 	ortho_mfma_shape<NT, ST>(&threads, &per_cu);
@@ -412,24 +428,27 @@ static void ortho_mfma_go(const KernelCfg &c, void *V, const void *AV, void *P, 
 	if (!img_ready)		/* inside the iteration the semi-inverse kernel has built the image already */
 		hipLaunchKernelGGL((k_ortho_mfma_prep<NT>), dim3(OG<NT>::NCH * OG<NT>::ND * 16 / 4), dim3(256), 0, s, small, img, ctl);
 	const size_t lds = OG<NT, ST>::lds_bytes(threads);
-	hipLaunchKernelGGL((k_ortho_mfma<NT, ST>), dim3((unsigned)blocks), dim3(threads), lds, s, (u64 *)V, (const u64 *)AV, (u64 *)P,
-			   (long long)rows, small, img, ctl);
+	hipLaunchKernelGGL((k_ortho_mfma<NT, ST>), dim3((unsigned)blocks), dim3(threads), lds, s, (const u64 *)V, (const u64 *)AV,
+			   (const u64 *)P, (u64 *)Vout, (u64 *)Pout, (long long)rows, small, img, ctl, skip_p);
 }
 
 hipError_t launch_orthogonalize_mfma(const KernelCfg &c, void *V, const void *AV, void *P, int64_t rows, const u64 *small,
-				     const DevCtl *ctl, hipStream_t s, bool img_ready)
+				     const DevCtl *ctl, hipStream_t s, bool img_ready, bool rotate)
 {
 	if (rows <= 0)
 		return hipSuccess;
+	/* in place, or the rotating form of the iteration: v' into p's buffer, p' (when it is written at all) into v's */
+	void *Vout = rotate ? P : V, *Pout = rotate ? V : P;
+	const u64 *skip_p = rotate ? small + small_skip_p(c.n) : nullptr;
 	/* n = 8 (64-byte rows: a fragment load covers 1 KB of consecutive rows anyway) loads fragments straight from HBM:
 	 * the staged form is no faster there (115.6 / 116.0 against 113.9 / 114.6 us on the GL7d19 shape); BLZ_MFMA_STAGE8=1
 	 * takes it for A/B */
 	if (c.n == 16)
-		ortho_mfma_go<16, true>(c, V, AV, P, rows, small, ctl, s, img_ready);
+		ortho_mfma_go<16, true>(c, V, AV, P, rows, small, ctl, s, img_ready, Vout, Pout, skip_p);
 	else if (c.mfma_stage8)
-		ortho_mfma_go<8, true>(c, V, AV, P, rows, small, ctl, s, img_ready);
+		ortho_mfma_go<8, true>(c, V, AV, P, rows, small, ctl, s, img_ready, Vout, Pout, skip_p);
 	else
-		ortho_mfma_go<8, false>(c, V, AV, P, rows, small, ctl, s, img_ready);
+		ortho_mfma_go<8, false>(c, V, AV, P, rows, small, ctl, s, img_ready, Vout, Pout, skip_p);
 	return hipGetLastError();
 }
 

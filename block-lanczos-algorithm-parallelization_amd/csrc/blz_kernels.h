@@ -139,11 +139,18 @@ hipError_t launch_dot_finalize(const KernelCfg &c, const u64 *partial, int nbloc
  * Reads vtAv/vtAAv (reduced mod p first: they may be sums over ranks), writes the rest and
  * updates ctl.  sequential/lanczos_modp.c:342-438 and :460-475. */
 hipError_t launch_semi_inverse(const KernelCfg &c, const u64 *sums, u64 *small, DevCtl *ctl, int in_loop, int build_img,
-			       hipStream_t s);
+			       hipStream_t s, int rot_un = 0);
 /* `sums` = the 2 n^2 words vtAv | vtAAv the kernel starts from: `small` itself on one rank, the landing place of the
  * all-reduce on several (sums of the ranks' residues; the kernel writes their residues to `small` unless the stop flag
  * is up, so `small` never holds anything but residues).  build_img != 0: the kernel also writes the coefficient image
- * of the matrix-core block update (c.mfma_img; ortho_mfma_supported(c) must hold): one launch instead of two. */
+ * of the matrix-core block update (c.mfma_img; ortho_mfma_supported(c) must hold): one launch instead of two.
+ * rot_un != 0 (with in_loop and build_img; = the caller's block width, the columns past it never pivot): the rotating
+ * form of the iteration, where p is kept as X * E (X = the block v of the step before, E n x n at small_E()).  While every
+ * d[j] is non-zero p' = v * winv needs no pass over memory: the image gets E * vtAvd in vtAvd's place (p * vtAvd =
+ * X * (E * vtAvd)), E <- winv and the skip flag goes up.  Otherwise E <- I and p' is written: at n = 8 the image also gets
+ * E * (1 - D) (p' = X * (E (1 - D)) + v * winv out of the one chain, no other launch); at n = 16 the old E is set aside at
+ * small_Emat() and the materialise flag goes up (launch_block_mul_gated makes X <- X * Emat = p before the update runs as
+ * it always did).  `small`'s own panels are what they are without rot_un.  An iteration that stops (npiv = 0) changes none of it. */
 
 /* Row-local update in place: V <- v', P <- p'.  sequential/lanczos_modp.c:478-491, :655-656 */
 hipError_t launch_orthogonalize(const KernelCfg &c, void *V, const void *AV, void *P, int64_t rows,
@@ -165,7 +172,11 @@ hipError_t launch_reduce_modp(const KernelCfg &c, void *dst, const void *src, in
 size_t ortho_mfma_image_bytes(void);
 bool ortho_mfma_supported(const KernelCfg &c);
 hipError_t launch_orthogonalize_mfma(const KernelCfg &c, void *V, const void *AV, void *P, int64_t rows, const u64 *small,
-				     const DevCtl *ctl, hipStream_t s, bool img_ready);
+				     const DevCtl *ctl, hipStream_t s, bool img_ready, bool rotate = false);
+/* the rotating form (matrix cores only, image built by the semi-inverse kernel with rot_un): reads v = V, p = P and Av,
+ * writes v' into P's buffer and -- unless the skip flag in `small` is up -- p' into V's: the caller swaps the two */
+hipError_t launch_orthogonalize_rotate(const KernelCfg &c, void *V, const void *AV, void *P, int64_t rows, const u64 *small,
+				       const DevCtl *ctl, hipStream_t s);
 
 /* block_dot_products on the matrix cores (p = 2^61-1, n = 8 / 16): same partial rows as launch_block_dot */
 bool block_dot_mfma_supported(const KernelCfg &c);
@@ -193,7 +204,15 @@ hipError_t launch_rref_merge(const KernelCfg &c, const u64 *stack, int64_t rows,
 			     hipStream_t s);
 /* X <- X * Z in place, row by row (rows x n words of the context's width, row stride ld; Z: n x n u64 residues) */
 hipError_t launch_block_mul(const KernelCfg &c, void *X, int64_t rows, int ld, int n, const u64 *Z, hipStream_t s);
+/* the same, but a no-op when the stop flag is up or *gate == 0 (device memory): the rotating iteration's general step */
+hipError_t launch_block_mul_gated(const KernelCfg &c, void *X, int64_t rows, int ld, int n, const u64 *Z, const DevCtl *ctl,
+				  const u64 *gate, hipStream_t s);
 
-static inline size_t small_words(int n) { return (size_t)6 * n * n; }
+/* behind the six panels: E (p = X * E), the E a general step multiplies X by, and two flag words */
+__host__ __device__ constexpr size_t small_E(int n) { return (size_t)6 * n * n; }
+__host__ __device__ constexpr size_t small_Emat(int n) { return (size_t)7 * n * n; }
+__host__ __device__ constexpr size_t small_skip_p(int n) { return (size_t)8 * n * n; }		/* this step writes no p' */
+__host__ __device__ constexpr size_t small_materialize(int n) { return (size_t)8 * n * n + 1; }	/* this step needs X <- X * Emat first */
+__host__ __device__ constexpr size_t small_words(int n) { return (size_t)8 * n * n + 8; }
 
 #endif

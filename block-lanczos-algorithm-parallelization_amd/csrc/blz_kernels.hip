@@ -2261,7 +2261,7 @@ __device__ static int ff_sweep(u64 *A, u64 *Wm, u64 *S, int n, int G, const ModP
 template <int MERS, int IMGN>
 __global__ void __launch_bounds__(1024)
 k_semi_inverse(const u64 *__restrict__ sums, u64 *__restrict__ small, DevCtl *__restrict__ ctl, int n, int G, ModP m, int in_loop,
-	       unsigned char *__restrict__ img)
+	       unsigned char *__restrict__ img, int rot_un)
 {
 	/* in_loop = 0: stand-alone call (blz_semi_inverse): neither obeys nor sets the sticky stop flag */
 	if (in_loop && ctl->stop)
@@ -2354,6 +2354,52 @@ k_semi_inverse(const u64 *__restrict__ sums, u64 *__restrict__ small, DevCtl *__
 		if (IMGN) {
 			coef[4 * nn + e] = ce;
 			coef[5 * nn + e] = ve;
+		}
+	}
+	if (IMGN && rot_un && npiv > 0) {
+		/* the rotating form (launch_semi_inverse): p = X * E.  Every branch here is uniform over the workgroup. */
+		u64 *Eg = small + small_E(n), *Emat = small + small_Emat(n);
+		const u64 want = rot_un >= 64 ? ~0ull : (1ull << rot_un) - 1;
+		const bool full = (dbits & want) == want;
+		__syncthreads();		/* coef's vtAvd panel is complete */
+		if (full) {
+			/* f = E * vtAvd into the image in vtAvd's place; then E <- winv */
+			for (int e = lane; e < nn; e += T) {
+				const int i = e / n, j = e % n;
+				Acc acc;
+				acc_zero(acc);
+				u32 cnt = 0;
+				for (int k = 0; k < n; k++) {
+					acc_mac64(acc, Eg[i * n + k], coef[5 * nn + k * n + j]);
+					if (++cnt == m.chunk) {
+						cnt = 0;
+						acc_set(acc, acc_reduce<MERS>(acc, m));
+					}
+				}
+				A[e] = acc_reduce<MERS>(acc, m);
+			}
+			__syncthreads();
+			for (int e = lane; e < nn; e += T) {
+				coef[5 * nn + e] = A[e];
+				Eg[e] = Wm[e];
+			}
+		} else {
+			/* the general step works on an explicit p: set the old E aside for the pass that makes it (none if E = I) */
+			int differs = 0;
+			for (int e = lane; e < nn; e += T) {
+				const u64 eo = Eg[e], id = (e / n == e % n) ? 1 : 0;
+				differs |= eo != id;
+				Emat[e] = eo;
+				Eg[e] = id;
+			}
+			differs = __syncthreads_or(differs);
+			if (lane == 0)
+				small[small_materialize(n)] = differs ? 1 : 0;
+		}
+		if (lane == 0) {
+			small[small_skip_p(n)] = full ? 1 : 0;
+			if (full)
+				small[small_materialize(n)] = 0;
 		}
 	}
 	if (lane == 0) {
@@ -2486,7 +2532,7 @@ __device__ static int ff_sweep_reg(u64 &a, u64 *w, u64 *s, int n, const ModP &m,
 template <int MERS, int LG, bool IMG>
 __global__ void __launch_bounds__(IMG ? 1024 : 64)
 k_semi_inverse_reg(const u64 *__restrict__ sums, u64 *__restrict__ small, DevCtl *__restrict__ ctl, int n, ModP m, int in_loop,
-		   unsigned char *__restrict__ img)
+		   unsigned char *__restrict__ img, int rot_un)
 {
 	constexpr int G = 1 << LG, T = IMG ? 1024 : 64;
 	const int nn = n * n, lane = threadIdx.x, i = (lane & 63) >> LG, k = lane & (G - 1);
@@ -2495,9 +2541,10 @@ k_semi_inverse_reg(const u64 *__restrict__ sums, u64 *__restrict__ small, DevCtl
 	/* the three loads go out together; the flag is looked at when they are back */
 	const int stop = in_loop ? ctl->stop : 0;
 	const u64 xr = sums[e], yr = sums[nn + e];
+	const u64 eo = (IMG && rot_un) ? small[small_E(n) + e] : 0;	/* the rotating form: p = X * E (launch_semi_inverse) */
 	if (stop)
 		return;
-	__shared__ u64 coef[IMG ? 6 * 64 : 1];
+	__shared__ u64 coef[IMG ? 7 * 64 : 1];	/* the six panels of `small`, and G of the rotating form (ortho_img.h) */
 	__shared__ int init_sh[IMG ? OG<8>::NE : 1];
 	if (lane < 64) {
 		u64 *vtAv = small, *vtAAv = small + nn, *winv = small + 2 * nn, *dvec = small + 3 * nn;
@@ -2569,10 +2616,35 @@ k_semi_inverse_reg(const u64 *__restrict__ sums, u64 *__restrict__ small, DevCtl
 			cmat[e] = ce;
 			vtAvd[e] = ve;
 		}
+		u64 fe = ve, ge = 0;
+		if (IMG && rot_un && npiv > 0) {	/* uniform: n = 8 = G, every lane of the wavefront owns an entry */
+			/* the rotating form: p = X * E.  The image gets f = E * vtAvd in vtAvd's place (p * vtAvd = X * f) */
+			const u64 want = (1ull << rot_un) - 1;
+			acc_zero(acc);
+			cnt = 0;
+			static_for<0, G>([&](auto qc) {
+				constexpr int Q = decltype(qc)::value;
+				const u64 eiq = col_bcast<Q, LG>(eo), vqk = shfl64(ve, (Q << LG) + k);
+				acc_mac64(acc, eiq, vqk);
+				if (++cnt == m.chunk) {
+					cnt = 0;
+					acc_set(acc, acc_reduce<MERS>(acc, m));
+				}
+			});
+			fe = acc_reduce<MERS>(acc, m);
+			const bool full = (dbits & want) == want;
+			/* every column pivots: p' = v * winv is not written, E <- winv.  Otherwise the update writes
+			 * p' = X * G + v * winv with G = E (1 - D) in the image's fourth quarter, and E <- I */
+			ge = (full || dk) ? 0 : eo;
+			small[small_E(n) + e] = full ? wn : (i == k ? 1 : 0);
+			if (lane == 0)
+				small[small_skip_p(n)] = full ? 1 : 0;
+		}
 		if (IMG) {		/* n = 8 = G: e = lane */
 			coef[2 * 64 + lane] = wn;
 			coef[4 * 64 + lane] = ce;
-			coef[5 * 64 + lane] = ve;
+			coef[5 * 64 + lane] = fe;
+			coef[6 * 64 + lane] = ge;
 		}
 		if (lane == 0) {
 			ctl->npiv = npiv;
@@ -2586,13 +2658,15 @@ k_semi_inverse_reg(const u64 *__restrict__ sums, u64 *__restrict__ small, DevCtl
 	}
 	if constexpr (IMG) {
 		__syncthreads();
-		ortho_image_build<8>(coef, img, init_sh, lane, T);
+		ortho_image_build<8>(coef, img, init_sh, lane, T, rot_un != 0);
 	}
 }
 
 hipError_t launch_semi_inverse(const KernelCfg &c, const u64 *sums, u64 *small, DevCtl *ctl, int in_loop, int build_img,
-			       hipStream_t s)
+			       hipStream_t s, int rot_un)
 {
+	if (rot_un && !(in_loop && build_img && rot_un <= c.n))
+		return hipErrorInvalidValue;
 	int G = 1, LG = 0;
 	while (G < c.n) {
 		G <<= 1;
@@ -2603,7 +2677,7 @@ hipError_t launch_semi_inverse(const KernelCfg &c, const u64 *sums, u64 *small, 
 		return hipErrorInvalidValue;
 	if (c.n <= 8) {		/* the whole n x n problem fits one wavefront's registers */
 #define SEMI_REG(MM, LL)                                                                                          \
-	hipLaunchKernelGGL((k_semi_inverse_reg<MM, LL, false>), dim3(1), dim3(64), 0, s, sums, small, ctl, c.n, c.m, in_loop, img)
+	hipLaunchKernelGGL((k_semi_inverse_reg<MM, LL, false>), dim3(1), dim3(64), 0, s, sums, small, ctl, c.n, c.m, in_loop, img, 0)
 #define SEMI_REG_LG(MM)                                                                                           \
 	do {                                                                                                      \
 		if (LG == 0) SEMI_REG(MM, 0);                                                                     \
@@ -2613,7 +2687,7 @@ hipError_t launch_semi_inverse(const KernelCfg &c, const u64 *sums, u64 *small, 
 	} while (0)
 		if (build_img)		/* n = 8, p = 2^61 - 1 (ortho_mfma_supported): 16 wavefronts, one 16-byte piece of the image each */
 			hipLaunchKernelGGL((k_semi_inverse_reg<61, 3, true>), dim3(1), dim3(1024), 0, s, sums, small, ctl, c.n, c.m, in_loop,
-					   img);
+					   img, rot_un);
 		else if (c.mers == 61)
 			SEMI_REG_LG(61);
 		else if (c.mers == 31)
@@ -2632,7 +2706,7 @@ hipError_t launch_semi_inverse(const KernelCfg &c, const u64 *sums, u64 *small, 
 		if (lds > 48 * 1024)                                                                               \
 			hipFuncSetAttribute((const void *)k_semi_inverse<MM, II>, hipFuncAttributeMaxDynamicSharedMemorySize,  \
 					    (int)lds);                                                             \
-		hipLaunchKernelGGL((k_semi_inverse<MM, II>), dim3(1), dim3(threads), lds, s, sums, small, ctl, c.n, G, c.m, in_loop, img); \
+		hipLaunchKernelGGL((k_semi_inverse<MM, II>), dim3(1), dim3(threads), lds, s, sums, small, ctl, c.n, G, c.m, in_loop, img, rot_un); \
 	} while (0)
 	if (build_img) {	/* n = 16, p = 2^61 - 1: all 16 wavefronts for the 49 KB image */
 		lds += (size_t)6 * c.n * c.n * sizeof(u64) + OG<16>::NE * sizeof(int);
@@ -2960,6 +3034,14 @@ static hipError_t ortho_dispatch(const KernelCfg &c, W *V, const W *AV, W *P, in
 bool ortho_uses_mfma(const KernelCfg &c, int64_t rows)
 {
 	return ortho_mfma_supported(c) && rows >= c.mfma_min_rows && rows > 0;
+}
+
+hipError_t launch_orthogonalize_rotate(const KernelCfg &c, void *V, const void *AV, void *P, int64_t rows, const u64 *small,
+				       const DevCtl *ctl, hipStream_t s)
+{
+	if (!ortho_uses_mfma(c, rows))
+		return hipErrorInvalidValue;	/* only the matrix-core kernels have the form: no fall-back */
+	return launch_orthogonalize_mfma(c, V, AV, P, rows, small, ctl, s, true, true);
 }
 
 hipError_t launch_orthogonalize(const KernelCfg &c, void *V, const void *AV, void *P, int64_t rows,
@@ -3320,8 +3402,11 @@ hipError_t launch_rref_merge(const KernelCfg &c, const u64 *stack, int64_t rows,
 /* X <- X * Z in place (rows x n, row stride ld words; Z: n x n u64 residues, row-major), lane = column */
 template <typename W, int MERS>
 __global__ void __launch_bounds__(BLOCK)
-k_block_mul(W *__restrict__ X, long long rows, int ld, int n, int G, const u64 *__restrict__ Z, ModP m)
+k_block_mul(W *__restrict__ X, long long rows, int ld, int n, int G, const u64 *__restrict__ Z, ModP m,
+	    const DevCtl *__restrict__ ctl, const u64 *__restrict__ gate)
 {
+	if ((ctl && ctl->stop) || (gate && *gate == 0))
+		return;
 	__shared__ u64 Zs[RREF_MAXN * RREF_MAXN];
 	for (int k = threadIdx.x; k < RREF_MAXN * RREF_MAXN; k += BLOCK) {
 		const int j = k / RREF_MAXN, cc = k % RREF_MAXN;
@@ -3351,6 +3436,12 @@ k_block_mul(W *__restrict__ X, long long rows, int ld, int n, int G, const u64 *
 
 hipError_t launch_block_mul(const KernelCfg &c, void *X, int64_t rows, int ld, int n, const u64 *Z, hipStream_t s)
 {
+	return launch_block_mul_gated(c, X, rows, ld, n, Z, nullptr, nullptr, s);
+}
+
+hipError_t launch_block_mul_gated(const KernelCfg &c, void *X, int64_t rows, int ld, int n, const u64 *Z, const DevCtl *ctl,
+				  const u64 *gate, hipStream_t s)
+{
 	if (n < 1 || n > RREF_MAXN)
 		return hipErrorInvalidValue;
 	if (rows <= 0)
@@ -3361,14 +3452,14 @@ hipError_t launch_block_mul(const KernelCfg &c, void *X, int64_t rows, int ld, i
 	const dim3 grid((unsigned)blocks), blk(BLOCK);
 	if (c.word == 4) {
 		if (c.mers == 31)
-			hipLaunchKernelGGL((k_block_mul<u32, 31>), grid, blk, 0, s, (u32 *)X, (long long)rows, ld, n, G, Z, c.m);
+			hipLaunchKernelGGL((k_block_mul<u32, 31>), grid, blk, 0, s, (u32 *)X, (long long)rows, ld, n, G, Z, c.m, ctl, gate);
 		else
-			hipLaunchKernelGGL((k_block_mul<u32, 0>), grid, blk, 0, s, (u32 *)X, (long long)rows, ld, n, G, Z, c.m);
+			hipLaunchKernelGGL((k_block_mul<u32, 0>), grid, blk, 0, s, (u32 *)X, (long long)rows, ld, n, G, Z, c.m, ctl, gate);
 	} else {
 		if (c.mers == 61)
-			hipLaunchKernelGGL((k_block_mul<u64, 61>), grid, blk, 0, s, (u64 *)X, (long long)rows, ld, n, G, Z, c.m);
+			hipLaunchKernelGGL((k_block_mul<u64, 61>), grid, blk, 0, s, (u64 *)X, (long long)rows, ld, n, G, Z, c.m, ctl, gate);
 		else
-			hipLaunchKernelGGL((k_block_mul<u64, 0>), grid, blk, 0, s, (u64 *)X, (long long)rows, ld, n, G, Z, c.m);
+			hipLaunchKernelGGL((k_block_mul<u64, 0>), grid, blk, 0, s, (u64 *)X, (long long)rows, ld, n, G, Z, c.m, ctl, gate);
 	}
 	return hipGetLastError();
 }

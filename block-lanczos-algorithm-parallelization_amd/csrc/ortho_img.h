@@ -30,6 +30,9 @@ struct OG {
 	 * and their 108 KB of staging areas -- 1.77 ms with 2 x 4 wavefronts, 1.56 with 12, 1.49 with 16 on the config-5 quarter
 	 * shape, which is what a bare streaming kernel with this traffic reaches.  n = 8: 256 (five workgroups per CU). */
 	static constexpr int THREADS = !ST ? 256 : (NT == 16 ? 1024 : 768);
+	/* wavefronts per SIMD the register allocation has to leave room for: what the workgroup needs, and for the direct form
+	 * the six it has always had (five workgroups per CU fit beside the images in LDS; at four the kernel loses) */
+	static constexpr int WAVES_PER_SIMD = !ST ? 6 : THREADS / 256;
 };
 
 /* digit t (signed, base 256) of x < 2^62: with C = 0x8080...80, x = sum_t (byte_t(x + C) - 128) 256^t and every
@@ -51,7 +54,8 @@ MODP_DEV u64 rot61(u64 x, int sh)
 template <int NT>
 MODP_DEV int coef_index(int ch, int kk, int col)
 {
-	/* returns an index into the digit table [3][NT*NT]: 0 = c, 1 = vtAvd, 2 = winv; -1 = zero */
+	/* returns an index into the digit table [4][NT*NT]: 0 = c, 1 = vtAvd, 2 = winv, 3 = p's own coefficient in p' (n = 8 and
+	 * the rotating form of the iteration only, see coefficient()); -1 = zero */
 	if (NT == 16) {
 		if (ch == 0)
 			return kk < 16 ? 0 * 256 + kk * 16 + col : 1 * 256 + (kk - 16) * 16 + col;
@@ -59,20 +63,24 @@ MODP_DEV int coef_index(int ch, int kk, int col)
 	}
 	if (col < 8)
 		return kk < 8 ? 0 * 64 + kk * 8 + col : 1 * 64 + (kk - 8) * 8 + col;
-	return kk < 8 ? 2 * 64 + kk * 8 + (col - 8) : -1;
+	return kk < 8 ? 2 * 64 + kk * 8 + (col - 8) : 3 * 64 + (kk - 8) * 8 + (col - 8);
 }
 
 /* coefficient of word kk and tile column col in chain ch (0 where the chain has none); the multiplier of K' = (kk, byte a)
  * is rot61(coefficient, 8 a) = coefficient * 2^(8a) mod p.  `small` is the context's [vtAv | vtAAv | winv | d | c | vtAvd]
- * (global memory, or a copy of the same six n x n panels anywhere else). */
+ * (global memory, or a copy of the same six n x n panels anywhere else).  with_pp (n = 8, the rotating form of the iteration):
+ * a seventh panel follows them, G with p' = X * G + v * winv (G = E (1 - D): the term (d ? 0 : p) of a general step as a
+ * product); without it that quarter of the image is zero and the term is added by the kernel. */
 template <int NT>
-MODP_DEV u64 coefficient(const u64 *small, int ch, int kk, int col)
+MODP_DEV u64 coefficient(const u64 *small, int ch, int kk, int col, bool with_pp = false)
 {
 	constexpr int NN = NT * NT;
 	const int ci = coef_index<NT>(ch, kk, col);
 	if (ci < 0)
 		return 0;
 	const int mat = ci / NN, at = ci % NN;
+	if (mat == 3)
+		return with_pp ? small[6 * NN + at] : 0;
 	return small[(mat == 0 ? 4 : (mat == 1 ? 5 : 2)) * NN + at];
 }
 
@@ -80,11 +88,12 @@ MODP_DEV u64 coefficient(const u64 *small, int ch, int kk, int col)
  * The whole image by ONE workgroup of `nthreads` threads: a thread makes 16 consecutive bytes of B at a time (one lane's
  * fragment of one K step and digit position: two coefficients, eight rotations each, one 16-byte store) and adds their
  * sum to the accumulator-start entry of its (chain, digit, column) in `init_sh` (LDS, OG<NT>::NE ints, zeroed here);
- * `coef` = the six-panel layout of `small` (LDS copy of the coefficients).  Ends with every thread past a barrier and the
- * image complete in `img`.
+ * `coef` = the six-panel layout of `small` (LDS copy of the coefficients; seven panels with with_pp, see coefficient()).
+ * Ends with every thread past a barrier and the image complete in `img`.
  */
 template <int NT>
-MODP_DEV void ortho_image_build(const u64 *coef, unsigned char *__restrict__ img, int *init_sh, int tid, int nthreads)
+MODP_DEV void ortho_image_build(const u64 *coef, unsigned char *__restrict__ img, int *init_sh, int tid, int nthreads,
+				bool with_pp = false)
 {
 	using G = OG<NT>;
 	for (int e = tid; e < G::NE; e += nthreads)
@@ -95,7 +104,7 @@ MODP_DEV void ortho_image_build(const u64 *coef, unsigned char *__restrict__ img
 		const int ln = item & 63, dg = (item >> 6) & 7, ks = item >> 9;
 		const int ch = ks < G::KS1 ? 0 : 1, kc = ch == 0 ? ks : ks - G::KS1;
 		const int E0 = 64 * kc + 16 * (ln >> 4), col = ln & 15;
-		const u64 c0 = coefficient<NT>(coef, ch, E0 >> 3, col), c1 = coefficient<NT>(coef, ch, (E0 >> 3) + 1, col);
+		const u64 c0 = coefficient<NT>(coef, ch, E0 >> 3, col, with_pp), c1 = coefficient<NT>(coef, ch, (E0 >> 3) + 1, col, with_pp);
 		u32 out[4] = { 0, 0, 0, 0 };
 		int sum = 0;
 #pragma unroll

@@ -582,6 +582,11 @@ class Context:
     def iterations(self):
         return int(lib().blz_iterations(self.h))
 
+    @property
+    def p_implicit(self):
+        """blz_p_implicit(): 1 while the iteration keeps p as X * E, 0 when the P block holds p itself (test hook)."""
+        return int(lib().blz_p_implicit(self.h))
+
     def set_iterations(self, its):
         check(lib().blz_set_iterations(self.h, C.c_int64(its)))
 

@@ -393,6 +393,11 @@ int blz_orthogonalize(blz_ctx *ctx);
  * of this call measured with HIP events on the context's stream. */
 int blz_iterate(blz_ctx *ctx, int max_iters, int *done, int *stopped, float *ms);
 int64_t blz_iterations(const blz_ctx *ctx);
+/* Test hook, read-only: 1 while the iteration keeps p implicit (as X * E: the block v of the step before and an n x n
+ * matrix on the device; blz_iterate on the matrix-core block update, unless BLZ_EXPLICIT_P=1 or BLZ_GRAPH=1), 0 when the
+ * P block holds p itself.  Every call that looks at P (blz_get_block, blz_snapshot_begin, blz_orthogonalize, ...) makes
+ * it explicit first; blz_set_block(P) makes it explicit. */
+int blz_p_implicit(const blz_ctx *ctx);
 int blz_set_iterations(blz_ctx *ctx, int64_t iterations);	/* --load-checkpoint */
 
 /* final_check(), :560-582, on V and on TMP (= M^T v of the last iteration). */
@@ -432,7 +437,10 @@ int blz_solution(blz_ctx *ctx, uint64_t *x, int *status);
  * thread (the checkpoint writer) while the owner is inside blz_iterate -- the one exception to one thread per handle
  * (the in-flight mark is an atomic: begin in the owner's thread sees a wait that finished in the writer's).
  * v == p == NULL drops the snapshot: a writer that has failed (memory, one rank's copy) must still collect from EVERY
- * context, or their next blz_snapshot_begin is refused.  One snapshot in flight per context. */
+ * context, or their next blz_snapshot_begin is refused.  One snapshot in flight per context.
+ * While the iteration keeps p implicit (blz_p_implicit), blz_snapshot_begin first makes the P block p: one more pass
+ * over that block on the compute stream (X <- X * E), after which it waits for that stream -- idle between two
+ * blz_iterate calls -- and resets E with a small blocking copy, before the asynchronous part above. */
 int blz_snapshot_begin(blz_ctx *c);
 int blz_snapshot_wait(blz_ctx *c, uint64_t *v, uint64_t *p, int64_t *iterations);
 
