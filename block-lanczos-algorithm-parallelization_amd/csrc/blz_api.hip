@@ -233,6 +233,12 @@ struct blz_ctx {
 	void *rhs = nullptr;		/* b: one word of the context's width per row of side 1, solver's numbering */
 	int64_t border = -1;		/* the border row of side 0 in the solver's numbering (perm[0][last]) */
 	u64 *border_partial = nullptr;	/* partial rows of the border dot */
+	/* several right-hand sides (blz_set_rhs_block, k > 1): rhs = rows x rhs_kp words, zero padded, and the k border rows of
+	 * side 0 (the last k of the original numbering) in the solver's numbering, on the host and on the device */
+	int rhs_k = 0, rhs_kp = 0;	/* 0 / 1: at most the single border above */
+	size_t border_partial_words = 0;	/* room in border_partial when the block form sized it */
+	std::vector<int64_t> border_rows;
+	long long *border_rows_dev = nullptr;
 };
 
 /* HIP-event span around one enqueue on the context's stream (only while profiling is on). */
@@ -488,6 +494,7 @@ extern "C" void blz_destroy(blz_ctx *c)
 	if (c->rref_ctl) hipFree(c->rref_ctl);
 	if (c->rhs) hipFree(c->rhs);
 	if (c->border_partial) hipFree(c->border_partial);
+	if (c->border_rows_dev) hipFree(c->border_rows_dev);
 	if (c->dot_send) hipFree(c->dot_send);
 	if (c->dot_recv) hipFree(c->dot_recv);
 	if (c->rs_recv) hipFree(c->rs_recv);
@@ -715,6 +722,8 @@ extern "C" int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int ra
 		c->rhs = nullptr;
 	}
 	c->border = -1;
+	c->rhs_k = c->rhs_kp = 0;
+	c->border_rows.clear();
 	/* side 0 = rows of v: rows of M for a left kernel, columns of M for a right kernel
 	 * (sequential/lanczos_modp.c:592-593). */
 	c->glob_rows[0] = right ? P->ncols : P->nrows;
@@ -949,6 +958,9 @@ extern "C" int blz_set_rhs(blz_ctx *c, const uint64_t *b)
 	if (!c->border_partial)
 		HIPCHK(hipMalloc(&c->border_partial, (size_t)border_dot_max_blocks(c->cfg) * BLZ_BORDER_MAXN * sizeof(u64)));
 	c->border = border;
+	c->rhs_k = 1;
+	c->rhs_kp = 0;
+	c->border_rows.clear();
 	/* the fused inner products would read the border row of Av before the border dot has written it: the second product
 	 * runs plain and block_dot as its own kernel */
 	c->fuse_local_off = true;
@@ -977,6 +989,110 @@ extern "C" int blz_set_matrix_rhs(blz_ctx *c, const blz_coo *M, int right, const
 }
 
 extern "C" int blz_has_rhs(const blz_ctx *c) { return c && c->have_matrix && c->rhs != nullptr; }
+
+extern "C" int blz_rhs_count(const blz_ctx *c) { return blz_has_rhs(c) ? (c->rhs_k > 1 ? c->rhs_k : 1) : 0; }
+
+static int rhs_block_refuse_k(const blz_ctx *c, const char *who, int k)
+{
+	if (k < 1 || k > c->un || k > BLZ_MAX_RHS)
+		return blz_fail(BLZ_EINVAL, "%s: %d right-hand sides: between 1 and min(n = %d, BLZ_MAX_RHS = %d) are possible", who, k,
+				c->un, BLZ_MAX_RHS);
+	return BLZ_OK;
+}
+
+extern "C" int blz_set_rhs_block(blz_ctx *c, int k, const uint64_t *b)
+{
+	if (!c || !c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "no matrix loaded (blz_set_matrix)");
+	HIPCHK(hipSetDevice(c->device));
+	if (!b)
+		return blz_fail(BLZ_EINVAL, "blz_set_rhs_block: b is NULL");
+	int rc = rhs_block_refuse_k(c, "blz_set_rhs_block", k);
+	if (rc != BLZ_OK)
+		return rc;
+	if (k == 1)
+		return blz_set_rhs(c, b);	/* one column is today's border, kernels and all */
+	if ((rc = rhs_refuse_ranks(c, "blz_set_rhs_block", true)) != BLZ_OK)
+		return rc;
+	if (c->csr[0].size() != 1 || c->csr[1].size() != 1 || c->short_side[0] || c->short_side[1] || c->glob_rows[0] < k)
+		return blz_fail(BLZ_EINVAL, "blz_set_rhs_block: the matrix was not set for a single rank in one piece");
+	HIPCHK(hipStreamSynchronize(c->stream));
+	const int64_t first = c->glob_rows[0] - k, len = c->glob_rows[1];
+	const int kp = border_kp(k);
+	std::vector<int64_t> rows((size_t)k);
+	{	/* the k border rows / columns of the matrix itself must be empty: the product whose rows live on side 0 says so */
+		const DevCsr &A = c->csr[c->row_side[0] == 0 ? 0 : 1][0];
+		if (A.rows != c->glob_rows[0])
+			return blz_fail(BLZ_EINVAL, "blz_set_rhs_block: unexpected slab shape");
+		for (int i = 0; i < k; i++) {
+			u32 rp[2] = { 0, 0 };
+			rows[(size_t)i] = c->perm[0].empty() ? first + i : c->perm[0][(size_t)(first + i)];
+			HIPCHK(hipMemcpy(rp, A.row_ptr + rows[(size_t)i], sizeof rp, hipMemcpyDeviceToHost));
+			if (rp[0] != rp[1])
+				return blz_fail(BLZ_EINVAL, "blz_set_rhs_block: the last %d %s of the matrix must be empty (they stand for the "
+						"right-hand sides)", k, c->right ? "columns" : "rows");
+		}
+	}
+	std::vector<uint64_t> bs((size_t)std::max<int64_t>(len, 1) * kp, 0);
+	for (int64_t r = 0; r < len; r++) {
+		const size_t at = (size_t)(c->perm[1].empty() ? r : c->perm[1][(size_t)r]) * kp;
+		for (int i = 0; i < k; i++) {
+			if (b[r * k + i] >= c->prime)
+				return blz_fail(BLZ_EINVAL, "blz_set_rhs_block: b[%lld, %d] is not below p", (long long)r, i);
+			bs[at + i] = b[r * k + i];
+		}
+	}
+	if (c->rhs)
+		hipFree(c->rhs);
+	c->rhs = nullptr;
+	HIPCHK(hipMalloc(&c->rhs, bs.size() * c->cfg.word));
+	if ((rc = put_words(c, c->rhs, bs.data(), (int64_t)bs.size())) != BLZ_OK)
+		return rc;
+	const size_t need = (size_t)border_dot_max_blocks(c->cfg) * kp * BLZ_BORDER_MAXN;
+	if (c->border_partial_words < need) {
+		if (c->border_partial)
+			hipFree(c->border_partial);
+		c->border_partial = nullptr;
+		c->border_partial_words = 0;
+		HIPCHK(hipMalloc(&c->border_partial, need * sizeof(u64)));
+		c->border_partial_words = need;
+	}
+	if (!c->border_rows_dev)
+		HIPCHK(hipMalloc(&c->border_rows_dev, BLZ_MAX_RHS * sizeof(long long)));
+	{
+		long long dev_rows[BLZ_MAX_RHS] = { 0 };
+		for (int i = 0; i < k; i++)
+			dev_rows[i] = rows[(size_t)i];
+		HIPCHK(hipMemcpy(c->border_rows_dev, dev_rows, sizeof dev_rows, hipMemcpyHostToDevice));
+	}
+	c->border_rows = rows;
+	c->border = rows[(size_t)k - 1];
+	c->rhs_k = k;
+	c->rhs_kp = kp;
+	c->fuse_local_off = true;	/* as in blz_set_rhs */
+	if (c->iter_graph) {
+		hipGraphExecDestroy(c->iter_graph);
+		c->iter_graph = nullptr;
+	}
+	return BLZ_OK;
+}
+
+extern "C" int blz_set_matrix_rhs_block(blz_ctx *c, const blz_coo *M, int right, int k, const uint64_t *b)
+{
+	if (!c || !M || !b)
+		return blz_fail(BLZ_EINVAL, "blz_set_matrix_rhs_block: NULL argument");
+	int rc = rhs_block_refuse_k(c, "blz_set_matrix_rhs_block", k);
+	if (rc != BLZ_OK || (rc = rhs_refuse_ranks(c, "blz_set_matrix_rhs_block", false)) != BLZ_OK)
+		return rc;
+	blz_coo Mb = *M;	/* the same triplets under a dimension raised by k: k empty rows (x M = b) / columns (M x = b) */
+	if (right)
+		Mb.ncols += k;
+	else
+		Mb.nrows += k;
+	if ((rc = blz_set_matrix(c, &Mb, right, 0, 1)) != BLZ_OK)
+		return rc;
+	return blz_set_rhs_block(c, k, b);
+}
 
 extern "C" int64_t blz_rows(const blz_ctx *c, int block)
 {
@@ -1483,6 +1599,15 @@ static inline const u64 *dot_sums(blz_ctx *c) { return exchanging(c) ? c->dot_re
 static int enqueue_border(blz_ctx *c, int transpose, int src, int dst, const DevCtl *ctl)
 {
 	const size_t row_bytes = (size_t)c->cfg.n * c->cfg.word;
+	if (c->rhs_k > 1) {	/* several right-hand sides: the same two passes, fused over the k columns */
+		if (c->row_side[transpose] == 1)
+			HIPCHK(launch_border_update_k(c->cfg, slab_ptr(c, dst), c->rhs, slab_ptr(c, src), c->border_rows_dev, c->rhs_k,
+						      c->count[1], ctl, c->stream));
+		else
+			HIPCHK(launch_border_dot_k(c->cfg, slab_ptr(c, src), c->rhs, c->count[1], c->border_partial, slab_ptr(c, dst),
+						   c->border_rows_dev, c->rhs_k, ctl, c->stream));
+		return BLZ_OK;
+	}
 	if (c->row_side[transpose] == 1)
 		HIPCHK(launch_border_update(c->cfg, slab_ptr(c, dst), c->rhs, slab_ptr(c, src) + (size_t)c->border * row_bytes, c->count[1],
 					    ctl, c->stream));
@@ -1971,6 +2096,8 @@ extern "C" int blz_solution(blz_ctx *c, uint64_t *x, int *status)
 	NEED_MATRIX(c);
 	if (!c->rhs || !x || !status)
 		return blz_fail(BLZ_EINVAL, "blz_solution: %s", !c->rhs ? "the context has no right-hand side (blz_set_matrix_rhs)" : "NULL argument");
+	if (c->rhs_k > 1)
+		return blz_fail(BLZ_EINVAL, "blz_solution: the context has %d right-hand sides: use blz_solution_block", c->rhs_k);
 	const int n = c->un, np = c->cfg.n;
 	const u64 p = c->prime;
 	int k = 0;
@@ -2022,6 +2149,113 @@ extern "C" int blz_solution(blz_ctx *c, uint64_t *x, int *status)
 	for (int64_t i = 0; i + 1 < c->glob_rows[0]; i++)	/* the border row is the last one in the original numbering */
 		x[i] = v[(size_t)i * n];
 	*status = 0;
+	return BLZ_OK;
+}
+
+/* the side-1 product of V with the border applied, past the stop (on control words of its own), tested for zero on the
+ * GPU like blz_final_check: *nonzero = some word of it is not zero */
+static int solution_residual(blz_ctx *c, int *nonzero)
+{
+	DevCtl *idle = nullptr;
+	HIPCHK(hipMalloc(&idle, sizeof(DevCtl)));
+	hipError_t e = hipMemsetAsync(idle, 0, sizeof(DevCtl), c->stream);
+	int rc = e == hipSuccess ? enqueue_product(c, !c->right, BLZ_V, BLZ_TMP, false, nullptr, idle) : BLZ_OK;
+	if (e == hipSuccess)
+		e = hipStreamSynchronize(c->stream);
+	hipFree(idle);
+	HIPCHK(e);
+	if (rc != BLZ_OK)
+		return rc;
+	HIPCHK(hipMemsetAsync(&c->ctl->flag_t_nonzero, 0, sizeof(int), c->stream));
+	HIPCHK(launch_any_nonzero(c->cfg, slab_ptr(c, BLZ_TMP), c->count[1] * c->cfg.n, &c->ctl->flag_t_nonzero, c->stream));
+	if ((rc = fetch_ctl(c)) != BLZ_OK)
+		return rc;
+	*nonzero = c->host_ctl.flag_t_nonzero != 0;
+	return BLZ_OK;
+}
+
+static inline uint64_t host_mulmod(uint64_t a, uint64_t b, uint64_t p) { return (uint64_t)((unsigned __int128)a * b % p); }
+
+extern "C" int blz_solution_block(blz_ctx *c, uint64_t *x, int *status)
+{
+	NEED_MATRIX(c);
+	if (!c->rhs || !x || !status)
+		return blz_fail(BLZ_EINVAL, "blz_solution_block: %s",
+				!c->rhs ? "the context has no right-hand side (blz_set_matrix_rhs_block)" : "NULL argument");
+	const int n = c->un, np = c->cfg.n, k = c->rhs_k > 1 ? c->rhs_k : 1;
+	const u64 p = c->prime;
+	int kb = 0;
+	int rc = blz_kernel_basis(c, &kb, nullptr);
+	if (rc != BLZ_OK)
+		return rc;
+	/* W = the k border rows of the kb basis vectors, next to -I_k: the basis vectors are v = (y, w) with M y + B w = 0, so a
+	 * combination V c has border part W c, and W c = -e_i makes its upper part a solution of system i */
+	const int cols = kb + k;
+	std::vector<uint64_t> A((size_t)k * cols, 0), brow((size_t)np);
+	for (int i = 0; i < k; i++) {
+		const int64_t row = k > 1 ? c->border_rows[(size_t)i] : c->border;
+		if ((rc = get_words(c, brow.data(), slab_ptr(c, BLZ_V) + (size_t)row * np * c->cfg.word, np)) != BLZ_OK)
+			return rc;
+		for (int j = 0; j < kb; j++)
+			A[(size_t)i * cols + j] = brow[(size_t)j];
+		A[(size_t)i * cols + kb + i] = p - 1;
+	}
+	/* reduced row echelon form of [W | -I] over W's columns */
+	std::vector<int> piv;
+	int r = 0;
+	for (int j = 0; j < kb && r < k; j++) {
+		int q = r;
+		while (q < k && A[(size_t)q * cols + j] == 0)
+			q++;
+		if (q == k)
+			continue;
+		for (int t = 0; t < cols && q != r; t++)
+			std::swap(A[(size_t)q * cols + t], A[(size_t)r * cols + t]);
+		const uint64_t inv = host_inverse(A[(size_t)r * cols + j], p);
+		for (int t = 0; t < cols; t++)
+			A[(size_t)r * cols + t] = host_mulmod(A[(size_t)r * cols + t], inv, p);
+		for (int i = 0; i < k; i++) {
+			const uint64_t f = A[(size_t)i * cols + j];
+			if (i == r || f == 0)
+				continue;
+			for (int t = 0; t < cols; t++) {
+				const uint64_t d = host_mulmod(f, A[(size_t)r * cols + t], p), a = A[(size_t)i * cols + t];
+				A[(size_t)i * cols + t] = a >= d ? a - d : a + p - d;
+			}
+		}
+		piv.push_back(j);
+		r++;
+	}
+	/* system i is solved by this basis exactly when -e_i lies in W's column space: its reduced column is zero below the
+	 * rank; then c = that column at the pivots, zero elsewhere */
+	std::vector<uint64_t> Z((size_t)n * n, 0);
+	for (int i = 0; i < k; i++) {
+		status[i] = 0;
+		for (int t = r; t < k; t++)
+			if (A[(size_t)t * cols + kb + i])
+				status[i] = 1;
+		if (status[i])
+			continue;
+		for (int t = 0; t < r; t++)
+			Z[(size_t)piv[(size_t)t] * n + i] = A[(size_t)t * cols + kb + i];
+	}
+	/* V <- V * C: column i = (y_i, -e_i), unsolved columns and the columns from k on zero */
+	if ((rc = block_mul(c, Z)) != BLZ_OK)
+		return rc;
+	int nonzero = 0;
+	if ((rc = solution_residual(c, &nonzero)) != BLZ_OK)
+		return rc;
+	if (nonzero) {
+		for (int i = 0; i < k; i++)
+			status[i] = 2;
+		return BLZ_OK;
+	}
+	std::vector<uint64_t> v((size_t)c->glob_rows[0] * n);
+	if ((rc = blz_get_block(c, BLZ_V, v.data())) != BLZ_OK)
+		return rc;
+	for (int64_t i = 0; i < c->glob_rows[0] - k; i++)	/* the border rows are the last k */
+		for (int j = 0; j < k; j++)
+			x[i * k + j] = v[(size_t)i * n + j];
 	return BLZ_OK;
 }
 

@@ -17,4 +17,17 @@ hipError_t launch_border_update(const KernelCfg &c, void *T, const void *B, cons
 hipError_t launch_border_dot(const KernelCfg &c, const void *T, const void *B, int64_t rows, u64 *partial, void *out_row,
 			     const DevCtl *ctl, hipStream_t s);
 
+/* k > 1 right-hand sides, 2 <= k <= BLZ_BORDER_MAXK: B = rows x border_kp(k) words of the context's width, row-major, zero
+ * padded; brow = the k border rows of side 0 in the solver's numbering, on the device.
+ * launch_border_update_k: T[r, :] = (T[r, :] + sum_i B[r, i] * V[brow[i], :]) mod p; V = the operand block (side 0).
+ * launch_border_dot_k: S[brow[i], :] = sum_r B[r, i] * T[r, :] mod p; S = the destination block (side 0); partial = room for
+ * border_dot_max_blocks(c) * border_kp(k) * BLZ_BORDER_MAXN u64 words.
+ * One pass over T serves all k.  No-ops once the stop flag is up. */
+#define BLZ_BORDER_MAXK 16
+int border_kp(int k);
+hipError_t launch_border_update_k(const KernelCfg &c, void *T, const void *B, const void *V, const long long *brow, int k,
+				  int64_t rows, const DevCtl *ctl, hipStream_t s);
+hipError_t launch_border_dot_k(const KernelCfg &c, const void *T, const void *B, int64_t rows, u64 *partial, void *S,
+			       const long long *brow, int k, const DevCtl *ctl, hipStream_t s);
+
 #endif

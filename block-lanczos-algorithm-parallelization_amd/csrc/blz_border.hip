@@ -9,6 +9,12 @@
  * Both are no-ops once the stop flag is up, like the products they follow.  Exact for every 2 <= p < 2^62: one
  * 128-bit (96-bit for 32-bit words) sum per output word, reduced with the reducers of modp.h, at most m.chunk
  * products between two reductions.
+ *
+ * With k > 1 right-hand sides (up to 16) B holds kp = k rounded up to a power of two words per row, zero padded, the k
+ * border rows of side 0 sit anywhere in the slab (brow[] holds their numbers), and the same two passes serve all k:
+ *   k_border_update_k tmp[r, :] += sum_i B[r, i] * v[brow[i], :]        one read and one write of tmp
+ *   k_border_dot_k    Av[brow[i], :] = sum_r B[r, i] * tmp[r, :]        one read of tmp, k accumulators per lane
+ *                     (k_border_finalize_k sums the partial k x n tiles and scatters the k rows)
  */
 #include "blz_border.h"
 
@@ -224,4 +230,246 @@ hipError_t launch_border_dot(const KernelCfg &c, const void *T, const void *B, i
 		hipLaunchKernelGGL((k_border_finalize<u64>), dim3(1), blk, 0, s, partial, (int)blocks, n, G, c.m.p, (u64 *)out_row, ctl);
 	}
 	return hipGetLastError();
+}
+
+/* ---- k right-hand sides: B = rows x KP words (KP = k rounded up to a power of two, zero padded) ---- */
+
+/*
+ * T[r, j] = (T[r, j] + sum_{i<k} B[r, i] * v[brow[i], j]) mod p.  The k x n words of the border rows of the operand block
+ * V are gathered into LDS once per workgroup (rows k..KP-1 are zero, like B's padding); a lane keeps its row of B in
+ * registers and one 128-bit (96-bit) sum per word of its 16 bytes of T, reduced after m.chunk products at the latest.
+ * Bytes: one read and one write of T, one read of B.
+ */
+template <typename W, int MERS, int VEC, bool POW2, int KP>
+__global__ void __launch_bounds__(BLOCK)
+k_border_update_k(W *__restrict__ T, const W *__restrict__ B, const W *__restrict__ V, const long long *__restrict__ brow,
+		  int k, long long rows, int n, int sh, ModP m, const DevCtl *__restrict__ ctl)
+{
+	if (ctl->stop)
+		return;
+	using A = typename std::conditional<sizeof(W) == 4, AccS, Acc>::type;
+	__shared__ u64 vs[KP][BLZ_BORDER_MAXN];
+	for (int q = threadIdx.x; q < KP * BLZ_BORDER_MAXN; q += BLOCK) {
+		const int i = q / BLZ_BORDER_MAXN, j = q % BLZ_BORDER_MAXN;
+		vs[i][j] = (i < k && j < n) ? (u64)V[brow[i] * n + j] : 0;
+	}
+	__syncthreads();
+	using Vec = WordVec<W, VEC>;
+	using BVec = WordVec<W, KP>;
+	Vec *__restrict__ T4 = (Vec *)T;
+	const BVec *__restrict__ B4 = (const BVec *)B;
+	const long long total = rows * n / VEC, step = (long long)gridDim.x * BLOCK;
+	for (long long q = (long long)blockIdx.x * BLOCK + threadIdx.x; q < total; q += step) {
+		const long long e = q * VEC;
+		const long long r = POW2 ? (e >> sh) : (e / n);
+		const int j = (int)(e - r * n);
+		const BVec b = B4[r];
+		Vec x = T4[q];
+		A acc[VEC];
+#pragma unroll
+		for (int u = 0; u < VEC; u++)
+			acc_set(acc[u], (u64)x.w[u]);
+		u32 cnt = 0;
+#pragma unroll
+		for (int i = 0; i < KP; i++) {
+#pragma unroll
+			for (int u = 0; u < VEC; u++)
+				acc_mac64(acc[u], (u64)b.w[i], vs[i][j + u]);
+			if (++cnt == m.chunk && i + 1 < KP) {
+				cnt = 0;
+#pragma unroll
+				for (int u = 0; u < VEC; u++)
+					acc_set(acc[u], acc_reduce<MERS>(acc[u], m));
+			}
+		}
+#pragma unroll
+		for (int u = 0; u < VEC; u++)
+			x.w[u] = (W)acc_reduce<MERS>(acc[u], m);
+		T4[q] = x;
+	}
+}
+
+/*
+ * partial[block][i][col] = sum over the block's rows of B[r, i] * T[r, col] mod p, i < KP.  Lanes as in k_border_dot; every
+ * loaded word of T feeds KP accumulators, so T is read once for all right-hand sides.  Rows in flight per lane shrink
+ * as KP grows (the row of B is KP words of registers per row in flight).
+ */
+template <typename W, int MERS, int KP>
+__global__ void __launch_bounds__(BLOCK)
+k_border_dot_k(const W *__restrict__ T, const W *__restrict__ B, long long rows, int n, int G, ModP m,
+	       u64 *__restrict__ partial, const DevCtl *__restrict__ ctl)
+{
+	if (ctl->stop)
+		return;
+	constexpr int U = KP <= 4 ? 4 : (KP == 8 ? 2 : 1);
+	using A = typename std::conditional<sizeof(W) == 4, AccS, Acc>::type;
+	using BVec = WordVec<W, KP>;
+	__shared__ u64 red[BLOCK / 64][BLZ_BORDER_MAXN];
+	const BVec *__restrict__ B4 = (const BVec *)B;
+	const int t = threadIdx.x, lane = t & 63, col = lane & (G - 1), gpb = BLOCK / G;
+	const bool mine = col < n;
+	const long long g0 = (long long)blockIdx.x * gpb + t / G, ng = (long long)gridDim.x * gpb;
+	A acc[KP];
+#pragma unroll
+	for (int i = 0; i < KP; i++)
+		acc_zero(acc[i]);
+	u32 cnt = 0;
+	for (long long r = g0; r < rows; r += ng * U) {
+		u64 x[U];
+		BVec b[U];
+#pragma unroll
+		for (int u = 0; u < U; u++) {
+			const long long rr = r + u * ng;
+			const bool ok = mine && rr < rows;
+			x[u] = ok ? (u64)T[rr * n + col] : 0;
+			b[u] = B4[rr < rows ? rr : 0];	/* (x = 0 makes the row count for nothing) */
+		}
+#pragma unroll
+		for (int u = 0; u < U; u++) {
+#pragma unroll
+			for (int i = 0; i < KP; i++)
+				acc_mac64(acc[i], (u64)b[u].w[i], x[u]);
+			if (++cnt == m.chunk) {
+				cnt = 0;
+#pragma unroll
+				for (int i = 0; i < KP; i++)
+					acc_set(acc[i], acc_reduce<MERS>(acc[i], m));
+			}
+		}
+	}
+#pragma unroll
+	for (int i = 0; i < KP; i++) {
+		u64 s = acc_reduce<MERS>(acc[i], m);
+		for (int off = G; off < 64; off <<= 1)
+			s = addmod(s, (u64)__shfl_xor((unsigned long long)s, off, 64), m.p);
+		if (lane < G)
+			red[t >> 6][lane] = s;
+		__syncthreads();
+		if (t < G) {
+			u64 x = 0;
+#pragma unroll
+			for (int w = 0; w < BLOCK / 64; w++)
+				x = addmod(x, red[w][t], m.p);
+			partial[((size_t)blockIdx.x * KP + i) * G + t] = x;
+		}
+		__syncthreads();
+	}
+}
+
+/* S[brow[i] * n + col] = sum_b partial[b][i][col] mod p in the slab's word width: workgroup i serves border row i */
+template <typename W>
+__global__ void __launch_bounds__(BLOCK)
+k_border_finalize_k(const u64 *__restrict__ partial, int nblocks, int n, int G, int kp, u64 p, W *__restrict__ S,
+		    const long long *__restrict__ brow, const DevCtl *__restrict__ ctl)
+{
+	if (ctl->stop)
+		return;
+	__shared__ u64 red[BLOCK];
+	const int t = threadIdx.x, col = t & (G - 1), part = t / G, parts = BLOCK / G, i = blockIdx.x;
+	u64 s = 0;
+	for (int b = part; b < nblocks; b += parts)
+		s = addmod(s, partial[((size_t)b * kp + i) * G + col], p);
+	red[t] = s;
+	__syncthreads();
+	if (t < G && t < n) {
+		u64 x = 0;
+		for (int q = 0; q < parts; q++)
+			x = addmod(x, red[q * G + t], p);
+		S[brow[i] * n + t] = (W)x;
+	}
+}
+
+int border_kp(int k)
+{
+	int kp = 2;
+	while (kp < k)
+		kp <<= 1;
+	return kp;
+}
+
+template <typename W, int MERS, int KP>
+static void border_update_k_go(const KernelCfg &c, W *T, const W *B, const W *V, const long long *brow, int k, long long rows,
+			       const DevCtl *ctl, hipStream_t s)
+{
+	constexpr int V16 = 16 / (int)sizeof(W);
+	const int n = c.n;
+	const bool pow2 = (n & (n - 1)) == 0;
+	int sh = 0;
+	while ((1 << sh) < n)
+		sh++;
+	const bool wide = n % V16 == 0;
+	const long long total = rows * n / (wide ? V16 : 1);
+	long long blocks = (total + BLOCK - 1) / BLOCK;
+	blocks = blocks < 1 ? 1 : (blocks > (long long)c.num_cu * 8 ? (long long)c.num_cu * 8 : blocks);
+	const dim3 grid((unsigned)blocks), blk(BLOCK);
+	if (wide && pow2)
+		hipLaunchKernelGGL((k_border_update_k<W, MERS, V16, true, KP>), grid, blk, 0, s, T, B, V, brow, k, rows, n, sh, c.m, ctl);
+	else if (wide)
+		hipLaunchKernelGGL((k_border_update_k<W, MERS, V16, false, KP>), grid, blk, 0, s, T, B, V, brow, k, rows, n, sh, c.m, ctl);
+	else if (pow2)
+		hipLaunchKernelGGL((k_border_update_k<W, MERS, 1, true, KP>), grid, blk, 0, s, T, B, V, brow, k, rows, n, sh, c.m, ctl);
+	else
+		hipLaunchKernelGGL((k_border_update_k<W, MERS, 1, false, KP>), grid, blk, 0, s, T, B, V, brow, k, rows, n, sh, c.m, ctl);
+}
+
+template <typename W, int MERS, int KP>
+static void border_dot_k_go(const KernelCfg &c, const W *T, const W *B, long long rows, u64 *partial, W *S, const long long *brow,
+			    int k, const DevCtl *ctl, hipStream_t s)
+{
+	constexpr int U = KP <= 4 ? 4 : (KP == 8 ? 2 : 1);
+	const int n = c.n, G = border_group(n), gpb = BLOCK / G;
+	long long blocks = (rows + (long long)gpb * U - 1) / ((long long)gpb * U);
+	blocks = blocks < 1 ? 1 : (blocks > border_dot_max_blocks(c) ? border_dot_max_blocks(c) : blocks);
+	hipLaunchKernelGGL((k_border_dot_k<W, MERS, KP>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, T, B, rows, n, G, c.m, partial, ctl);
+	hipLaunchKernelGGL((k_border_finalize_k<W>), dim3((unsigned)k), dim3(BLOCK), 0, s, partial, (int)blocks, n, G, KP, c.m.p, S,
+			   brow, ctl);
+}
+
+/* word width, reducer and KP once, then one of the two launches */
+template <typename W, int MERS>
+static hipError_t border_k_kp(const KernelCfg &c, bool update, void *T, const void *B, void *S, const long long *brow, int k,
+			      long long rows, u64 *partial, const DevCtl *ctl, hipStream_t s)
+{
+#define BORDER_K_CASE(KP) \
+	case KP: \
+		if (update) \
+			border_update_k_go<W, MERS, KP>(c, (W *)T, (const W *)B, (const W *)S, brow, k, rows, ctl, s); \
+		else \
+			border_dot_k_go<W, MERS, KP>(c, (const W *)T, (const W *)B, rows, partial, (W *)S, brow, k, ctl, s); \
+		break
+	switch (border_kp(k)) {
+	BORDER_K_CASE(2);
+	BORDER_K_CASE(4);
+	BORDER_K_CASE(8);
+	BORDER_K_CASE(16);
+	default: return hipErrorInvalidValue;
+	}
+#undef BORDER_K_CASE
+	return hipGetLastError();
+}
+
+static hipError_t border_k(const KernelCfg &c, bool update, void *T, const void *B, void *S, const long long *brow, int k,
+			   int64_t rows, u64 *partial, const DevCtl *ctl, hipStream_t s)
+{
+	if (c.n < 1 || c.n > BLZ_BORDER_MAXN || k < 2 || k > BLZ_BORDER_MAXK)
+		return hipErrorInvalidValue;
+	if (update && rows <= 0)
+		return hipSuccess;
+	if (c.word == 4)
+		return c.mers == 31 ? border_k_kp<u32, 31>(c, update, T, B, S, brow, k, rows, partial, ctl, s)
+				    : border_k_kp<u32, 0>(c, update, T, B, S, brow, k, rows, partial, ctl, s);
+	return c.mers == 61 ? border_k_kp<u64, 61>(c, update, T, B, S, brow, k, rows, partial, ctl, s)
+			    : border_k_kp<u64, 0>(c, update, T, B, S, brow, k, rows, partial, ctl, s);
+}
+
+hipError_t launch_border_update_k(const KernelCfg &c, void *T, const void *B, const void *V, const long long *brow, int k,
+				  int64_t rows, const DevCtl *ctl, hipStream_t s)
+{
+	return border_k(c, true, T, B, const_cast<void *>(V), brow, k, rows, nullptr, ctl, s);
+}
+
+hipError_t launch_border_dot_k(const KernelCfg &c, const void *T, const void *B, int64_t rows, u64 *partial, void *S,
+			       const long long *brow, int k, const DevCtl *ctl, hipStream_t s)
+{
+	return border_k(c, false, const_cast<void *>(T), B, S, brow, k, rows, partial, ctl, s);
 }

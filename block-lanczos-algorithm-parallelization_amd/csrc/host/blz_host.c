@@ -2247,6 +2247,156 @@ int blz_check_solution(const char *matrix_path, const char *rhs_path, const char
 	return rc;
 }
 
+/* A len x k "array integer general" file, column-major, into out[r * k + i] (row-major), 1 <= k <= kmax; entries as in
+ * load_column.  out == NULL: the size line only.  *k is set as soon as the row count has matched (len < 0: any). */
+static int load_columns(const char *path, uint64_t prime, int64_t len, int kmax, int true_residue, int *k, uint64_t *out)
+{
+	*k = 0;
+	int fd = open(path, O_RDONLY);
+	struct stat st;
+	if (fd < 0 || fstat(fd, &st) != 0 || st.st_size == 0) {
+		if (fd >= 0)
+			close(fd);
+		return blz_fail(BLZ_EIO, "cannot open %s", path);
+	}
+	char *base = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
+	close(fd);
+	if (base == MAP_FAILED)
+		return blz_fail(BLZ_EIO, "mmap %s: %s", path, strerror(errno));
+	cursor c = { base, base + st.st_size };
+	char line[1100];
+	long long nk = 0, n = 0;
+	int rc = BLZ_OK;
+	if (next_line(&c, line, sizeof line) || (rc = check_banner(line, 1)) != BLZ_OK) {
+		if (rc == BLZ_OK)
+			rc = blz_fail(BLZ_EFORMAT, "Could not process Matrix Market banner.");
+		goto done;
+	}
+	do {
+		if (next_line(&c, line, sizeof line)) {
+			rc = blz_fail(BLZ_EIO, "%s: cannot read the size line", path);
+			goto done;
+		}
+	} while (line[0] == '%');
+	if (sscanf(line, "%lld %lld", &nk, &n) != 2 || nk < 0 || (len >= 0 && nk != len)) {
+		rc = blz_fail(BLZ_EIO, "%s: expected a %lld x k array, the size line says \"%.40s\"", path, (long long)len, line);
+		goto done;
+	}
+	*k = n < 0 ? 0 : (n > INT32_MAX ? INT32_MAX : (int)n);
+	if (n < 1 || n > kmax) {
+		rc = blz_fail(BLZ_EIO, "%s: %lld columns: between 1 and %d are possible, the size line says \"%.40s\"", path, n, kmax, line);
+		goto done;
+	}
+	if (!out)
+		goto done;
+	for (long long col = 0; col < n; col++)
+		for (int64_t i = 0; i < nk; i++) {
+			const char *q = c.p;
+			while (q < c.end && is_blank(*q))
+				q++;
+			if (q < c.end && (*q == '-' || *q == '+'))
+				q++;
+			const char *d0 = q;
+			while (q < c.end && *q >= '0' && *q <= '9')
+				q++;
+			/* sign and magnitude apart, as in load_column */
+			if (q == d0 || q - d0 > 19) {
+				rc = blz_fail(BLZ_EIO, "%s: parse error at entry %lld, %lld", path, (long long)i, col);
+				goto done;
+			}
+			const int neg = d0 > c.p && d0[-1] == '-';
+			uint64_t mag = 0;
+			for (const char *d = d0; d < q; d++)
+				mag = mag * 10 + (uint64_t)(*d - '0');
+			c.p = q;
+			uint64_t word;
+			if (true_residue) {
+				const uint64_t r = mag % prime;
+				word = (neg && r) ? prime - r : r;
+			} else {
+				word = !neg ? mag : (mag >= 1 && mag <= 0x80000000ull ? 0x100000000ull - mag : UINT64_MAX);
+				if (word >= prime) {
+					rc = blz_fail(BLZ_EINVAL, "%s: entry %lld, %lld out of bound", path, (long long)i, col);
+					goto done;
+				}
+			}
+			out[i * n + col] = word;
+		}
+	while (c.p < c.end && is_blank(*c.p))
+		c.p++;
+	if (c.p < c.end)
+		rc = blz_fail(BLZ_EIO, "%s: more than %lld entries", path, nk * n);
+done:
+	munmap(base, (size_t)st.st_size);
+	return rc;
+}
+
+int blz_rhs_load_block(const char *path, uint64_t prime, int64_t len, int kmax, int *k, uint64_t *b)
+{
+	if (!path || !k || prime < 2 || prime >= (1ull << 62) || kmax < 1 || (b && len < 0))
+		return blz_fail(BLZ_EINVAL, "blz_rhs_load_block: bad argument");
+	return load_columns(path, prime, len, kmax, 1, k, b);
+}
+
+int blz_check_solution_block(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+			     int *status, int64_t *bad_row)
+{
+	if (!matrix_path || !rhs_path || !x_path || !status || prime < 2 || prime >= (1ull << 62))
+		return blz_fail(BLZ_EINVAL, "blz_check_solution_block: bad argument");
+	blz_coo M;
+	int rc = blz_mm_load(matrix_path, prime, &M);
+	if (rc != BLZ_OK)
+		return rc;
+	const int64_t xlen = right ? M.ncols : M.nrows, blen = right ? M.nrows : M.ncols;
+	int k = 0, kx = 0;
+	uint64_t *x = NULL, *b = NULL;
+	unsigned __int128 *y = NULL;
+	if ((rc = load_columns(rhs_path, prime, blen, BLZ_MAX_RHS, 1, &k, NULL)) != BLZ_OK)
+		goto done;
+	x = malloc(sizeof *x * (size_t)(xlen * k + 1));
+	b = malloc(sizeof *b * (size_t)(blen * k + 1));
+	y = calloc((size_t)(blen * k + 1), sizeof *y);
+	if (!x || !b || !y) {
+		rc = blz_fail(BLZ_ENOMEM, "cannot allocate the vectors");
+		goto done;
+	}
+	if ((rc = load_columns(rhs_path, prime, blen, k, 1, &k, b)) != BLZ_OK ||
+	    (rc = load_columns(x_path, prime, xlen, k, 0, &kx, x)) != BLZ_OK)
+		goto done;
+	if (kx != k) {
+		rc = blz_fail(BLZ_EIO, "%s: %d columns for %d right-hand sides", x_path, kx, k);
+		goto done;
+	}
+	/* unreduced 128-bit sums, one reduction per word, as in blz_check_solution */
+	for (int64_t u = 0; u < M.nnz; u++) {
+		const int64_t i = right ? M.j[u] : M.i[u], j = right ? M.i[u] : M.j[u];
+		for (int t = 0; t < k; t++)
+			y[j * k + t] += (unsigned __int128)M.x[u] * x[i * k + t];
+	}
+	for (int t = 0; t < k; t++) {
+		int zero = 1;
+		for (int64_t i = 0; i < xlen && zero; i++)
+			zero = x[i * k + t] == 0;
+		status[t] = zero ? 3 : 0;
+		if (bad_row)
+			bad_row[t] = -1;
+		for (int64_t j = 0; j < blen && !zero; j++)
+			if ((uint64_t)(y[j * k + t] % prime) != b[j * k + t]) {
+				if (bad_row)
+					bad_row[t] = j;
+				status[t] = 2;
+				break;
+			}
+	}
+	rc = k;
+done:
+	free(x);
+	free(b);
+	free(y);
+	blz_coo_free(&M);
+	return rc;
+}
+
 /* rank of a kernel block: the RREF of its row space, row by row (the GPU's k_rref restated), stopping at full rank */
 
 static uint64_t host_invmod(uint64_t a, uint64_t p)

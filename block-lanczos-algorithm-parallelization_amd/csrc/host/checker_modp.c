@@ -4,7 +4,8 @@
  * lines and exit codes: "OK" + exit 0, or a KO message + exit 1.  Plain C, no GPU.
  * --independent (no reference counterpart) also asks that the kernel vectors be linearly independent mod P.
  * --rhs FILE (no reference counterpart) checks a solution instead: --kernel names the file of x, and M*x == b (--right)
- * or x*M == b (--left) is asked for the vector b of FILE.
+ * or x*M == b (--left) is asked for the vector b of FILE.  With k > 1 columns in FILE, --kernel holds the k columns of x and
+ * each is checked against its own b; an all-zero column of x stands for a system that was not solved and does not fail.
  */
 #define _GNU_SOURCE
 #include <err.h>
@@ -52,6 +53,25 @@ int main(int argc, char **argv)
 	}
 	if (rhs) {
 		printf("Reading Matrix from %s, solution from %s and right-hand side from %s\n", matrix, kernel, rhs);
+		int k = 0;
+		blz_rhs_load_block(rhs, prime, -1, BLZ_MAX_RHS, &k, NULL);	/* the size line only; one column: as ever, below */
+		if (k > 1) {
+			int status[BLZ_MAX_RHS], failed = 0;
+			int64_t bad_row[BLZ_MAX_RHS];
+			const int kk = blz_check_solution_block(matrix, rhs, kernel, prime, right, status, bad_row);
+			if (kk < 0)
+				errx(1, "%s", blz_last_error());
+			for (int i = 0; i < kk; i++) {
+				if (status[i] == 0)
+					printf("OK\n");
+				else if (status[i] == 3)
+					printf("KO: no solution (rhs %d, x is zero)\n", i);
+				else
+					printf("KO: %s != b (rhs %d, row %lld)\n", right ? "M*x" : "x*M", i, (long long)bad_row[i]);
+				failed += status[i] == 2;
+			}
+			exit(failed ? EXIT_FAILURE : EXIT_SUCCESS);
+		}
 		int64_t bad = 0;
 		const int rcs = blz_check_solution(matrix, rhs, kernel, prime, right, &bad);
 		if (rcs == 0) {

@@ -77,6 +77,8 @@ static void usage(char **argv)
 	printf("--rhs FILENAME              solve M*x = b (--right) or x*M = b (--left) for the vector b of FILENAME (MatrixMarket\n");
 	printf("                            array, one column; signed entries are reduced mod P, so -1 means P-1): the matrix\n");
 	printf("                            gets b as a dense border and --output-file receives the solution x\n");
+	printf("                            A file of k columns, 2 <= k <= min(N, 16), solves the k systems in ONE run: the\n");
+	printf("                            output has k columns, zero where a system has no solution\n");
 	printf("--device D                  first HIP device to run on [default 0]\n");
 	printf("--gpus G                    row-partition the matrix over G GPUs of this node (devices D..D+G-1), RCCL\n");
 	printf("                            all-gather of the block before each product [default 1]\n");
@@ -85,7 +87,7 @@ static void usage(char **argv)
 	printf("The --stop-after and --output-file arguments mutually exclusive\n");
 	printf("The --stop-after and --basis arguments mutually exclusive\n");
 	printf("The --rhs argument excludes --stop-after and --gpus above 1, and --basis (the solution is taken from the\n");
-	printf("kernel basis of the bordered matrix, which --rhs computes itself; it is one vector, not a block)\n");
+	printf("kernel basis of the bordered matrix, which --rhs computes itself; it is one vector per system, not a kernel block)\n");
 	exit(0);
 }
 
@@ -389,19 +391,29 @@ int main(int argc, char **argv)
 		(long)M.nnz);
 	fprintf(stderr, "  - Read in %.2fs\n", wtime() - t_load);
 	uint64_t *rhs = NULL;
+	int rhs_k = 1;
 	if (rhs_filename) {
 		/* M*x = b / x*M = b as kernel vectors of [M | b] / [M ; b]: the matrix gets one empty column / row (so the cache
 		 * key, the blocks and the checkpoints are those of the bordered operator) and b goes to the device as its border */
 		const int64_t len = right_kernel ? M.nrows : M.ncols;
 		printf("Loading right-hand side from %s\n", rhs_filename);
-		rhs = malloc(sizeof *rhs * (size_t)(len + 1));
+		/* a len x k file with k > 1 is a block of right-hand sides; anything else goes the single vector's way */
+		const int peek = blz_rhs_load_block(rhs_filename, prime, len, BLZ_MAX_RHS, &rhs_k, NULL);
+		if (rhs_k > 1 && peek != BLZ_OK)
+			errx(1, "%s", blz_last_error());
+		if (rhs_k < 1)
+			rhs_k = 1;
+		rhs = malloc(sizeof *rhs * (size_t)(len * rhs_k + 1));
 		if (!rhs)
 			errx(1, "cannot allocate the right-hand side");
-		CHECK(blz_rhs_load(rhs_filename, prime, len, rhs));
-		if (right_kernel)
-			M.ncols++;
+		if (rhs_k > 1)
+			CHECK(blz_rhs_load_block(rhs_filename, prime, len, BLZ_MAX_RHS, &rhs_k, rhs));
 		else
-			M.nrows++;
+			CHECK(blz_rhs_load(rhs_filename, prime, len, rhs));
+		if (right_kernel)
+			M.ncols += rhs_k;
+		else
+			M.nrows += rhs_k;
 	}
 
 	{
@@ -446,7 +458,9 @@ int main(int argc, char **argv)
 	}
 	team.P = P;
 	team_run(OP_MATRIX);
-	if (rhs)
+	if (rhs && rhs_k > 1)
+		CHECK(blz_set_rhs_block(ctx, rhs_k, rhs));
+	else if (rhs)
 		CHECK(blz_set_rhs(ctx, rhs));
 	free(rhs);
 	blz_prepared_free(P);
@@ -568,7 +582,29 @@ int main(int argc, char **argv)
 		else
 			printf("  - KO: no kernel vector\n");
 	}
-	if (rhs_filename) {		/* no reference counterpart: blz_solution, include/blz.h */
+	if (rhs_filename && rhs_k > 1) {	/* no reference counterpart: blz_solution_block, include/blz.h */
+		int status[BLZ_MAX_RHS] = { 0 }, solved = 0;
+		CHECK(blz_solution_block(ctx, v, status));
+		printf("Solve:\n");
+		for (int i = 0; i < rhs_k; i++) {
+			if (status[i] == 0)
+				printf(right_kernel ? "  - rhs %d: OK: M*x == b\n" : "  - rhs %d: OK: x*M == b\n", i);
+			else if (status[i] == 1)
+				printf("  - rhs %d: KO: no solution found\n", i);
+			else
+				errx(1, "the solutions failed their verification on the GPU");
+			solved += status[i] == 0;
+		}
+		printf("  - %d of %d systems solved\n", solved, rhs_k);
+		if (solved == 0) {
+			printf("Not saving result (no solution)\n");
+		} else if (kernel_filename) {
+			printf("Saving result in %s\n", kernel_filename);
+			CHECK(blz_save_block(kernel_filename, nrows - rhs_k, rhs_k, v));
+		} else {
+			printf("Not saving result (no --output given)\n");
+		}
+	} else if (rhs_filename) {		/* no reference counterpart: blz_solution, include/blz.h */
 		int status = 0;
 		CHECK(blz_solution(ctx, v, &status));
 		printf("Solve:\n");

@@ -373,6 +373,30 @@ def check_solution(matrix_path, rhs_path, x_path, prime, right=False):
     return rc, (int(row.value) if rc == 2 else None)
 
 
+MAX_RHS = 16
+
+
+def rhs_load_block(path, prime, length, kmax=MAX_RHS):
+    """blz_rhs_load_block(): the length x k words of a file of k right-hand sides, row-major (b[r, i] = entry r of
+    right-hand side i), as an array of shape (length, k)."""
+    b = np.zeros(max(length, 1) * kmax, dtype=np.uint64)
+    k = C.c_int(0)
+    check(lib().blz_rhs_load_block(path.encode(), C.c_uint64(prime), C.c_int64(length), C.c_int(kmax), C.byref(k), ptr(b)))
+    return b[:length * k.value].reshape(length, k.value)
+
+
+def check_solution_block(matrix_path, rhs_path, x_path, prime, right=False):
+    """blz_check_solution_block(): one (status, row) per right-hand side -- (0, None) equal, (2, first differing row),
+    (3, None) the x column is all zero; raises on file / format errors."""
+    status = (C.c_int * MAX_RHS)()
+    rows = (C.c_int64 * MAX_RHS)()
+    k = lib().blz_check_solution_block(matrix_path.encode(), rhs_path.encode(), x_path.encode(), C.c_uint64(prime),
+                                       C.c_int(int(right)), status, rows)
+    if k < 0:
+        check(k)
+    return [(int(status[i]), int(rows[i]) if status[i] == 2 else None) for i in range(k)]
+
+
 def checkpoint_save(path, prime, n, right, nrows, iterations, v, p):
     check(lib().blz_checkpoint_save(path.encode(), C.c_uint64(prime), C.c_int(n), C.c_int(int(right)),
                                     C.c_int64(nrows), C.c_int64(iterations), ptr(u64(v)), ptr(u64(p))))
@@ -464,6 +488,35 @@ class Context:
         status = C.c_int(-1)
         check(lib().blz_solution(self.h, ptr(x), C.byref(status)))
         return int(status.value), (x[:self.rows(V) - 1] if status.value == 0 else None)
+
+    def set_matrix_rhs_block(self, M, b, right=False):
+        """blz_set_matrix_rhs_block(): M X = B (right; B is M.nrows x k) or X M = B (B is M.ncols x k), k right-hand sides
+        in one bordered operator; rows(V) then counts the k border rows."""
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        assert b.ndim == 2 and b.shape[0] == (M.nrows if right else M.ncols), (b.shape, M.nrows, M.ncols, right)
+        check(lib().blz_set_matrix_rhs_block(self.h, C.byref(M.c), C.c_int(int(right)), C.c_int(b.shape[1]), ptr(b.reshape(-1))))
+        self.right = bool(right)
+
+    def set_rhs_block(self, b):
+        """blz_set_rhs_block(): the k borders for a matrix already set with the k extra empty last rows / columns."""
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        assert b.ndim == 2 and b.shape[0] == self.rows(TMP), (b.shape, self.rows(TMP))
+        check(lib().blz_set_rhs_block(self.h, C.c_int(b.shape[1]), ptr(b.reshape(-1))))
+
+    @property
+    def rhs_count(self):
+        return int(lib().blz_rhs_count(self.h))
+
+    def solution_block(self):
+        """blz_solution_block(): (statuses, x) -- statuses[i] is 0 (solved and verified), 1 (not solved, column i of x
+        zero) or 2 (verification failed: x is None); x has shape (rows(V) - k, k)."""
+        k = self.rhs_count
+        length = self.rows(V) - k
+        x = np.zeros(max(length * k, 1), dtype=np.uint64)
+        status = (C.c_int * MAX_RHS)(*([-1] * MAX_RHS))
+        check(lib().blz_solution_block(self.h, ptr(x), status))
+        st = [int(status[i]) for i in range(k)]
+        return st, (None if 2 in st else x[:length * k].reshape(length, k))
 
     def rows(self, block):
         return int(lib().blz_rows(self.h, C.c_int(block)))

@@ -38,6 +38,7 @@ extern "C" {
 #define BLZ_ECOMM      -7	/* RCCL failure */
 
 #define BLZ_MAX_N      64	/* block width limit (one wavefront holds a block row) */
+#define BLZ_MAX_RHS    16	/* right-hand sides of one bordered solve (blz_set_matrix_rhs_block) */
 
 /* block selectors: the four N x n blocks of block_lanczos(), sequential/lanczos_modp.c:602-605 */
 enum { BLZ_V = 0, BLZ_TMP = 1, BLZ_AV = 2, BLZ_P = 3 };
@@ -222,12 +223,26 @@ int blz_check_independent(const char *kernel_path, uint64_t prime, int *rank, in
  * other than len x 1, an entry that does not parse or has 20 digits or more, and trailing entries are BLZ_EIO. */
 int blz_rhs_load(const char *path, uint64_t prime, int64_t len, uint64_t *b);
 
+/* Several right-hand sides for blz_set_matrix_rhs_block: an "array integer general" file of len x k entries, column-major
+ * as blz_save_block writes a block, 1 <= k <= kmax, entries as in blz_rhs_load (signed, true residues).  Fills
+ * b[r * k + i] = entry r of right-hand side i (row-major; room for len * kmax words) and *k.  With b == NULL only the
+ * size line is read: *k receives its column count whenever the row count is len (len < 0: any), also when that count
+ * exceeds kmax and the call fails.  Errors as blz_rhs_load; a column count outside 1..kmax is BLZ_EIO. */
+int blz_rhs_load_block(const char *path, uint64_t prime, int64_t len, int kmax, int *k, uint64_t *b);
+
 /* Host check of a solution file against a right-hand side file: x (len x 1, as blz_save_block writes it, entries below
  * prime) and b (as blz_rhs_load reads it) with M x == b (right != 0: x has M's column count, b its row count) or
  * x M == b (right == 0) mod prime, by unreduced 128-bit sums like blz_check_kernel.  Returns 0 = equal, 2 = not equal
  * (*bad_row, may be NULL = the first word of the product that differs from b), or a negative BLZ_E* code. */
 int blz_check_solution(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
 		       int64_t *bad_row);
+
+/* The same for k right-hand sides: b has k <= BLZ_MAX_RHS columns (blz_rhs_load_block) and x the same k columns (as
+ * blz_save_block writes them).  status[i] (room for BLZ_MAX_RHS): 0 = column i is equal, 2 = not equal (bad_row[i], when
+ * bad_row is not NULL, = the first word that differs), 3 = the x column is all zero (an unsolved system, not compared).
+ * Returns k, or a negative BLZ_E* code. */
+int blz_check_solution_block(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+			     int *status, int64_t *bad_row);
 
 /* Checkpoints (openMP/lanczos_modp.c:571-676, :933-940, :1013-1022).  blz_checkpoint_save writes
  * one binary file atomically (tmp + rename): v, p, iteration count, prime, n, shape.
@@ -282,7 +297,18 @@ int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank);
  *                       (right == 0) / column (right != 0), e.g. through blz_prepare_for / blz_prepared_load /
  *                       blz_set_matrix_prepared (the CLI's --cache); b has blz_rows(ctx, BLZ_TMP) words
  *   blz_has_rhs         1 when the context carries a border
- * Setting a matrix again drops the border. */
+ * Setting a matrix again drops the border.
+ *
+ * Up to BLZ_MAX_RHS right-hand sides share ONE run: M X = B (right) / X M = B as kernel vectors of [M | B] / [M ; B], the
+ * dimension raised by k, 1 <= k <= min(n, BLZ_MAX_RHS).  b = rows x k words, row-major (word [r * k + i] = entry r of
+ * right-hand side i), all below p.  The two border kernels run once per product for all k columns.
+ *   blz_set_matrix_rhs_block  the one-call form
+ *   blz_set_rhs_block         for a matrix the caller has set with the k extra empty last rows / columns
+ *   blz_rhs_count             0 without a border, 1 after blz_set_rhs / blz_set_matrix_rhs, k after the block forms
+ * k == 1 is the single border above in every respect.  Same refusals (BLZ_EINVAL) as for one right-hand side. */
+int blz_set_matrix_rhs_block(blz_ctx *ctx, const blz_coo *M, int right, int k, const uint64_t *b);
+int blz_set_rhs_block(blz_ctx *ctx, int k, const uint64_t *b);
+int blz_rhs_count(const blz_ctx *ctx);
 int blz_set_matrix_rhs(blz_ctx *ctx, const blz_coo *M, int right, const uint64_t *b);
 int blz_set_rhs(blz_ctx *ctx, const uint64_t *b);
 int blz_has_rhs(const blz_ctx *ctx);
@@ -428,6 +454,16 @@ int blz_kernel_basis(blz_ctx *ctx, int *k, uint64_t *z);
  * numbering, the border row left out).  *status: 0 = solved and verified; 1 = no kernel vector with a non-zero border
  * word (an inconsistent system, or an unlucky start), x untouched; 2 = the verification failed (a bug), x untouched. */
 int blz_solution(blz_ctx *ctx, uint64_t *x, int *status);
+
+/* The solutions of a context with k = blz_rhs_count(ctx) right-hand sides (k == 1 included), in the same state.  Runs
+ * blz_kernel_basis (kb vectors), solves W C = -I_k on the host for the k x kb border part W of the basis, and computes
+ * V <- V C on the device: column i of V then is (y_i, -e_i) with M y_i = b_i, and zero where system i is not solvable
+ * from this basis (e_i not in W's column space: an inconsistent system, or an unlucky start).  The side-1 product of V
+ * with the border applied is recomputed into TMP and tested for zero on the GPU.  status[i]: 0 = solved and verified,
+ * 1 = not solved (column i of x zero), 2 = the verification failed (a bug: every status is 2 and x is untouched).
+ * x = (blz_rows(ctx, BLZ_V) - k) x k words, row-major, original numbering, the border rows left out.
+ * blz_solution itself refuses a context with k > 1. */
+int blz_solution_block(blz_ctx *ctx, uint64_t *x, int *status);
 
 /* Asynchronous snapshot of (v, p, iteration count) for checkpoints (openMP/lanczos_modp.c:1013-1022 stops its loop
  * for them).  blz_snapshot_begin, called between two blz_iterate calls, enqueues the device-to-host copies of this

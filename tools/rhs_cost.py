@@ -1,6 +1,6 @@
 """What the dense border of a right-hand-side solve costs per iteration.
 
-    python tools/rhs_cost.py [--workload gl7d19] [--steps 20] [--warmup 3] [--repeats 5]
+    python tools/rhs_cost.py [--workload gl7d19] [--steps 20] [--warmup 3] [--repeats 5] [--ks 4,8]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/rhs_cost.py --trace-only
 
 Three contexts on bench.py's synthetic matrix of the workload, in one process, timed in alternation (one region of
@@ -10,6 +10,10 @@ with a seeded right-hand side.  bordered - nofuse isolates the two border kernel
 fusion.  Prints one JSON line with the times and the bytes the border moves (the model the times are held against).
 --trace-only runs the bordered context alone, for a kernel trace: k_border_update / k_border_dot / k_border_finalize
 appear there by name.
+--ks 4,8 adds one context per k with k seeded right-hand sides (blz_set_matrix_rhs_block: k_border_update_k /
+k_border_dot_k / k_border_finalize_k) to the alternation, as "bordered_k4", "bordered_k8"; border_ms then holds, per
+bordered context, its time minus the nofuse context's, i.e. what its border kernels cost, and the k = 1 figure times k
+next to it -- what a loop over today's kernels would cost.
 """
 import argparse
 import json
@@ -40,11 +44,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--trace-only", action="store_true")
+    ap.add_argument("--ks", default="", help="comma-separated counts of right-hand sides to time as well, e.g. 4,8")
     args = ap.parse_args()
     w = bench.WORKLOADS[args.workload]
     p, n, right = w["prime"], w["n"], w["right"]
     M = blz.Matrix.synth(w["rows"], w["cols"], w["nnz"], w["seed"], p, pattern=w["pattern"])
     b = np.random.default_rng(0x52485300).integers(0, p, size=M.nrows if right else M.ncols, dtype=np.uint64)
+
+    ks = [int(k) for k in args.ks.split(",") if k]
+    assert all(2 <= k <= min(n, blz.MAX_RHS) for k in ks), ks
+    B = np.random.default_rng(0x52485301).integers(0, p, size=(b.size, max(ks, default=1)), dtype=np.uint64)
 
     def make(kind):
         if kind == "nofuse":
@@ -55,12 +64,14 @@ def main():
             os.environ.pop("BLZ_NO_FUSE", None)
         if kind == "bordered":
             ctx.set_matrix_rhs(M, b, right)
+        elif kind.startswith("bordered_k"):
+            ctx.set_matrix_rhs_block(M, B[:, :int(kind[len("bordered_k"):])], right)
         else:
             ctx.set_matrix(M, right)
         ctx.init_v()
         return ctx
 
-    kinds = ("bordered",) if args.trace_only else ("plain", "nofuse", "bordered")
+    kinds = ("bordered",) if args.trace_only else ("plain", "nofuse", "bordered") + tuple(f"bordered_k{k}" for k in ks)
     ctxs = {k: make(k) for k in kinds}
     for ctx in ctxs.values():
         done, stopped, _ = ctx.iterate(args.warmup)
@@ -83,8 +94,15 @@ def main():
                ms_per_step_all={k: [round(t, 4) for t in v] for k, v in times.items()},
                border_bytes=border_bytes(ctx.rows(blz.V), ctx.rows(blz.TMP), width, word))
     if not args.trace_only:
+        ms = out["ms_per_step"]
+        one = ms["bordered"] - ms["nofuse"]
+        out["border_ms"] = {"bordered": dict(k=1, border=one, looped=one)}
+        for k in ks:
+            words = ctxs[f"bordered_k{k}"].rows(blz.TMP) * blz.lib().blz_rhs_count(ctxs[f"bordered_k{k}"].h)
+            out["border_ms"][f"bordered_k{k}"] = dict(k=k, border=ms[f"bordered_k{k}"] - ms["nofuse"], looped=k * one,
+                                                      b_words=int(words))
         kern = {}
-        for k in ("nofuse", "bordered"):            # the same products and block_dot alone (blz_time_kernel), for the split
+        for k in ("nofuse", "bordered") + tuple(f"bordered_k{k}" for k in ks):            # the same products and block_dot alone (blz_time_kernel), for the split
             kern[k] = {name: ctxs[k].time_kernel(which, 20) for which, name in ((0, "spmv1"), (1, "spmv2"), (2, "block_dot"))}
         out["kernel_ms"] = kern
     print(json.dumps(out))
