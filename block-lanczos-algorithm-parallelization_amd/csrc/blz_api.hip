@@ -239,6 +239,14 @@ struct blz_ctx {
 	size_t border_partial_words = 0;	/* room in border_partial when the block form sized it */
 	std::vector<int64_t> border_rows;
 	long long *border_rows_dev = nullptr;
+	/* the border on several ranks (blz_set_rhs_ranks): rhs = this rank's own rows of B; border / border_rows[_dev] = the
+	 * border rows' positions in the GATHERED operand of side 0 (the slab's own rows on one rank); border_own[_dev][i] = the
+	 * local row of border row i where this rank owns it, -1 elsewhere; border_send = the rank's k x n share of the border dot,
+	 * border_recv = where its all-reduce lands (k_border_place reads it while the stop flag is down: allreduce_dots' rule) */
+	bool rhs_ranks = false;
+	std::vector<int64_t> border_own;
+	long long *border_own_dev = nullptr;
+	u64 *border_send = nullptr, *border_recv = nullptr;	/* BLZ_MAX_RHS x cfg.n words each */
 };
 
 /* HIP-event span around one enqueue on the context's stream (only while profiling is on). */
@@ -495,6 +503,9 @@ extern "C" void blz_destroy(blz_ctx *c)
 	if (c->rhs) hipFree(c->rhs);
 	if (c->border_partial) hipFree(c->border_partial);
 	if (c->border_rows_dev) hipFree(c->border_rows_dev);
+	if (c->border_own_dev) hipFree(c->border_own_dev);
+	if (c->border_send) hipFree(c->border_send);
+	if (c->border_recv) hipFree(c->border_recv);
 	if (c->dot_send) hipFree(c->dot_send);
 	if (c->dot_recv) hipFree(c->dot_recv);
 	if (c->rs_recv) hipFree(c->rs_recv);
@@ -694,7 +705,9 @@ extern "C" uint64_t blz_prepare_key(const blz_ctx *c, uint64_t content_hash, int
 	return h ? h : 1;
 }
 
-extern "C" int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank)
+/* allow_short_side = false: plan no short-side product (a bordered context: the border rows of the operand are not
+ * gathered in that form) */
+static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool allow_short_side)
 {
 	if (!c || !P)
 		return blz_fail(BLZ_EINVAL, "blz_set_matrix_prepared: NULL argument");
@@ -724,6 +737,8 @@ extern "C" int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int ra
 	c->border = -1;
 	c->rhs_k = c->rhs_kp = 0;
 	c->border_rows.clear();
+	c->rhs_ranks = false;
+	c->border_own.clear();
 	/* side 0 = rows of v: rows of M for a left kernel, columns of M for a right kernel
 	 * (sequential/lanczos_modp.c:592-593). */
 	c->glob_rows[0] = right ? P->ncols : P->nrows;
@@ -769,6 +784,8 @@ extern "C" int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int ra
 		bool on = (nranks > 1 || c->force_comm) && c->cfg.word == 8 && c->glob_rows[cs_t] >= 8 * c->glob_rows[rs_t];
 		if (const char *e = getenv("BLZ_SHORT_SIDE"))
 			on = e[0] == '1' && c->cfg.word == 8 && (nranks > 1 || c->force_comm);
+		if (!allow_short_side)
+			on = false;
 		c->short_side[t] = on;
 		if (on) {
 			part_need = std::max(part_need, (size_t)nranks * (size_t)std::max<int64_t>(c->stride[rs_t], 1) * c->cfg.n * 8);
@@ -886,6 +903,11 @@ extern "C" int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int ra
 	}
 	c->have_matrix = true;
 	return BLZ_OK;
+}
+
+extern "C" int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank)
+{
+	return set_matrix_prepared(c, P, rank, true);
 }
 
 /* The one-call form: prepare for this context, keep this rank's share, drop the rest.  Several contexts of one process
@@ -1092,6 +1114,175 @@ extern "C" int blz_set_matrix_rhs_block(blz_ctx *c, const blz_coo *M, int right,
 	if ((rc = blz_set_matrix(c, &Mb, right, 0, 1)) != BLZ_OK)
 		return rc;
 	return blz_set_rhs_block(c, k, b);
+}
+
+/* ---- the border on several ranks ---- */
+
+static inline bool exchanging(const blz_ctx *c);
+static int coll_allreduce_i32(blz_ctx *c, const void *send, void *recv, size_t words, hipStream_t st);
+
+extern "C" int blz_set_rhs_ranks(blz_ctx *c, int k, const uint64_t *b)
+{
+	if (!c || !c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "no matrix loaded (blz_set_matrix)");
+	HIPCHK(hipSetDevice(c->device));
+	const bool plain = c->nranks == 1 && !c->comm && !c->loop && !c->force_comm;
+	if (!b && plain)
+		return blz_fail(BLZ_EINVAL, "blz_set_rhs_ranks: b is NULL");
+	int rc = rhs_block_refuse_k(c, "blz_set_rhs_ranks", k);
+	if (rc != BLZ_OK)
+		return rc;
+	if (plain)
+		return blz_set_rhs_block(c, k, b);	/* a plain single rank: the one-rank border in every respect */
+	/* the refusals below are the same on every rank (same k, same matrix, same mode): nobody is left alone in the collective
+	 * further down.  What one rank alone may get wrong (a NULL b, a border row that is not empty) goes through it. */
+	if (c->external_exchange)
+		return blz_fail(BLZ_EINVAL, "blz_set_rhs_ranks: the context is in external-exchange mode (the all-reduce of the border "
+				"words is the library's own)");
+	if (c->short_side[0] || c->short_side[1])
+		return blz_fail(BLZ_EINVAL, "blz_set_rhs_ranks: a product of this matrix runs in its short-side form, which a bordered "
+				"context cannot use (the border rows of the operand are not gathered there): set the matrix with "
+				"BLZ_SHORT_SIDE=0, or through blz_set_matrix_rhs_ranks");
+	if (c->nranks > 1 && !c->comm && !c->loop)
+		return blz_fail(BLZ_ECOMM, "nranks > 1 but blz_comm_init was not called");
+	if (c->glob_rows[0] < k || c->csr[0].empty() || c->csr[0].size() != c->csr[1].size())
+		return blz_fail(BLZ_EINVAL, "blz_set_rhs_ranks: unexpected matrix shape");
+	HIPCHK(hipStreamSynchronize(c->stream));
+	HIPCHK(hipStreamSynchronize(c->xstream));
+	const int K = (int)c->csr[0].size(), np = c->cfg.n;
+	const int kp = k == 1 ? 1 : border_kp(k);
+	const int64_t first = c->glob_rows[0] - k, len = c->glob_rows[1];
+	if (!c->border_send) {
+		HIPCHK(hipMalloc(&c->border_send, (size_t)BLZ_MAX_RHS * np * sizeof(u64)));
+		HIPCHK(hipMalloc(&c->border_recv, (size_t)BLZ_MAX_RHS * np * sizeof(u64)));
+		HIPCHK(hipMemset(c->border_send, 0, (size_t)BLZ_MAX_RHS * np * sizeof(u64)));
+		HIPCHK(hipMemset(c->border_recv, 0, (size_t)BLZ_MAX_RHS * np * sizeof(u64)));
+	}
+	/* where the k border rows live, and are the ones this rank owns empty?  The product whose rows live on side 0 says so,
+	 * piece by piece.  A refusal is recorded, not returned: it goes out behind the collective, on every rank. */
+	std::vector<int64_t> gpos((size_t)k), own((size_t)k);
+	int refuse = 0;
+	char why[512] = "";
+	if (!b) {
+		refuse = 1;
+		snprintf(why, sizeof why, "blz_set_rhs_ranks: b is NULL");
+	}
+	const int t0 = c->row_side[0] == 0 ? 0 : 1;
+	for (int i = 0; i < k; i++) {
+		const int64_t row = c->perm[0].empty() ? first + i : c->perm[0][(size_t)(first + i)];
+		int owner = 0;
+		int64_t local = 0;
+		const int64_t pos = blz_gathered_position(c->bounds[0].data(), c->nranks, c->stride[0], K, row, &owner, &local);
+		if (pos < 0)
+			return (int)pos;	/* (bounds and strides are every rank's: the same verdict everywhere) */
+		gpos[(size_t)i] = pos;
+		own[(size_t)i] = owner == c->rank ? local : -1;
+		for (int q = 0; q < K && owner == c->rank && !refuse; q++) {
+			const DevCsr &A = c->csr[t0][(size_t)q];
+			u32 rp[2] = { 0, 1 };
+			if (A.rows != c->count[0] || local >= A.rows ||
+			    hipMemcpy(rp, A.row_ptr + local, sizeof rp, hipMemcpyDeviceToHost) != hipSuccess) {
+				refuse = 1;
+				snprintf(why, sizeof why, "blz_set_rhs_ranks: unexpected slab shape");
+			} else if (rp[0] != rp[1]) {
+				refuse = 1;
+				snprintf(why, sizeof why, "blz_set_rhs_ranks: the last %d %s of the matrix must be empty (they stand for the "
+					 "right-hand sides)", k, c->right ? "columns" : "rows");
+			}
+		}
+	}
+	std::vector<uint64_t> bs((size_t)std::max<int64_t>(c->count[1], 1) * kp, 0);
+	if (!refuse && blz_rhs_cut(b, len, k, kp, c->prime, c->perm[1].empty() ? nullptr : c->perm[1].data(), c->first[1], c->count[1],
+				   bs.data()) != BLZ_OK) {
+		refuse = 1;
+		snprintf(why, sizeof why, "blz_set_rhs_ranks: %s", blz_last_error());
+	}
+	if (exchanging(c)) {	/* all ranks pass or all fail */
+		int sum = 0;
+		HIPCHK(hipMemcpy(c->border_send, &refuse, sizeof refuse, hipMemcpyHostToDevice));
+		if ((rc = coll_allreduce_i32(c, c->border_send, c->border_recv, 1, c->stream)) != BLZ_OK)
+			return rc;
+		HIPCHK(hipStreamSynchronize(c->stream));
+		HIPCHK(hipMemcpy(&sum, c->border_recv, sizeof sum, hipMemcpyDeviceToHost));
+		if (sum && !refuse)
+			return blz_fail(BLZ_EINVAL, "blz_set_rhs_ranks: refused on another rank (%d of %d): the border rows must be empty and "
+					"every word of b below p", sum, c->nranks);
+	}
+	if (refuse)
+		return blz_fail(BLZ_EINVAL, "%s", why);
+	if (c->rhs)
+		hipFree(c->rhs);
+	c->rhs = nullptr;
+	HIPCHK(hipMalloc(&c->rhs, bs.size() * c->cfg.word));
+	if ((rc = put_words(c, c->rhs, bs.data(), (int64_t)bs.size())) != BLZ_OK)
+		return rc;
+	const size_t need = (size_t)border_dot_max_blocks(c->cfg) * kp * BLZ_BORDER_MAXN;
+	if (!c->border_partial || (c->border_partial_words < need && kp > 1)) {
+		if (c->border_partial)
+			hipFree(c->border_partial);
+		c->border_partial = nullptr;
+		c->border_partial_words = 0;
+		HIPCHK(hipMalloc(&c->border_partial, need * sizeof(u64)));
+		c->border_partial_words = kp > 1 ? need : 0;	/* (as the one-rank entry points account for it) */
+	}
+	if (!c->border_rows_dev)
+		HIPCHK(hipMalloc(&c->border_rows_dev, BLZ_MAX_RHS * sizeof(long long)));
+	if (!c->border_own_dev)
+		HIPCHK(hipMalloc(&c->border_own_dev, BLZ_MAX_RHS * sizeof(long long)));
+	{
+		long long dev_rows[BLZ_MAX_RHS] = { 0 }, dev_own[BLZ_MAX_RHS];
+		for (int i = 0; i < BLZ_MAX_RHS; i++)
+			dev_own[i] = -1;
+		for (int i = 0; i < k; i++) {
+			dev_rows[i] = gpos[(size_t)i];
+			dev_own[i] = own[(size_t)i];
+		}
+		HIPCHK(hipMemcpy(c->border_rows_dev, dev_rows, sizeof dev_rows, hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(c->border_own_dev, dev_own, sizeof dev_own, hipMemcpyHostToDevice));
+	}
+	c->border_own = own;
+	c->border = gpos[(size_t)k - 1];
+	c->border_rows.clear();
+	if (k > 1)
+		c->border_rows = gpos;
+	c->rhs_k = k;
+	c->rhs_kp = k > 1 ? kp : 0;
+	c->rhs_ranks = true;
+	c->fuse_local_off = true;	/* as in blz_set_rhs */
+	if (c->iter_graph) {
+		hipGraphExecDestroy(c->iter_graph);
+		c->iter_graph = nullptr;
+	}
+	return BLZ_OK;
+}
+
+extern "C" int blz_set_matrix_rhs_ranks(blz_ctx *c, const blz_coo *M, int right, int k, const uint64_t *b, int rank, int nranks)
+{
+	if (!c || !M || !b)
+		return blz_fail(BLZ_EINVAL, "blz_set_matrix_rhs_ranks: NULL argument");
+	if (nranks < 1 || rank < 0 || rank >= nranks)
+		return blz_fail(BLZ_EINVAL, "blz_set_matrix_rhs_ranks: rank %d of %d", rank, nranks);
+	int rc = rhs_block_refuse_k(c, "blz_set_matrix_rhs_ranks", k);
+	if (rc != BLZ_OK)
+		return rc;
+	if (nranks == 1 && !c->comm && !c->loop && !c->force_comm)
+		return blz_set_matrix_rhs_block(c, M, right, k, b);
+	if (c->external_exchange)
+		return blz_fail(BLZ_EINVAL, "blz_set_matrix_rhs_ranks: the context is in external-exchange mode (the all-reduce of the "
+				"border words is the library's own)");
+	blz_coo Mb = *M;	/* the same triplets under a dimension raised by k, as in blz_set_matrix_rhs_block */
+	if (right)
+		Mb.ncols += k;
+	else
+		Mb.nrows += k;
+	blz_prepared *P = nullptr;
+	if ((rc = blz_prepare_for(c, &Mb, right, nranks, &P)) != BLZ_OK)
+		return rc;
+	rc = set_matrix_prepared(c, P, rank, false);	/* no short-side product, whatever BLZ_SHORT_SIDE says */
+	blz_prepared_free(P);
+	if (rc != BLZ_OK)
+		return rc;
+	return blz_set_rhs_ranks(c, k, b);
 }
 
 extern "C" int64_t blz_rows(const blz_ctx *c, int block)
@@ -1596,9 +1787,44 @@ static inline const u64 *dot_sums(blz_ctx *c) { return exchanging(c) ? c->dot_re
  *  dst[border, :] = sum_r b[r] * src[r, :]  (the SpMV has written zeros there).  Enqueued on the context's stream behind
  * launch_spmv, which has joined its outlier launches' side stream by the time it returns.
  */
-static int enqueue_border(blz_ctx *c, int transpose, int src, int dst, const DevCtl *ctl)
+static int enqueue_border(blz_ctx *c, int transpose, int src, int dst, const DevCtl *ctl, int cls)
 {
 	const size_t row_bytes = (size_t)c->cfg.n * c->cfg.word;
+	if (c->rhs_ranks && exchanging(c)) {
+		/* Several ranks.  T and B are this rank's own rows.  The product that writes side 1 reads the k border rows of its
+		 * operand where the exchange has just put them (all K pieces have landed: the products above waited for them), at
+		 * their positions in the gathered layout -- nothing more is exchanged.  The one that writes side 0 takes the dot over
+		 * its own rows (zeros from a rank without any), all-reduces the k x n words and the owners store their rows.  The
+		 * collective is enqueued whatever the stop flag says, out of a send buffer into a landing buffer of its own (the
+		 * reasoning of allreduce_dots): past the stop the two kernels around it are no-ops and the slab keeps its rows. */
+		const int k = c->rhs_k > 1 ? c->rhs_k : 1;
+		if (c->row_side[transpose] == 1) {
+			Span sp(c, cls);
+			const char *X = (const char *)operand_ptr(c, src);
+			if (k > 1)
+				HIPCHK(launch_border_update_k(c->cfg, slab_ptr(c, dst), c->rhs, X, c->border_rows_dev, k, c->count[1], ctl,
+							      c->stream));
+			else
+				HIPCHK(launch_border_update(c->cfg, slab_ptr(c, dst), c->rhs, X + (size_t)c->border * row_bytes, c->count[1], ctl,
+							    c->stream));
+			return BLZ_OK;
+		}
+		{
+			Span sp(c, cls);
+			HIPCHK(launch_border_dot_send(c->cfg, slab_ptr(c, src), c->rhs, c->count[1], c->border_partial, c->border_send, k, ctl,
+						      c->stream));
+		}
+		{
+			Span sp(c, PK_AR);
+			int rc_ = coll_allreduce_u64(c, c->border_send, c->border_recv, (size_t)k * c->cfg.n, c->stream);
+			if (rc_ != BLZ_OK)
+				return rc_;
+		}
+		Span sp(c, cls);
+		HIPCHK(launch_border_place(c->cfg, c->border_recv, slab_ptr(c, dst), c->border_own_dev, k, ctl, c->stream));
+		return BLZ_OK;
+	}
+	Span sp(c, cls);
 	if (c->rhs_k > 1) {	/* several right-hand sides: the same two passes, fused over the k columns */
 		if (c->row_side[transpose] == 1)
 			HIPCHK(launch_border_update_k(c->cfg, slab_ptr(c, dst), c->rhs, slab_ptr(c, src), c->border_rows_dev, c->rhs_k,
@@ -1690,10 +1916,8 @@ static int enqueue_product(blz_ctx *c, int transpose, int src, int dst, bool wit
 		else
 			HIPCHK(launch_spmv(c->cfg, A, X, slab_ptr(c, dst), k > 0, ctl, c->stream));
 	}
-	if (c->rhs) {
-		Span sp(c, cls);
-		return enqueue_border(c, transpose, src, dst, ctl);
-	}
+	if (c->rhs)
+		return enqueue_border(c, transpose, src, dst, ctl, cls);
 	return BLZ_OK;
 }
 
@@ -2091,6 +2315,55 @@ static uint64_t host_inverse(uint64_t a, uint64_t p)
 	return (uint64_t)(t < 0 ? t + p : t);
 }
 
+/* the k border rows of V on the host, cfg.n words each.  Several ranks: every rank sends the rows it owns (zeros for the
+ * others) through the border's all-reduce, so every rank reads the same words; collective. */
+static int border_rows_to_host(blz_ctx *c, int k, std::vector<uint64_t> &W)
+{
+	const int np = c->cfg.n;
+	W.assign((size_t)k * np, 0);
+	if (c->rhs_ranks && exchanging(c)) {
+		HIPCHK(launch_border_rows_send(c->cfg, slab_ptr(c, BLZ_V), c->border_own_dev, k, c->border_send, c->stream));
+		int rc = coll_allreduce_u64(c, c->border_send, c->border_recv, (size_t)k * np, c->stream);
+		if (rc != BLZ_OK)
+			return rc;
+		HIPCHK(hipStreamSynchronize(c->stream));
+		HIPCHK(hipMemcpy(W.data(), c->border_recv, W.size() * sizeof(u64), hipMemcpyDeviceToHost));
+		return BLZ_OK;
+	}
+	for (int i = 0; i < k; i++) {
+		const int64_t row = c->rhs_k > 1 ? c->border_rows[(size_t)i] : c->border;
+		int rc = get_words(c, W.data() + (size_t)i * np, slab_ptr(c, BLZ_V) + (size_t)row * np * c->cfg.word, np);
+		if (rc != BLZ_OK)
+			return rc;
+	}
+	return BLZ_OK;
+}
+
+/* does this rank hold row `orig` (original numbering) of side sd? */
+static inline bool owns_row(const blz_ctx *c, int sd, int64_t orig)
+{
+	const int64_t r = c->perm[sd].empty() ? orig : c->perm[sd][(size_t)orig];
+	return r >= c->first[sd] && r < c->first[sd] + c->count[sd];
+}
+
+/* the zero test of the verification product, summed over the ranks the way blz_final_check does it */
+static int residual_flag(blz_ctx *c, int *nonzero)
+{
+	HIPCHK(hipMemsetAsync(&c->ctl->flag_t_nonzero, 0, sizeof(int), c->stream));
+	HIPCHK(launch_any_nonzero(c->cfg, slab_ptr(c, BLZ_TMP), c->count[1] * c->cfg.n, &c->ctl->flag_t_nonzero, c->stream));
+	if (c->nranks > 1 && !c->external_exchange) {
+		int rc_ = coll_allreduce_i32(c, &c->ctl->flag_t_nonzero, c->dot_recv, 1, c->stream);
+		if (rc_ != BLZ_OK)
+			return rc_;
+		HIPCHK(hipMemcpyAsync(&c->ctl->flag_t_nonzero, c->dot_recv, sizeof(int), hipMemcpyDeviceToDevice, c->stream));
+	}
+	int rc = fetch_ctl(c);
+	if (rc != BLZ_OK)
+		return rc;
+	*nonzero = c->host_ctl.flag_t_nonzero != 0;
+	return BLZ_OK;
+}
+
 extern "C" int blz_solution(blz_ctx *c, uint64_t *x, int *status)
 {
 	NEED_MATRIX(c);
@@ -2098,15 +2371,15 @@ extern "C" int blz_solution(blz_ctx *c, uint64_t *x, int *status)
 		return blz_fail(BLZ_EINVAL, "blz_solution: %s", !c->rhs ? "the context has no right-hand side (blz_set_matrix_rhs)" : "NULL argument");
 	if (c->rhs_k > 1)
 		return blz_fail(BLZ_EINVAL, "blz_solution: the context has %d right-hand sides: use blz_solution_block", c->rhs_k);
-	const int n = c->un, np = c->cfg.n;
+	const int n = c->un;
 	const u64 p = c->prime;
 	int k = 0;
 	int rc = blz_kernel_basis(c, &k, nullptr);
 	if (rc != BLZ_OK)
 		return rc;
 	/* the first basis vector with a non-zero border word: v = (y, w), M' v = 0  <=>  M y + w b = 0 */
-	std::vector<uint64_t> brow((size_t)np);
-	if ((rc = get_words(c, brow.data(), slab_ptr(c, BLZ_V) + (size_t)c->border * np * c->cfg.word, np)) != BLZ_OK)
+	std::vector<uint64_t> brow;
+	if ((rc = border_rows_to_host(c, 1, brow)) != BLZ_OK)
 		return rc;
 	int j = 0;
 	while (j < k && brow[(size_t)j] == 0)
@@ -2135,11 +2408,10 @@ extern "C" int blz_solution(blz_ctx *c, uint64_t *x, int *status)
 		if (rc != BLZ_OK)
 			return rc;
 	}
-	HIPCHK(hipMemsetAsync(&c->ctl->flag_t_nonzero, 0, sizeof(int), c->stream));
-	HIPCHK(launch_any_nonzero(c->cfg, slab_ptr(c, BLZ_TMP), c->count[1] * c->cfg.n, &c->ctl->flag_t_nonzero, c->stream));
-	if ((rc = fetch_ctl(c)) != BLZ_OK)
+	int nonzero = 0;
+	if ((rc = residual_flag(c, &nonzero)) != BLZ_OK)
 		return rc;
-	if (c->host_ctl.flag_t_nonzero) {
+	if (nonzero) {
 		*status = 2;
 		return BLZ_OK;
 	}
@@ -2147,7 +2419,8 @@ extern "C" int blz_solution(blz_ctx *c, uint64_t *x, int *status)
 	if ((rc = blz_get_block(c, BLZ_V, v.data())) != BLZ_OK)
 		return rc;
 	for (int64_t i = 0; i + 1 < c->glob_rows[0]; i++)	/* the border row is the last one in the original numbering */
-		x[i] = v[(size_t)i * n];
+		if (owns_row(c, 0, i))		/* (several ranks: the rows this rank owns, like blz_get_block) */
+			x[i] = v[(size_t)i * n];
 	*status = 0;
 	return BLZ_OK;
 }
@@ -2166,12 +2439,7 @@ static int solution_residual(blz_ctx *c, int *nonzero)
 	HIPCHK(e);
 	if (rc != BLZ_OK)
 		return rc;
-	HIPCHK(hipMemsetAsync(&c->ctl->flag_t_nonzero, 0, sizeof(int), c->stream));
-	HIPCHK(launch_any_nonzero(c->cfg, slab_ptr(c, BLZ_TMP), c->count[1] * c->cfg.n, &c->ctl->flag_t_nonzero, c->stream));
-	if ((rc = fetch_ctl(c)) != BLZ_OK)
-		return rc;
-	*nonzero = c->host_ctl.flag_t_nonzero != 0;
-	return BLZ_OK;
+	return residual_flag(c, nonzero);
 }
 
 static inline uint64_t host_mulmod(uint64_t a, uint64_t b, uint64_t p) { return (uint64_t)((unsigned __int128)a * b % p); }
@@ -2191,13 +2459,12 @@ extern "C" int blz_solution_block(blz_ctx *c, uint64_t *x, int *status)
 	/* W = the k border rows of the kb basis vectors, next to -I_k: the basis vectors are v = (y, w) with M y + B w = 0, so a
 	 * combination V c has border part W c, and W c = -e_i makes its upper part a solution of system i */
 	const int cols = kb + k;
-	std::vector<uint64_t> A((size_t)k * cols, 0), brow((size_t)np);
+	std::vector<uint64_t> A((size_t)k * cols, 0), brow;
+	if ((rc = border_rows_to_host(c, k, brow)) != BLZ_OK)
+		return rc;
 	for (int i = 0; i < k; i++) {
-		const int64_t row = k > 1 ? c->border_rows[(size_t)i] : c->border;
-		if ((rc = get_words(c, brow.data(), slab_ptr(c, BLZ_V) + (size_t)row * np * c->cfg.word, np)) != BLZ_OK)
-			return rc;
 		for (int j = 0; j < kb; j++)
-			A[(size_t)i * cols + j] = brow[(size_t)j];
+			A[(size_t)i * cols + j] = brow[(size_t)i * np + j];
 		A[(size_t)i * cols + kb + i] = p - 1;
 	}
 	/* reduced row echelon form of [W | -I] over W's columns */
@@ -2254,7 +2521,7 @@ extern "C" int blz_solution_block(blz_ctx *c, uint64_t *x, int *status)
 	if ((rc = blz_get_block(c, BLZ_V, v.data())) != BLZ_OK)
 		return rc;
 	for (int64_t i = 0; i < c->glob_rows[0] - k; i++)	/* the border rows are the last k */
-		for (int j = 0; j < k; j++)
+		for (int j = 0; j < k && owns_row(c, 0, i); j++)	/* (several ranks: the rows this rank owns, like blz_get_block) */
 			x[i * k + j] = v[(size_t)i * n + j];
 	return BLZ_OK;
 }
@@ -2443,6 +2710,9 @@ extern "C" int blz_set_exchange_mode(blz_ctx *c, int external)
 {
 	if (!c)
 		return blz_fail(BLZ_EINVAL, "blz_set_exchange_mode: NULL context");
+	if (external && c->have_matrix && c->rhs && c->rhs_ranks)
+		return blz_fail(BLZ_EINVAL, "blz_set_exchange_mode: the context carries a right-hand side on several ranks (the all-reduce "
+				"of its border words is the library's own)");
 	c->external_exchange = external != 0;
 	return BLZ_OK;
 }

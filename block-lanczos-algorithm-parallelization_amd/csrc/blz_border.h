@@ -30,4 +30,17 @@ hipError_t launch_border_update_k(const KernelCfg &c, void *T, const void *B, co
 hipError_t launch_border_dot_k(const KernelCfg &c, const void *T, const void *B, int64_t rows, u64 *partial, void *S,
 			       const long long *brow, int k, const DevCtl *ctl, hipStream_t s);
 
+/* Several ranks (blz_set_rhs_ranks): T and B are the rank's own rows.
+ * launch_border_dot_send: send[i * c.n + col] = this rank's share of sum_r B[r, i] * T[r, col] mod p, k x c.n 64-bit words
+ * (k == 1: the single-border dot; B as in the forms above), for an all-reduce over the ranks; partial as above.
+ * launch_border_place: S[own[i], :] = recv[i, :] mod p in the context's width where own[i] >= 0 (own = k local row numbers on
+ * the device, -1 for the rows of other ranks); recv = the all-reduced sums, below nranks * p <= 2^64.
+ * Both are no-ops once the stop flag is up.
+ * launch_border_rows_send: send[i, :] = V[own[i], :] as 64-bit words, zeros where own[i] < 0 (no stop flag: outside the loop). */
+hipError_t launch_border_dot_send(const KernelCfg &c, const void *T, const void *B, int64_t rows, u64 *partial, u64 *send, int k,
+				  const DevCtl *ctl, hipStream_t s);
+hipError_t launch_border_place(const KernelCfg &c, const u64 *recv, void *S, const long long *own, int k, const DevCtl *ctl,
+			       hipStream_t s);
+hipError_t launch_border_rows_send(const KernelCfg &c, const void *V, const long long *own, int k, u64 *send, hipStream_t s);
+
 #endif

@@ -15,6 +15,14 @@
  *   k_border_update_k tmp[r, :] += sum_i B[r, i] * v[brow[i], :]        one read and one write of tmp
  *   k_border_dot_k    Av[brow[i], :] = sum_r B[r, i] * tmp[r, :]        one read of tmp, k accumulators per lane
  *                     (k_border_finalize_k sums the partial k x n tiles and scatters the k rows)
+ *
+ * On several ranks (blz_set_rhs_ranks) a rank holds its own rows of tmp and of B.  The update runs as above on the rank's
+ * slab, its border rows read from the gathered operand.  The dot is taken over the rank's rows only:
+ *   k_border_finalize_send  send[i, :] = this rank's share of border row i, as 64-bit residues (instead of the scatter)
+ *   (all-reduce of the k x n words over the ranks: sums below nranks * p <= 2^64)
+ *   k_border_place          Av[own[i], :] = recv[i, :] mod p on the rank that owns border row i (own[i] = its local row, -1
+ *                           elsewhere), in the slab's word width
+ *   k_border_rows_send      send[i, :] = V[own[i], :] or zeros: the border words of the kernel basis for the same all-reduce
  */
 #include "blz_border.h"
 
@@ -148,6 +156,64 @@ k_border_finalize(const u64 *__restrict__ partial, int nblocks, int n, int G, u6
 	}
 }
 
+/*
+ * send[i * n + col] = sum_b partial[b][i][col] mod p, workgroup i serving border row i: k_border_finalize_k with the k rows
+ * stored one after the other as 64-bit residues instead of scattered into the slab -- the rank's share of the border dot
+ * before the all-reduce over the ranks.  kp = 1 reads k_border_dot's partial rows.  (Partial rows and send buffer are
+ * 64-bit words whatever the slab's width.)
+ */
+__global__ void __launch_bounds__(BLOCK)
+k_border_finalize_send(const u64 *__restrict__ partial, int nblocks, int n, int G, int kp, u64 p, u64 *__restrict__ send,
+		       const DevCtl *__restrict__ ctl)
+{
+	if (ctl->stop)
+		return;
+	__shared__ u64 red[BLOCK];
+	const int t = threadIdx.x, col = t & (G - 1), part = t / G, parts = BLOCK / G, i = blockIdx.x;
+	u64 s = 0;
+	for (int b = part; b < nblocks; b += parts)
+		s = addmod(s, partial[((size_t)b * kp + i) * G + col], p);
+	red[t] = s;
+	__syncthreads();
+	if (t < G && t < n) {
+		u64 x = 0;
+		for (int q = 0; q < parts; q++)
+			x = addmod(x, red[q * G + t], p);
+		send[(size_t)i * n + t] = x;
+	}
+}
+
+/*
+ * S[own[i] * n + col] = recv[i * n + col] mod p for the border rows this rank owns (own[i] >= 0), all n words of the row in
+ * the slab's word width.  recv holds sums of nranks residues, below nranks * p <= 2^64.  One workgroup: k * n <= 1024 words.
+ */
+template <typename W, int MERS>
+__global__ void __launch_bounds__(BLOCK)
+k_border_place(const u64 *__restrict__ recv, int k, int n, ModP m, W *__restrict__ S, const long long *__restrict__ own,
+	       const DevCtl *__restrict__ ctl)
+{
+	if (ctl->stop)
+		return;
+	for (int q = threadIdx.x; q < k * n; q += BLOCK) {
+		const int i = q / n;
+		const long long r = own[i];
+		if (r >= 0)
+			S[r * n + (q - i * n)] = (W)reduce128<MERS>(0, recv[q], m);
+	}
+}
+
+/* send[i * n + col] = V[own[i] * n + col] where this rank owns border row i, zero elsewhere (outside the loop: no stop flag) */
+template <typename W>
+__global__ void __launch_bounds__(BLOCK)
+k_border_rows_send(const W *__restrict__ V, const long long *__restrict__ own, int k, int n, u64 *__restrict__ send)
+{
+	for (int q = threadIdx.x; q < k * n; q += BLOCK) {
+		const int i = q / n;
+		const long long r = own[i];
+		send[q] = r >= 0 ? (u64)V[r * n + (q - i * n)] : 0;
+	}
+}
+
 static inline int border_group(int n)
 {
 	int G = 1;
@@ -203,8 +269,9 @@ hipError_t launch_border_update(const KernelCfg &c, void *T, const void *B, cons
 	return hipGetLastError();
 }
 
-hipError_t launch_border_dot(const KernelCfg &c, const void *T, const void *B, int64_t rows, u64 *partial, void *out_row,
-			     const DevCtl *ctl, hipStream_t s)
+/* the dot and one of its two finalize forms: the row in the slab's width (out_row), or 64-bit words for the all-reduce (send) */
+static hipError_t border_dot_go(const KernelCfg &c, const void *T, const void *B, int64_t rows, u64 *partial, void *out_row,
+				u64 *send, const DevCtl *ctl, hipStream_t s)
 {
 	if (c.n < 1 || c.n > BLZ_BORDER_MAXN)
 		return hipErrorInvalidValue;
@@ -219,7 +286,8 @@ hipError_t launch_border_dot(const KernelCfg &c, const void *T, const void *B, i
 		else
 			hipLaunchKernelGGL((k_border_dot<u32, 0>), grid, blk, 0, s, (const u32 *)T, (const u32 *)B, (long long)rows, n, G, c.m,
 					   partial, ctl);
-		hipLaunchKernelGGL((k_border_finalize<u32>), dim3(1), blk, 0, s, partial, (int)blocks, n, G, c.m.p, (u32 *)out_row, ctl);
+		if (!send)
+			hipLaunchKernelGGL((k_border_finalize<u32>), dim3(1), blk, 0, s, partial, (int)blocks, n, G, c.m.p, (u32 *)out_row, ctl);
 	} else {
 		if (c.mers == 61)
 			hipLaunchKernelGGL((k_border_dot<u64, 61>), grid, blk, 0, s, (const u64 *)T, (const u64 *)B, (long long)rows, n, G, c.m,
@@ -227,9 +295,18 @@ hipError_t launch_border_dot(const KernelCfg &c, const void *T, const void *B, i
 		else
 			hipLaunchKernelGGL((k_border_dot<u64, 0>), grid, blk, 0, s, (const u64 *)T, (const u64 *)B, (long long)rows, n, G, c.m,
 					   partial, ctl);
-		hipLaunchKernelGGL((k_border_finalize<u64>), dim3(1), blk, 0, s, partial, (int)blocks, n, G, c.m.p, (u64 *)out_row, ctl);
+		if (!send)
+			hipLaunchKernelGGL((k_border_finalize<u64>), dim3(1), blk, 0, s, partial, (int)blocks, n, G, c.m.p, (u64 *)out_row, ctl);
 	}
+	if (send)
+		hipLaunchKernelGGL(k_border_finalize_send, dim3(1), blk, 0, s, partial, (int)blocks, n, G, 1, c.m.p, send, ctl);
 	return hipGetLastError();
+}
+
+hipError_t launch_border_dot(const KernelCfg &c, const void *T, const void *B, int64_t rows, u64 *partial, void *out_row,
+			     const DevCtl *ctl, hipStream_t s)
+{
+	return border_dot_go(c, T, B, rows, partial, out_row, nullptr, ctl, s);
 }
 
 /* ---- k right-hand sides: B = rows x KP words (KP = k rounded up to a power of two, zero padded) ---- */
@@ -414,28 +491,32 @@ static void border_update_k_go(const KernelCfg &c, W *T, const W *B, const W *V,
 
 template <typename W, int MERS, int KP>
 static void border_dot_k_go(const KernelCfg &c, const W *T, const W *B, long long rows, u64 *partial, W *S, const long long *brow,
-			    int k, const DevCtl *ctl, hipStream_t s)
+			    int k, u64 *send, const DevCtl *ctl, hipStream_t s)
 {
 	constexpr int U = KP <= 4 ? 4 : (KP == 8 ? 2 : 1);
 	const int n = c.n, G = border_group(n), gpb = BLOCK / G;
 	long long blocks = (rows + (long long)gpb * U - 1) / ((long long)gpb * U);
 	blocks = blocks < 1 ? 1 : (blocks > border_dot_max_blocks(c) ? border_dot_max_blocks(c) : blocks);
 	hipLaunchKernelGGL((k_border_dot_k<W, MERS, KP>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, T, B, rows, n, G, c.m, partial, ctl);
-	hipLaunchKernelGGL((k_border_finalize_k<W>), dim3((unsigned)k), dim3(BLOCK), 0, s, partial, (int)blocks, n, G, KP, c.m.p, S,
-			   brow, ctl);
+	if (send)
+		hipLaunchKernelGGL(k_border_finalize_send, dim3((unsigned)k), dim3(BLOCK), 0, s, partial, (int)blocks, n, G, KP, c.m.p,
+				   send, ctl);
+	else
+		hipLaunchKernelGGL((k_border_finalize_k<W>), dim3((unsigned)k), dim3(BLOCK), 0, s, partial, (int)blocks, n, G, KP, c.m.p, S,
+				   brow, ctl);
 }
 
 /* word width, reducer and KP once, then one of the two launches */
 template <typename W, int MERS>
 static hipError_t border_k_kp(const KernelCfg &c, bool update, void *T, const void *B, void *S, const long long *brow, int k,
-			      long long rows, u64 *partial, const DevCtl *ctl, hipStream_t s)
+			      long long rows, u64 *partial, u64 *send, const DevCtl *ctl, hipStream_t s)
 {
 #define BORDER_K_CASE(KP) \
 	case KP: \
 		if (update) \
 			border_update_k_go<W, MERS, KP>(c, (W *)T, (const W *)B, (const W *)S, brow, k, rows, ctl, s); \
 		else \
-			border_dot_k_go<W, MERS, KP>(c, (const W *)T, (const W *)B, rows, partial, (W *)S, brow, k, ctl, s); \
+			border_dot_k_go<W, MERS, KP>(c, (const W *)T, (const W *)B, rows, partial, (W *)S, brow, k, send, ctl, s); \
 		break
 	switch (border_kp(k)) {
 	BORDER_K_CASE(2);
@@ -449,27 +530,65 @@ static hipError_t border_k_kp(const KernelCfg &c, bool update, void *T, const vo
 }
 
 static hipError_t border_k(const KernelCfg &c, bool update, void *T, const void *B, void *S, const long long *brow, int k,
-			   int64_t rows, u64 *partial, const DevCtl *ctl, hipStream_t s)
+			   int64_t rows, u64 *partial, u64 *send, const DevCtl *ctl, hipStream_t s)
 {
 	if (c.n < 1 || c.n > BLZ_BORDER_MAXN || k < 2 || k > BLZ_BORDER_MAXK)
 		return hipErrorInvalidValue;
 	if (update && rows <= 0)
 		return hipSuccess;
 	if (c.word == 4)
-		return c.mers == 31 ? border_k_kp<u32, 31>(c, update, T, B, S, brow, k, rows, partial, ctl, s)
-				    : border_k_kp<u32, 0>(c, update, T, B, S, brow, k, rows, partial, ctl, s);
-	return c.mers == 61 ? border_k_kp<u64, 61>(c, update, T, B, S, brow, k, rows, partial, ctl, s)
-			    : border_k_kp<u64, 0>(c, update, T, B, S, brow, k, rows, partial, ctl, s);
+		return c.mers == 31 ? border_k_kp<u32, 31>(c, update, T, B, S, brow, k, rows, partial, send, ctl, s)
+				    : border_k_kp<u32, 0>(c, update, T, B, S, brow, k, rows, partial, send, ctl, s);
+	return c.mers == 61 ? border_k_kp<u64, 61>(c, update, T, B, S, brow, k, rows, partial, send, ctl, s)
+			    : border_k_kp<u64, 0>(c, update, T, B, S, brow, k, rows, partial, send, ctl, s);
 }
 
 hipError_t launch_border_update_k(const KernelCfg &c, void *T, const void *B, const void *V, const long long *brow, int k,
 				  int64_t rows, const DevCtl *ctl, hipStream_t s)
 {
-	return border_k(c, true, T, B, const_cast<void *>(V), brow, k, rows, nullptr, ctl, s);
+	return border_k(c, true, T, B, const_cast<void *>(V), brow, k, rows, nullptr, nullptr, ctl, s);
 }
 
 hipError_t launch_border_dot_k(const KernelCfg &c, const void *T, const void *B, int64_t rows, u64 *partial, void *S,
 			       const long long *brow, int k, const DevCtl *ctl, hipStream_t s)
 {
-	return border_k(c, false, const_cast<void *>(T), B, S, brow, k, rows, partial, ctl, s);
+	return border_k(c, false, const_cast<void *>(T), B, S, brow, k, rows, partial, nullptr, ctl, s);
+}
+
+/* ---- several ranks: the rank's share of the dot into a send buffer, the all-reduced rows into the slab ---- */
+
+hipError_t launch_border_dot_send(const KernelCfg &c, const void *T, const void *B, int64_t rows, u64 *partial, u64 *send, int k,
+				  const DevCtl *ctl, hipStream_t s)
+{
+	if (!send)
+		return hipErrorInvalidValue;
+	if (k == 1)
+		return border_dot_go(c, T, B, rows, partial, nullptr, send, ctl, s);
+	return border_k(c, false, const_cast<void *>(T), B, nullptr, nullptr, k, rows, partial, send, ctl, s);
+}
+
+hipError_t launch_border_place(const KernelCfg &c, const u64 *recv, void *S, const long long *own, int k, const DevCtl *ctl,
+			       hipStream_t s)
+{
+	if (c.n < 1 || c.n > BLZ_BORDER_MAXN || k < 1 || k > BLZ_BORDER_MAXK)
+		return hipErrorInvalidValue;
+	const dim3 grid(1), blk(BLOCK);
+	if (c.word == 4)	/* (the sums of 32-bit residues go through Barrett at either reducer class, as in k_reduce_modp) */
+		hipLaunchKernelGGL((k_border_place<u32, 0>), grid, blk, 0, s, recv, k, c.n, c.m, (u32 *)S, own, ctl);
+	else if (c.mers == 61)
+		hipLaunchKernelGGL((k_border_place<u64, 61>), grid, blk, 0, s, recv, k, c.n, c.m, (u64 *)S, own, ctl);
+	else
+		hipLaunchKernelGGL((k_border_place<u64, 0>), grid, blk, 0, s, recv, k, c.n, c.m, (u64 *)S, own, ctl);
+	return hipGetLastError();
+}
+
+hipError_t launch_border_rows_send(const KernelCfg &c, const void *V, const long long *own, int k, u64 *send, hipStream_t s)
+{
+	if (c.n < 1 || c.n > BLZ_BORDER_MAXN || k < 1 || k > BLZ_BORDER_MAXK)
+		return hipErrorInvalidValue;
+	if (c.word == 4)
+		hipLaunchKernelGGL((k_border_rows_send<u32>), dim3(1), dim3(BLOCK), 0, s, (const u32 *)V, own, k, c.n, send);
+	else
+		hipLaunchKernelGGL((k_border_rows_send<u64>), dim3(1), dim3(BLOCK), 0, s, (const u64 *)V, own, k, c.n, send);
+	return hipGetLastError();
 }

@@ -2338,6 +2338,48 @@ int blz_rhs_load_block(const char *path, uint64_t prime, int64_t len, int kmax, 
 	return load_columns(path, prime, len, kmax, 1, k, b);
 }
 
+/* ---- the bordered solve on several ranks: where a border row lives, and a rank's own rows of B (include/blz.h) ---- */
+
+int64_t blz_gathered_position(const int64_t *bounds, int nranks, int64_t stride, int chunks, int64_t row, int *owner, int64_t *local)
+{
+	if (!bounds || nranks < 1 || chunks < 1 || stride < chunks || stride % chunks || row < bounds[0] || row >= bounds[nranks])
+		return blz_fail(BLZ_EINVAL, "blz_gathered_position: bad argument");
+	int lo = 0, hi = nranks - 1;	/* largest g with bounds[g] <= row, as blz_remap_columns finds it */
+	while (lo < hi) {
+		const int mid = (lo + hi + 1) / 2;
+		if (bounds[mid] <= row)
+			lo = mid;
+		else
+			hi = mid - 1;
+	}
+	const int64_t q = row - bounds[lo], piece = stride / chunks;
+	if (q >= stride)
+		return blz_fail(BLZ_EINVAL, "blz_gathered_position: rank %d holds more rows than a slab has", lo);
+	if (owner)
+		*owner = lo;
+	if (local)
+		*local = q;
+	return (q / piece) * ((int64_t)nranks * piece) + (int64_t)lo * piece + q % piece;
+}
+
+int blz_rhs_cut(const uint64_t *b, int64_t len, int k, int kp, uint64_t prime, const int32_t *perm, int64_t first, int64_t count,
+		uint64_t *out)
+{
+	if (!b || !out || len < 0 || k < 1 || kp < k || first < 0 || count < 0 || first + count > len)
+		return blz_fail(BLZ_EINVAL, "blz_rhs_cut: bad argument");
+	memset(out, 0, (size_t)(count > 0 ? count : 1) * (size_t)kp * sizeof *out);
+	for (int64_t r = 0; r < len; r++) {
+		const int64_t at = perm ? perm[r] : r;
+		for (int i = 0; i < k; i++)	/* every rank reads all of b: a bad word is refused by all of them */
+			if (b[r * k + i] >= prime)
+				return blz_fail(BLZ_EINVAL, "a right-hand side word is not below p: b[%lld, %d]", (long long)r, i);
+		if (at < first || at >= first + count)
+			continue;
+		memcpy(out + (size_t)(at - first) * kp, b + (size_t)r * k, (size_t)k * sizeof *out);
+	}
+	return BLZ_OK;
+}
+
 int blz_check_solution_block(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
 			     int *status, int64_t *bad_row)
 {

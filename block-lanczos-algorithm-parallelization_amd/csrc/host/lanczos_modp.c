@@ -29,8 +29,8 @@
 static long n = 1;
 static uint64_t prime;
 static char *matrix_filename, *kernel_filename, *rhs_filename;
-static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis;
-static int stop_after = -1, checkpoint_timer = 60, device, gpus = 1;
+static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis, rhs_gpus_given;
+static int stop_after = -1, checkpoint_timer = 60, device, gpus = 1, rhs_gpus;
 
 static double wtime(void)
 {
@@ -79,6 +79,8 @@ static void usage(char **argv)
 	printf("                            gets b as a dense border and --output-file receives the solution x\n");
 	printf("                            A file of k columns, 2 <= k <= min(N, 16), solves the k systems in ONE run: the\n");
 	printf("                            output has k columns, zero where a system has no solution\n");
+	printf("--rhs-gpus G                with --rhs: row-partition the bordered matrix over G GPUs, as --gpus G does for a plain\n");
+	printf("                            run (the border's k x N words are all-reduced once more per iteration)\n");
 	printf("--device D                  first HIP device to run on [default 0]\n");
 	printf("--gpus G                    row-partition the matrix over G GPUs of this node (devices D..D+G-1), RCCL\n");
 	printf("                            all-gather of the block before each product [default 1]\n");
@@ -88,6 +90,7 @@ static void usage(char **argv)
 	printf("The --stop-after and --basis arguments mutually exclusive\n");
 	printf("The --rhs argument excludes --stop-after and --gpus above 1, and --basis (the solution is taken from the\n");
 	printf("kernel basis of the bordered matrix, which --rhs computes itself; it is one vector per system, not a kernel block)\n");
+	printf("The --rhs-gpus argument needs --rhs and excludes --gpus above 1\n");
 	exit(0);
 }
 
@@ -101,6 +104,7 @@ static void process_command_line_options(int argc, char **argv)
 		{"load-checkpoint", no_argument, NULL, 'L'}, {"device", required_argument, NULL, 'd'},
 		{"gpus", required_argument, NULL, 'g'}, {"verify", no_argument, NULL, 'V'},
 		{"cache", no_argument, NULL, 'C'}, {"basis", no_argument, NULL, 'B'}, {"rhs", required_argument, NULL, 'R'},
+		{"rhs-gpus", required_argument, NULL, 'G'},
 		{"help", no_argument, NULL, 'h'}, {NULL, 0, NULL, 0}
 	};
 	int ch;
@@ -127,6 +131,7 @@ static void process_command_line_options(int argc, char **argv)
 		case 'C': use_cache = true; break;
 		case 'B': basis = true; break;
 		case 'R': rhs_filename = optarg; break;
+		case 'G': rhs_gpus = atoi(optarg); rhs_gpus_given = true; break;
 		case 'h': usage(argv); break;
 		default: errx(1, "Unknown option\n");
 		}
@@ -139,12 +144,19 @@ static void process_command_line_options(int argc, char **argv)
 		usage(argv);
 	if (rhs_filename != NULL && (stop_after > 0 || basis || gpus > 1))
 		usage(argv);
+	if (rhs_gpus_given && (rhs_filename == NULL || gpus > 1))
+		usage(argv);
 	if (prime >= (1ull << 62))
 		errx(1, "p is capped at 2**62 - 1.");
 	if (n < 1 || n > BLZ_MAX_N)
 		errx(1, "n must be between 1 and %d", BLZ_MAX_N);
 	if (gpus < 1 || gpus > 64)
 		errx(1, "--gpus must be between 1 and 64");
+	if (rhs_gpus_given) {
+		if (rhs_gpus < 1 || rhs_gpus > 64)
+			errx(1, "--rhs-gpus must be between 1 and 64");
+		gpus = rhs_gpus;	/* from here on the team of --gpus, with the border distributed (blz_set_rhs_ranks) */
+	}
 }
 
 #define CHECK(call)                                                \
@@ -223,7 +235,7 @@ static void correctness_tests(blz_ctx *ctx)
  * blz_comm_init / blz_iterate / blz_final_check must be entered by all ranks concurrently).  With --gpus 1 the
  * operation runs on the calling thread.
  */
-enum { OP_CREATE, OP_COMM, OP_MATRIX, OP_INIT, OP_SET_VP, OP_ITERATE, OP_GET, OP_FINAL, OP_BASIS, OP_SNAP, OP_DESTROY };
+enum { OP_CREATE, OP_COMM, OP_MATRIX, OP_RHS, OP_INIT, OP_SET_VP, OP_ITERATE, OP_GET, OP_FINAL, OP_BASIS, OP_SOLVE, OP_SNAP, OP_DESTROY };
 
 static struct {
 	blz_ctx *ctx[64];
@@ -234,6 +246,8 @@ static struct {
 	uint64_t *host, *host2;
 	int64_t its;
 	int done[64], stopped[64], nonzero[64], zero[64], rank_vtm[64], k[64], rc[64];
+	const uint64_t *rhs;		/* --rhs-gpus: the whole right-hand side, every rank keeps its rows */
+	int rhs_k, status[64][BLZ_MAX_RHS];
 	float ms[64];
 	char err[64][512];
 } team;
@@ -254,6 +268,9 @@ static void *team_worker(void *arg)
 		break;
 	case OP_MATRIX:
 		rc = blz_set_matrix_prepared(team.ctx[g], team.P, g);
+		break;
+	case OP_RHS:		/* collective: every rank checks the border rows it owns */
+		rc = blz_set_rhs_ranks(team.ctx[g], team.rhs_k, team.rhs);
 		break;
 	case OP_INIT:
 		rc = blz_init_v(team.ctx[g]);
@@ -278,6 +295,10 @@ static void *team_worker(void *arg)
 		rc = blz_block_rref(team.ctx[g], BLZ_TMP, NULL, &team.rank_vtm[g], NULL);
 		if (rc == BLZ_OK)
 			rc = blz_kernel_basis(team.ctx[g], &team.k[g], NULL);
+		break;
+	case OP_SOLVE:		/* collective; writes only the rows of x this rank owns */
+		rc = team.rhs_k > 1 ? blz_solution_block(team.ctx[g], team.host, team.status[g])
+				    : blz_solution(team.ctx[g], team.host, &team.status[g][0]);
 		break;
 	case OP_SNAP:
 		rc = blz_snapshot_begin(team.ctx[g]);
@@ -334,6 +355,21 @@ static void team_get(int block, uint64_t *host)
 	team_run(OP_GET);
 }
 
+/* --rhs-gpus: every rank runs the (collective) solution call and writes its own rows of x; the statuses are the same on
+ * every rank by construction, which is checked here */
+static void team_solve(uint64_t *x, int k, int *status)
+{
+	team.host = x;
+	team.rhs_k = k;
+	team_run(OP_SOLVE);
+	for (int i = 0; i < k; i++) {
+		status[i] = team.status[0][i];
+		for (int g = 1; g < gpus; g++)
+			if (team.status[g][i] != status[i])
+				errx(1, "GPU %d and GPU %d disagree on right-hand side %d", device, device + g, i);
+	}
+}
+
 /* the checkpoint writer: collects the snapshot every context has begun (blz_snapshot_wait is the one call that may come
  * from another thread than the context's owner), writes lanczos_modp.ckpt atomically */
 static struct {
@@ -381,6 +417,10 @@ int main(int argc, char **argv)
 {
 	process_command_line_options(argc, argv);
 	setenv("HSA_ENABLE_IPC_MODE_LEGACY", "0", 0);	/* dmabuf IPC for RCCL; must precede the first HIP call */
+	if (rhs_gpus_given)
+		/* a bordered context runs no short-side product (the border rows of the operand are not gathered in that form):
+		 * blz_set_matrix_prepared plans none on a tall or wide matrix.  The prepared matrix and its cache do not depend on it. */
+		setenv("BLZ_SHORT_SIDE", "0", 1);
 
 	printf("Loading matrix from %s\n", matrix_filename);
 	fflush(stdout);
@@ -458,7 +498,11 @@ int main(int argc, char **argv)
 	}
 	team.P = P;
 	team_run(OP_MATRIX);
-	if (rhs && rhs_k > 1)
+	if (rhs && rhs_gpus_given) {
+		team.rhs = rhs;
+		team.rhs_k = rhs_k;
+		team_run(OP_RHS);
+	} else if (rhs && rhs_k > 1)
 		CHECK(blz_set_rhs_block(ctx, rhs_k, rhs));
 	else if (rhs)
 		CHECK(blz_set_rhs(ctx, rhs));
@@ -584,7 +628,10 @@ int main(int argc, char **argv)
 	}
 	if (rhs_filename && rhs_k > 1) {	/* no reference counterpart: blz_solution_block, include/blz.h */
 		int status[BLZ_MAX_RHS] = { 0 }, solved = 0;
-		CHECK(blz_solution_block(ctx, v, status));
+		if (rhs_gpus_given)
+			team_solve(v, rhs_k, status);
+		else
+			CHECK(blz_solution_block(ctx, v, status));
 		printf("Solve:\n");
 		for (int i = 0; i < rhs_k; i++) {
 			if (status[i] == 0)
@@ -606,7 +653,10 @@ int main(int argc, char **argv)
 		}
 	} else if (rhs_filename) {		/* no reference counterpart: blz_solution, include/blz.h */
 		int status = 0;
-		CHECK(blz_solution(ctx, v, &status));
+		if (rhs_gpus_given)
+			team_solve(v, 1, &status);
+		else
+			CHECK(blz_solution(ctx, v, &status));
 		printf("Solve:\n");
 		if (status == 0)
 			printf(right_kernel ? "  - OK: M*x == b\n" : "  - OK: x*M == b\n");

@@ -397,6 +397,29 @@ def check_solution_block(matrix_path, rhs_path, x_path, prime, right=False):
     return [(int(status[i]), int(rows[i]) if status[i] == 2 else None) for i in range(k)]
 
 
+def gathered_position(bounds, stride, chunks, row):
+    """blz_gathered_position(): (owner, local row, position in the gathered operand) of row `row` (solver's numbering)."""
+    bd = np.ascontiguousarray(bounds, dtype=np.int64)
+    owner, local = C.c_int(-1), C.c_int64(-1)
+    lib().blz_gathered_position.restype = C.c_int64
+    pos = int(lib().blz_gathered_position(bd.ctypes.data_as(C.POINTER(C.c_int64)), C.c_int(len(bd) - 1), C.c_int64(stride),
+                                          C.c_int(chunks), C.c_int64(row), C.byref(owner), C.byref(local)))
+    if pos < 0:
+        check(pos)
+    return int(owner.value), int(local.value), pos
+
+
+def rhs_cut(b, prime, first, count, kp, perm=None):
+    """blz_rhs_cut(): rows [first, first + count) (solver's numbering) of the len x k block b as a count x kp array."""
+    b = np.ascontiguousarray(b, dtype=np.uint64)
+    out = np.full(max(count, 1) * kp, 0xDEADBEEF, dtype=np.uint64)
+    pm = np.ascontiguousarray(perm, dtype=np.int32) if perm is not None else None
+    check(lib().blz_rhs_cut(ptr(b.reshape(-1)), C.c_int64(b.shape[0]), C.c_int(b.shape[1]), C.c_int(kp), C.c_uint64(prime),
+                            pm.ctypes.data_as(C.POINTER(C.c_int32)) if pm is not None else None, C.c_int64(first),
+                            C.c_int64(count), ptr(out)))
+    return out[:count * kp].reshape(count, kp)
+
+
 def checkpoint_save(path, prime, n, right, nrows, iterations, v, p):
     check(lib().blz_checkpoint_save(path.encode(), C.c_uint64(prime), C.c_int(n), C.c_int(int(right)),
                                     C.c_int64(nrows), C.c_int64(iterations), ptr(u64(v)), ptr(u64(p))))
@@ -502,6 +525,22 @@ class Context:
         b = np.ascontiguousarray(b, dtype=np.uint64)
         assert b.ndim == 2 and b.shape[0] == self.rows(TMP), (b.shape, self.rows(TMP))
         check(lib().blz_set_rhs_block(self.h, C.c_int(b.shape[1]), ptr(b.reshape(-1))))
+
+    def set_matrix_rhs_ranks(self, M, b, right=False, rank=0, nranks=1):
+        """blz_set_matrix_rhs_ranks(): the bordered operator of set_matrix_rhs_block row-partitioned over nranks ranks (attach
+        the communicator first); b is the WHOLE block (M.nrows x k resp. M.ncols x k) on every rank.  Collective."""
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        assert b.ndim == 2 and b.shape[0] == (M.nrows if right else M.ncols), (b.shape, M.nrows, M.ncols, right)
+        check(lib().blz_set_matrix_rhs_ranks(self.h, C.byref(M.c), C.c_int(int(right)), C.c_int(b.shape[1]), ptr(b.reshape(-1)),
+                                             C.c_int(rank), C.c_int(nranks)))
+        self.right = bool(right)
+
+    def set_rhs_ranks(self, b):
+        """blz_set_rhs_ranks(): the k borders for a matrix this rank has set with the k extra empty last rows / columns; b is
+        the whole rows(TMP) x k block on every rank.  Collective."""
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        assert b.ndim == 2 and b.shape[0] == self.rows(TMP), (b.shape, self.rows(TMP))
+        check(lib().blz_set_rhs_ranks(self.h, C.c_int(b.shape[1]), ptr(b.reshape(-1))))
 
     @property
     def rhs_count(self):

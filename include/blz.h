@@ -244,6 +244,23 @@ int blz_check_solution(const char *matrix_path, const char *rhs_path, const char
 int blz_check_solution_block(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
 			     int *status, int64_t *bad_row);
 
+/* TEST HOOKS, not part of the supported interface (they may change or go with the layout they describe; callers use
+ * blz_set_rhs_ranks): two pieces of host arithmetic of the bordered solve on several ranks, visible so that tests can hold
+ * them against a restatement and run them under a sanitizer in a program of their own.
+ * blz_gathered_position: row `row` (solver's numbering) of a block partitioned by bounds[0..nranks] belongs to the rank g with
+ * bounds[g] <= row < bounds[g + 1] (*owner), is row q = row - bounds[g] of that rank's slab (*local), and sits at
+ *     (q / piece) * (nranks * piece) + g * piece + q % piece,   piece = stride / chunks,
+ * in the gathered operand (the return value; the layout blz_shard_matrix describes; the identity for one rank).  owner and
+ * local may be NULL.  Negative = BLZ_EINVAL (row outside the bounds, stride not a multiple of chunks).
+ * blz_rhs_cut: the rows [first, first + count) in the solver's numbering of the len x k right-hand sides b (row-major,
+ * original numbering; perm[r] = solver's number of row r, NULL = identity) as count x kp words, zero padded -- what one rank
+ * keeps on its device.  out has room for max(count, 1) * kp words.  A word of b that is not below prime, in anybody's rows,
+ * is BLZ_EINVAL. */
+int64_t blz_gathered_position(const int64_t *bounds, int nranks, int64_t stride, int chunks, int64_t row, int *owner,
+			      int64_t *local);
+int blz_rhs_cut(const uint64_t *b, int64_t len, int k, int kp, uint64_t prime, const int32_t *perm, int64_t first, int64_t count,
+		uint64_t *out);
+
 /* Checkpoints (openMP/lanczos_modp.c:571-676, :933-940, :1013-1022).  blz_checkpoint_save writes
  * one binary file atomically (tmp + rename): v, p, iteration count, prime, n, shape.
  * The *_ref_text pair reads/writes the reference's five text files (v.txt tmp.txt Av.txt p.txt
@@ -291,7 +308,8 @@ int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank);
  * each product (blz_spmv included):  tmp[r, :] += b[r] * v[border, :]  after the product that writes the rows of tmp,
  * Av[border, :] = sum_r b[r] * tmp[r, :]  after the other.  Iterations, checkpoints, blz_final_check, blz_kernel_basis
  * work as on any matrix; the second product runs without the fused inner products (blz_slab_plan reports fused == 0).
- * One rank only: with nranks > 1, a communicator or a loopback group attached the call fails with BLZ_EINVAL.
+ * One rank only: with nranks > 1, a communicator or a loopback group attached the call fails with BLZ_EINVAL (several ranks:
+ * blz_set_rhs_ranks, below).
  *   blz_set_matrix_rhs  the one-call form (prepare, upload, set the border)
  *   blz_set_rhs         sets the border on a context whose matrix the CALLER has set with the extra empty last row
  *                       (right == 0) / column (right != 0), e.g. through blz_prepare_for / blz_prepared_load /
@@ -305,7 +323,28 @@ int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank);
  *   blz_set_matrix_rhs_block  the one-call form
  *   blz_set_rhs_block         for a matrix the caller has set with the k extra empty last rows / columns
  *   blz_rhs_count             0 without a border, 1 after blz_set_rhs / blz_set_matrix_rhs, k after the block forms
- * k == 1 is the single border above in every respect.  Same refusals (BLZ_EINVAL) as for one right-hand side. */
+ * k == 1 is the single border above in every respect.  Same refusals (BLZ_EINVAL) as for one right-hand side.
+ *
+ * Several ranks -- nranks > 1 with an RCCL communicator, a loopback group, or BLZ_FORCE_COMM=1 on one rank -- go through two
+ * entry points of their own (the four above keep their refusals):
+ *   blz_set_matrix_rhs_ranks  the one-call form: M prepared for nranks with the dimension raised by k, rank `rank`'s slabs,
+ *                             then the border.  It plans no short-side product, whatever BLZ_SHORT_SIDE says.
+ *   blz_set_rhs_ranks         the border for a matrix the caller has set for its rank with the k empty last rows / columns
+ *                             (blz_set_matrix_prepared)
+ * b is the WHOLE right-hand side on every rank (rows x k words, row-major, below p), 1 <= k <= min(n, BLZ_MAX_RHS); a rank
+ * keeps its own rows of it.  Both are collective: every rank checks the border rows it owns for emptiness and the verdict is
+ * summed over the ranks, so either all ranks succeed or all fail.  On a plain single rank they are blz_set_rhs_block.
+ * Per product and rank: the border update runs on the rank's slab of tmp with the k border rows read from the gathered
+ * operand (nothing more is exchanged); the border dot runs over the rank's own rows, its k x n words are all-reduced (one
+ * more small collective per iteration) and the rank that owns border row i stores it.  The border rows may sit on different
+ * ranks.  blz_iterate, blz_spmv, blz_final_check, blz_kernel_basis, snapshots work as on any several-rank context;
+ * blz_solution and blz_solution_block become collective there (every rank the same status; each writes only the rows of x it
+ * owns, like blz_get_block, and leaves the rest of x untouched).
+ * Refused with BLZ_EINVAL: external-exchange mode (and blz_set_exchange_mode(ctx, 1) afterwards); a matrix whose short-side
+ * form is active (the border rows of the operand are not gathered in that form); border rows that are not empty; words not
+ * below p; k out of range. */
+int blz_set_matrix_rhs_ranks(blz_ctx *ctx, const blz_coo *M, int right, int k, const uint64_t *b, int rank, int nranks);
+int blz_set_rhs_ranks(blz_ctx *ctx, int k, const uint64_t *b);
 int blz_set_matrix_rhs_block(blz_ctx *ctx, const blz_coo *M, int right, int k, const uint64_t *b);
 int blz_set_rhs_block(blz_ctx *ctx, int k, const uint64_t *b);
 int blz_rhs_count(const blz_ctx *ctx);
@@ -490,7 +529,8 @@ int blz_sync(blz_ctx *ctx);
 /* Per-kernel HIP-event spans inside blz_iterate (on the stream the kernels run on).  blz_profile(ctx,1)
  * clears and starts collecting, blz_profile(ctx,0) stops; blz_profile_read sums the spans collected so
  * far into 8 classes: 0 first SpMV, 1 second SpMV, 2 block_dot (+finalize), 3 semi_inverse,
- * 4 orthogonalize, 5 all-gather of v, 6 all-gather of tmp, 7 all-reduce of the n x n products. */
+ * 4 orthogonalize, 5 all-gather of v, 6 all-gather of tmp, 7 all-reduce of the n x n products (and, on a bordered
+ * several-rank context, of the k x n border words; the border kernels count with the product they follow). */
 #define BLZ_PROFILE_CLASSES 8
 int blz_profile(blz_ctx *ctx, int enable);
 int blz_profile_read(blz_ctx *ctx, double ms_sum[BLZ_PROFILE_CLASSES], int64_t launches[BLZ_PROFILE_CLASSES]);
@@ -498,7 +538,8 @@ int blz_profile_read(blz_ctx *ctx, double ms_sum[BLZ_PROFILE_CLASSES], int64_t l
 /* Exchange mode of a multi-rank context: 0 (default) = the library issues the RCCL collectives itself
  * inside blz_iterate / blz_block_dot; 1 = external: collectives are skipped and the caller moves the
  * slabs between ranks with blz_get_block / blz_set_block / blz_get_small / blz_set_small (used by the
- * single-GPU emulation tests of the sharded schedule; blz_iterate is refused in this mode). */
+ * single-GPU emulation tests of the sharded schedule; blz_iterate is refused in this mode).  A context that carries a
+ * right-hand side on several ranks (blz_set_rhs_ranks) refuses external = 1 with BLZ_EINVAL. */
 int blz_set_exchange_mode(blz_ctx *ctx, int external);
 
 /* Multi-GPU (one process per GPU).  id_bytes = ncclUniqueId from blz_comm_unique_id() on rank 0,
