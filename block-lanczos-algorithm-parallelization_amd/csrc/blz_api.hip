@@ -161,6 +161,7 @@ struct blz_ctx {
 	hipStream_t stream = nullptr;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	bool have_matrix = false;
+	bool values_signed = false;	/* signed value mode: matrix values are int32 bit patterns, an entry a means a mod p */
 	int right = 0, rank = 0, nranks = 1;
 	int64_t glob_rows[2] = { 0, 0 };		/* side 0: N, side 1: C */
 	int64_t first[2] = { 0, 0 }, count[2] = { 0, 0 }, stride[2] = { 0, 0 };
@@ -527,9 +528,42 @@ extern "C" void blz_destroy(blz_ctx *c)
 
 extern "C" int blz_word_bytes(const blz_ctx *c) { return c ? c->cfg.word : 0; }
 
-static int upload_csr(blz_ctx *c, const blz_csr &H, DevCsr &D, int64_t hot_rows = 0, bool dot_slab = false, double locality = 1.0)
+extern "C" int blz_set_values_signed(blz_ctx *c, int on)
+{
+	if (!c)
+		return blz_fail(BLZ_EINVAL, "blz_set_values_signed: NULL context");
+	if (c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "blz_set_values_signed: a matrix is resident; choose the value mode before the matrix is set");
+	c->values_signed = on != 0;
+	return BLZ_OK;
+}
+
+extern "C" int blz_values_signed(const blz_ctx *c) { return c && c->values_signed ? 1 : 0; }
+
+static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows = 0, bool dot_slab = false, double locality = 1.0)
 {
 	free_csr(D);
+	/* Signed value mode: H0.val holds int32 bit patterns.  64-bit words: they travel as they are and the slab's products run
+	 * the signed instantiations -- unless no entry is negative, when the pattern IS the residue and the unsigned ones do.
+	 * 4-byte words (p < 2^32): a mod p fits a u32, so the values are canonicalised here and today's kernels run. */
+	blz_csr H = H0;
+	std::vector<u32> canon;
+	bool sgn = false;
+	if (c->values_signed && H0.val) {
+		if (c->cfg.word == 8) {
+			for (int64_t k = 0; k < H0.nnz && !sgn; k++)
+				sgn = (int32_t)H0.val[k] < 0;
+		} else {
+			canon.resize((size_t)H0.nnz);
+			const int64_t p = (int64_t)c->prime;
+			for (int64_t k = 0; k < H0.nnz; k++) {
+				const int64_t r = (int64_t)(int32_t)H0.val[k] % p;
+				canon[(size_t)k] = (u32)(r < 0 ? r + p : r);
+			}
+			H.val = canon.data();
+		}
+	}
+	D.sgn = sgn;
 	D.locality = locality;
 	D.rows = H.rows;
 	D.cols = H.cols;
@@ -702,6 +736,8 @@ extern "C" uint64_t blz_prepare_key(const blz_ctx *c, uint64_t content_hash, int
 				   (uint64_t)(q.min_share * 1e6), (uint64_t)mrows, (uint64_t)mcols, (uint64_t)nnz, 2 /* format */ };
 	for (uint64_t x : parts)
 		h = (h ^ x) * 0x100000001b3ull;
+	if (c->values_signed)	/* one more round in signed value mode only: the unsigned keys are what they were */
+		h = (h ^ 0x5349474E45440001ull) * 0x100000001b3ull;
 	return h ? h : 1;
 }
 
@@ -1394,6 +1430,18 @@ extern "C" int blz_slab_plan(const blz_ctx *c, int transpose, int piece, blz_pla
 	/* the epilogue rides on the last piece of the second product */
 	out->fused = t == (c->right ? 1 : 0) && iteration_fuses(c) && piece == out->pieces - 1;
 	return BLZ_OK;
+}
+
+extern "C" int blz_slab_signed(const blz_ctx *c, int transpose, int piece)
+{
+	if (!c || !c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "blz_slab_signed: no context or no matrix");
+	const int t = transpose ? 1 : 0;
+	const bool sh = c->short_side[t];
+	if (piece < 0 || piece >= (sh ? 1 : (int)c->csr[t].size()))
+		return blz_fail(BLZ_EINVAL, "blz_slab_signed: piece %d of %d", piece, sh ? 1 : (int)c->csr[t].size());
+	const DevCsr &A = sh ? c->csr_short[t] : c->csr[t][(size_t)piece];
+	return A.sgn ? 1 : 0;
 }
 
 extern "C" int64_t blz_matrix_stream_bytes(const blz_ctx *c, int transpose)

@@ -28,6 +28,8 @@ struct DevCsr {
 	int *col_idx = nullptr;
 	u32 *val = nullptr;	/* nullptr: all ones, or packed (palette != nullptr) */
 	u32 *palette = nullptr;	/* 256 values: col_idx then holds  column | (palette index << 24)  */
+	bool sgn = false;	/* signed value mode AND the slab has a negative entry AND 64-bit words: its values are int32 bit
+				 * patterns and its products run the signed instantiations (acc_mac_val<true>, modp.h) */
 	HeavySeg *heavy = nullptr;	/* segments of the rows longer than heavy_thr: handled by k_spmv_heavy */
 	int n_heavy = 0;
 	HeavyRow *heavy_multi = nullptr;	/* the rows among them that span several segments */

@@ -104,9 +104,10 @@ MODP_DEV u64 shfl_xor64(u64 x, int mask)
  * shortens the dependent chain of a row -- relat8 shape, 15 us products: 17.0 -> 15.8 us; structured workload, gathers that
  * hit: 663 -> 647 us -- and costs the fabric-bound uniform shapes their dead slots (GL7d19 shape: 656 -> 664 us), so the
  * slab's plan asks for it only where the gathers hit or the product is a few launches' worth of latency (round 3). */
-template <typename W, bool TAILB = false>
+/* SGN: signed value mode (acc_mac_val, modp.h); `p` is read by that form only */
+template <typename W, bool TAILB = false, bool SGN = false>
 MODP_DEV void spmv_accumulate(Acc &acc, u32 k, u32 e, const int *__restrict__ ci, const u32 *__restrict__ va,
-			      const u32 *spal, const W *__restrict__ X, int stride, int xl)
+			      const u32 *spal, const W *__restrict__ X, int stride, int xl, u64 p = 0)
 {
 	if (spal) {
 		/* packed stream: one u32 per entry = column (24 bits) | index into the value palette (8 bits, in LDS) */
@@ -114,10 +115,10 @@ MODP_DEV void spmv_accumulate(Acc &acc, u32 k, u32 e, const int *__restrict__ ci
 			const u32 p0 = (u32)ci[k], p1 = (u32)ci[k + 1], p2 = (u32)ci[k + 2], p3 = (u32)ci[k + 3];
 			const W x0 = X[(size_t)(p0 & 0xFFFFFFu) * stride + xl], x1 = X[(size_t)(p1 & 0xFFFFFFu) * stride + xl];
 			const W x2 = X[(size_t)(p2 & 0xFFFFFFu) * stride + xl], x3 = X[(size_t)(p3 & 0xFFFFFFu) * stride + xl];
-			acc_mac32(acc, spal[p0 >> 24], x0);
-			acc_mac32(acc, spal[p1 >> 24], x1);
-			acc_mac32(acc, spal[p2 >> 24], x2);
-			acc_mac32(acc, spal[p3 >> 24], x3);
+			acc_mac_val<SGN>(acc, spal[p0 >> 24], x0, p);
+			acc_mac_val<SGN>(acc, spal[p1 >> 24], x1, p);
+			acc_mac_val<SGN>(acc, spal[p2 >> 24], x2, p);
+			acc_mac_val<SGN>(acc, spal[p3 >> 24], x3, p);
 		}
 		if (TAILB) {
 			if (k < e) {
@@ -126,14 +127,14 @@ MODP_DEV void spmv_accumulate(Acc &acc, u32 k, u32 e, const int *__restrict__ ci
 				const u32 p0 = (u32)ci[k], p1 = (u32)ci[q1], p2 = (u32)ci[q2];
 				const W x0 = X[(size_t)(p0 & 0xFFFFFFu) * stride + xl], x1 = X[(size_t)(p1 & 0xFFFFFFu) * stride + xl];
 				const W x2 = X[(size_t)(p2 & 0xFFFFFFu) * stride + xl];
-				acc_mac32(acc, spal[p0 >> 24], x0);
-				acc_mac32(acc, k + 1 < e ? spal[p1 >> 24] : 0u, x1);
-				acc_mac32(acc, k + 2 < e ? spal[p2 >> 24] : 0u, x2);
+				acc_mac_val<SGN>(acc, spal[p0 >> 24], x0, p);
+				acc_mac_val<SGN>(acc, k + 1 < e ? spal[p1 >> 24] : 0u, x1, p);
+				acc_mac_val<SGN>(acc, k + 2 < e ? spal[p2 >> 24] : 0u, x2, p);
 			}
 		} else {
 			for (; k < e; k++) {
 				const u32 pk = (u32)ci[k];
-				acc_mac32(acc, spal[pk >> 24], X[(size_t)(pk & 0xFFFFFFu) * stride + xl]);
+				acc_mac_val<SGN>(acc, spal[pk >> 24], X[(size_t)(pk & 0xFFFFFFu) * stride + xl], p);
 			}
 		}
 	} else if (va) {
@@ -142,10 +143,10 @@ MODP_DEV void spmv_accumulate(Acc &acc, u32 k, u32 e, const int *__restrict__ ci
 			const u32 a0 = va[k], a1 = va[k + 1], a2 = va[k + 2], a3 = va[k + 3];
 			const W x0 = X[(size_t)c0 * stride + xl], x1 = X[(size_t)c1 * stride + xl];
 			const W x2 = X[(size_t)c2 * stride + xl], x3 = X[(size_t)c3 * stride + xl];
-			acc_mac32(acc, a0, x0);
-			acc_mac32(acc, a1, x1);
-			acc_mac32(acc, a2, x2);
-			acc_mac32(acc, a3, x3);
+			acc_mac_val<SGN>(acc, a0, x0, p);
+			acc_mac_val<SGN>(acc, a1, x1, p);
+			acc_mac_val<SGN>(acc, a2, x2, p);
+			acc_mac_val<SGN>(acc, a3, x3, p);
 		}
 		if (TAILB) {
 			if (k < e) {
@@ -154,13 +155,13 @@ MODP_DEV void spmv_accumulate(Acc &acc, u32 k, u32 e, const int *__restrict__ ci
 				const int c0 = ci[k], c1 = ci[q1], c2 = ci[q2];
 				const u32 a0 = va[k], a1 = va[q1], a2 = va[q2];
 				const W x0 = X[(size_t)c0 * stride + xl], x1 = X[(size_t)c1 * stride + xl], x2 = X[(size_t)c2 * stride + xl];
-				acc_mac32(acc, a0, x0);
-				acc_mac32(acc, k + 1 < e ? a1 : 0u, x1);
-				acc_mac32(acc, k + 2 < e ? a2 : 0u, x2);
+				acc_mac_val<SGN>(acc, a0, x0, p);
+				acc_mac_val<SGN>(acc, k + 1 < e ? a1 : 0u, x1, p);
+				acc_mac_val<SGN>(acc, k + 2 < e ? a2 : 0u, x2, p);
 			}
 		} else {
 			for (; k < e; k++)
-				acc_mac32(acc, va[k], X[(size_t)ci[k] * stride + xl]);
+				acc_mac_val<SGN>(acc, va[k], X[(size_t)ci[k] * stride + xl], p);
 		}
 	} else {
 		for (; k + 4 <= e; k += 4) {
@@ -207,9 +208,9 @@ MODP_DEV void acc_add_acc(Acc &a, u64 olo, u64 ohi)
  */
 
 /* all threads of the block: sum entries [k0, e0) over BLOCK/G slices; group 0 returns the 128-bit total */
-template <typename W, int G>
+template <typename W, int G, bool SGN = false>
 MODP_DEV Acc heavy_range_sum(u32 k0, u32 e0, const int *__restrict__ ci, const u32 *__restrict__ va, const u32 *spal,
-			     const W *__restrict__ X, int stride, int xl, Acc (*slices)[G])
+			     const W *__restrict__ X, int stride, int xl, Acc (*slices)[G], u64 p = 0)
 {
 	constexpr int GPB = BLOCK / G;
 	const int grp = threadIdx.x / G, lane = threadIdx.x & (G - 1);
@@ -217,7 +218,7 @@ MODP_DEV Acc heavy_range_sum(u32 k0, u32 e0, const int *__restrict__ ci, const u
 	const u32 lo = k0 + (u32)grp * per;
 	Acc acc;
 	acc_zero(acc);
-	spmv_accumulate<W>(acc, lo < e0 ? lo : e0, (lo + per) < e0 ? (lo + per) : e0, ci, va, spal, X, stride, xl);
+	spmv_accumulate<W, false, SGN>(acc, lo < e0 ? lo : e0, (lo + per) < e0 ? (lo + per) : e0, ci, va, spal, X, stride, xl, p);
 	slices[grp][lane] = acc;
 	__syncthreads();
 	if (grp == 0)
@@ -227,7 +228,7 @@ MODP_DEV Acc heavy_range_sum(u32 k0, u32 e0, const int *__restrict__ ci, const u
 	return acc;
 }
 
-template <typename W, int G, int MERS, bool DOT>
+template <typename W, int G, int MERS, bool DOT, bool SGN = false>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_heavy(const int *__restrict__ ci, const u32 *__restrict__ va, const u32 *__restrict__ pal,
 	     const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd, const HeavySeg *__restrict__ segs,
@@ -239,7 +240,7 @@ k_spmv_heavy_combine(const HeavyRow *__restrict__ mrows, int nm, const u64 *__re
 		     const W *__restrict__ Vd, int n, int accum, ModP m, u64 *__restrict__ partial, int slot0,
 		     const DevCtl *__restrict__ ctl);
 
-template <typename W, int G, int MERS, bool DOT>
+template <typename W, int G, int MERS, bool DOT, bool SGN = false>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_wave(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__restrict__ va,
 	    const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd,
@@ -276,9 +277,9 @@ static void heavy_fork(const KernelCfg &c, const DevCsr &A, hipStream_t s)
 		(void)hipEventRecord(c.ev_fork, s);
 }
 
-template <typename W, int G, int MERS, bool DOT>
-static void launch_heavy(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum, u64 *partial,
-			 int slot0, long long hb, const DevCtl *ctl, hipStream_t main_stream)
+template <typename W, int G, int MERS, bool DOT, bool SGN>
+static void launch_heavy_as(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum, u64 *partial,
+			    int slot0, long long hb, const DevCtl *ctl, hipStream_t main_stream)
 {
 	hipStream_t s = main_stream;
 	if (c.side) {
@@ -297,7 +298,7 @@ static void launch_heavy(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, 
 		}
 	} join{ c, s, main_stream };
 	if (hb)
-		hipLaunchKernelGGL((k_spmv_heavy<W, G, MERS, DOT>), dim3((unsigned)hb), dim3(BLOCK), 0, s, A.col_idx, A.val,
+		hipLaunchKernelGGL((k_spmv_heavy<W, G, MERS, DOT, SGN>), dim3((unsigned)hb), dim3(BLOCK), 0, s, A.col_idx, A.val,
 				   A.palette, X, Y, Vd, A.heavy, A.n_heavy, A.heavy_scratch, c.n, accum, c.m, partial, slot0, ctl);
 	const long long cb = A.n_multi ? combine_blocks(A, G) : 0;
 	if (cb)
@@ -305,12 +306,26 @@ static void launch_heavy(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, 
 				   0, s, A.heavy_multi, A.n_multi, A.heavy_scratch, Y, Vd, c.n, accum, c.m, partial,
 				   slot0 + (int)hb, ctl);
 	if (A.n_medium)
-		hipLaunchKernelGGL((k_spmv_wave<W, G, MERS, DOT>), dim3((unsigned)medium_blocks(c, A)), dim3(BLOCK), 0, s,
+		hipLaunchKernelGGL((k_spmv_wave<W, G, MERS, DOT, SGN>), dim3((unsigned)medium_blocks(c, A)), dim3(BLOCK), 0, s,
 				   A.row_ptr, A.col_idx, A.val, A.palette, X, Y, Vd, A.medium_rows, A.n_medium, c.n, accum, c.m,
 				   partial, slot0 + (int)(hb + cb), ctl);
 }
 
-template <typename W, int G, int MERS, bool TAILB>
+/* the signed instantiations exist for 64-bit words only (DevCsr::sgn is never set on a slab of 4-byte words) */
+template <typename W, int G, int MERS, bool DOT>
+static void launch_heavy(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum, u64 *partial,
+			 int slot0, long long hb, const DevCtl *ctl, hipStream_t main_stream)
+{
+	if constexpr (sizeof(W) == 8) {
+		if (A.sgn) {
+			launch_heavy_as<W, G, MERS, DOT, true>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
+			return;
+		}
+	}
+	launch_heavy_as<W, G, MERS, DOT, false>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
+}
+
+template <typename W, int G, int MERS, bool TAILB, bool SGN = false>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__restrict__ va,
        const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, long long rows, int n, int split_log2,
@@ -352,7 +367,7 @@ k_spmv(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__rest
 		}
 		Acc acc;
 		acc_zero(acc);
-		spmv_accumulate<W, TAILB>(acc, k, e, ci, va, spal, X, n, xl);
+		spmv_accumulate<W, TAILB, SGN>(acc, k, e, ci, va, spal, X, n, xl, m.p);
 		for (int off = G; off < (G << split_log2); off <<= 1)
 			acc_add_acc(acc, shfl_xor64(acc.lo, off), shfl_xor64(acc.hi, off));
 		if (lane < n && part == 0) {
@@ -587,16 +602,24 @@ static hipError_t spmv_dispatch(const KernelCfg &c, const DevCsr &A, const W *X,
 	if (g.xcd)
 		for (int x = 0; x < 9; x++)
 			xr.begin[x] = A.xr_rows[x];
+	const bool sgn = sizeof(W) == 8 && A.sgn;
+#define SPMV_GO(GG, TT, SS)                                                                                     \
+	hipLaunchKernelGGL((k_spmv<W, GG, MERS, TT, SS>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, A.row_ptr,          \
+			   A.col_idx, A.val, A.palette, X, Y, (long long)A.rows, c.n, split_log2, accum,                  \
+			   A.heavy_thr, c.m, xr, ctl)
 #define SPMV_CASE(GG)                                                                                           \
 	case GG:                                                                                                  \
-		if (A.tail_batch)                                                                                 \
-			hipLaunchKernelGGL((k_spmv<W, GG, MERS, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, A.row_ptr,  \
-					   A.col_idx, A.val, A.palette, X, Y, (long long)A.rows, c.n, split_log2, accum,   \
-					   A.heavy_thr, c.m, xr, ctl);                                                     \
+		if (sgn) {                                                                                        \
+			if constexpr (sizeof(W) == 8) {                                                           \
+				if (A.tail_batch)                                                                 \
+					SPMV_GO(GG, true, true);                                                  \
+				else                                                                              \
+					SPMV_GO(GG, false, true);                                                 \
+			}                                                                                         \
+		} else if (A.tail_batch)                                                                          \
+			SPMV_GO(GG, true, false);                                                                 \
 		else                                                                                              \
-			hipLaunchKernelGGL((k_spmv<W, GG, MERS, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, A.row_ptr, \
-					   A.col_idx, A.val, A.palette, X, Y, (long long)A.rows, c.n, split_log2, accum,   \
-					   A.heavy_thr, c.m, xr, ctl);                                                     \
+			SPMV_GO(GG, false, false);                                                                \
 		if (A.n_heavy || A.n_medium)                                                                      \
 			launch_heavy<W, GG, MERS, false>(c, A, X, Y, (const W *)nullptr, accum, (u64 *)nullptr, 0,   \
 							 g.hb, ctl, s);                                               \
@@ -613,6 +636,7 @@ static hipError_t spmv_dispatch(const KernelCfg &c, const DevCsr &A, const W *X,
 		return hipErrorInvalidValue;
 	}
 #undef SPMV_CASE
+#undef SPMV_GO
 	return hipGetLastError();
 }
 
@@ -907,7 +931,7 @@ k_block_dot_64(const W *__restrict__ V, const W *__restrict__ AV, long long rows
  * per lane cost more occupancy than the saved pass is worth (measured: 15.8 ms fused against 12.4 + 2.3 ms apart on
  * the config-5 shape), so that width runs k_spmv and k_block_dot_fast.
  */
-template <typename W, int MERS, int NT, bool TAILB>
+template <typename W, int MERS, int NT, bool TAILB, bool SGN = false>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_dot(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__restrict__ va,
 	   const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd,
@@ -941,7 +965,7 @@ k_spmv_dot(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__
 		const u64 vi = Vd[(size_t)r * NT + lane];
 		Acc acc;
 		acc_zero(acc);
-		spmv_accumulate<W, TAILB>(acc, k, e, ci, va, spal, X, NT, lane);
+		spmv_accumulate<W, TAILB, SGN>(acc, k, e, ci, va, spal, X, NT, lane, m.p);
 		if (accum)
 			acc_add(acc, Y[(size_t)r * NT + lane]);
 		const u64 y = acc_reduce<MERS>(acc, m);
@@ -955,7 +979,7 @@ k_spmv_dot(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__
  * A row that is one segment is finished here; the 128-bit sums of a split row go to `scratch` and
  * k_spmv_heavy_combine adds them.  DOT: the launches follow k_spmv_dot and add these rows' share of v^T Av and
  * Av^T Av as partial rows slot0 + blockIdx.x (n = G). */
-template <typename W, int G, int MERS, bool DOT>
+template <typename W, int G, int MERS, bool DOT, bool SGN>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_heavy(const int *__restrict__ ci, const u32 *__restrict__ va, const u32 *__restrict__ pal,
 	     const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd, const HeavySeg *__restrict__ segs,
@@ -980,7 +1004,7 @@ k_spmv_heavy(const int *__restrict__ ci, const u32 *__restrict__ va, const u32 *
 		ds.init();
 	for (int h = blockIdx.x; h < nseg; h += gridDim.x) {
 		const HeavySeg sg = segs[h];
-		Acc acc = heavy_range_sum<W, G>(sg.k0, sg.k1, ci, va, spal, X, n, xl, slices);
+		Acc acc = heavy_range_sum<W, G, SGN>(sg.k0, sg.k1, ci, va, spal, X, n, xl, slices, m.p);
 		if (threadIdx.x < G && lane < n) {
 			if (!sg.whole_row) {
 				scratch[((size_t)h * G + lane) * 2] = acc.lo;
@@ -1040,7 +1064,7 @@ k_spmv_heavy_combine(const HeavyRow *__restrict__ mrows, int nm, const u64 *__re
 /* Medium rows (longer than the outlier threshold, at most 256 entries per lane group of a wavefront): one wavefront
  * per row -- its 64/G lane groups each sum a slice, the slices are added across lanes, group 0 finishes the row.  A
  * workgroup per row (k_spmv_heavy) spends most of its time in barriers on rows of a few hundred entries. */
-template <typename W, int G, int MERS, bool DOT>
+template <typename W, int G, int MERS, bool DOT, bool SGN>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_wave(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__restrict__ va,
 	    const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd,
@@ -1069,7 +1093,7 @@ k_spmv_wave(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *_
 		const u32 per = (e0 - k0 + GPW - 1) / GPW, lo = k0 + (u32)grp * per;
 		Acc acc;
 		acc_zero(acc);
-		spmv_accumulate<W>(acc, lo < e0 ? lo : e0, (lo + per) < e0 ? (lo + per) : e0, ci, va, spal, X, n, xl);
+		spmv_accumulate<W, false, SGN>(acc, lo < e0 ? lo : e0, (lo + per) < e0 ? (lo + per) : e0, ci, va, spal, X, n, xl, m.p);
 #pragma unroll
 		for (int off = G; off < 64; off <<= 1)
 			acc_add_acc(acc, shfl_xor64(acc.lo, off), shfl_xor64(acc.hi, off));
@@ -1104,14 +1128,23 @@ static hipError_t spmv_dot_dispatch(const KernelCfg &c, const DevCsr &A, const W
 		for (int x = 0; x < 9; x++)
 			xr.begin[x] = A.xr_rows[x];
 	*nblocks = (int)(blocks + hb + cb + mb);
+	const bool sgn = sizeof(W) == 8 && A.sgn;
+#define SPMV_DOT_GO(NN, TT, SS)                                                                                      \
+	hipLaunchKernelGGL((k_spmv_dot<W, MERS, NN, TT, SS>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, A.row_ptr, A.col_idx, \
+			   A.val, A.palette, X, Y, Vd, (long long)A.rows, accum, A.heavy_thr, c.m, partial, xr, ctl)
 #define SPMV_DOT(NN)                                                                                                \
 	case NN:                                                                                                    \
-		if (A.tail_batch)                                                                                   \
-			hipLaunchKernelGGL((k_spmv_dot<W, MERS, NN, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, A.row_ptr, A.col_idx, \
-					   A.val, A.palette, X, Y, Vd, (long long)A.rows, accum, A.heavy_thr, c.m, partial, xr, ctl); \
+		if (sgn) {                                                                                          \
+			if constexpr (sizeof(W) == 8) {                                                             \
+				if (A.tail_batch)                                                                   \
+					SPMV_DOT_GO(NN, true, true);                                                \
+				else                                                                                \
+					SPMV_DOT_GO(NN, false, true);                                               \
+			}                                                                                           \
+		} else if (A.tail_batch)                                                                            \
+			SPMV_DOT_GO(NN, true, false);                                                               \
 		else                                                                                                \
-			hipLaunchKernelGGL((k_spmv_dot<W, MERS, NN, false>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, A.row_ptr, A.col_idx, \
-					   A.val, A.palette, X, Y, Vd, (long long)A.rows, accum, A.heavy_thr, c.m, partial, xr, ctl); \
+			SPMV_DOT_GO(NN, false, false);                                                              \
 		if (hb || mb)                                                                                       \
 			launch_heavy<W, NN, MERS, true>(c, A, X, Y, Vd, accum, partial, (int)blocks, hb, ctl, s);      \
 		break;
@@ -1124,6 +1157,7 @@ static hipError_t spmv_dot_dispatch(const KernelCfg &c, const DevCsr &A, const W
 		return hipErrorInvalidValue;
 	}
 #undef SPMV_DOT
+#undef SPMV_DOT_GO
 	return hipGetLastError();
 }
 
@@ -1171,12 +1205,16 @@ struct XcdTiles {
 	int interleave;		/* 1: tiles dealt round-robin over all wavefronts of the grid (no XCD ranges) */
 };
 
-template <typename W, int VALS, int U>
+/* LATE (the signed form with a value array only): a slot's value is read from LDS when its gathered word is consumed, not
+ * before the gathers are issued, so the U values are not live across them -- the signed fused kernel at G = 8 then fits the
+ * 128 VGPRs of its four workgroups per CU without scratch.  The unsigned forms keep their order. */
+template <typename W, int VALS, int U, bool SGN = false>
 MODP_DEV void staged_accumulate(Acc &acc, u32 i, u32 i1, const u32 *sci, const u32 *sva, const u32 *spal,
-				const W *__restrict__ X, int stride, int xl)
+				const W *__restrict__ X, int stride, int xl, u64 p = 0)
 {
 	/* every slot of a batch reads LDS and gathers unconditionally (a left-over slot re-reads the row's last entry:
 	 * same LDS word, same line of X) and is switched off by a zero multiplier: no branches inside the batch */
+	constexpr bool LATE = SGN && VALS == V_ARRAY;
 	const u32 last = i1 - 1;
 	for (; i < i1; i += U) {
 		u32 c[U];
@@ -1186,7 +1224,7 @@ MODP_DEV void staged_accumulate(Acc &acc, u32 i, u32 i1, const u32 *sci, const u
 		for (int j = 0; j < U; j++) {
 			const u32 at = i + j < i1 ? i + j : last;
 			c[j] = sci[at];
-			if (VALS == V_ARRAY)
+			if (VALS == V_ARRAY && !LATE)
 				a[j] = sva[at];
 		}
 #pragma unroll
@@ -1198,10 +1236,12 @@ MODP_DEV void staged_accumulate(Acc &acc, u32 i, u32 i1, const u32 *sci, const u
 #pragma unroll
 		for (int j = 0; j < U; j++) {
 			const bool live = i + j < i1;
+			if (LATE)
+				a[j] = sva[live ? i + j : last];
 			if (VALS == V_ONES)
 				acc_add(acc, live ? (u64)x[j] : 0ull);
 			else
-				acc_mac32(acc, live ? a[j] : 0u, x[j]);
+				acc_mac_val<SGN>(acc, live ? a[j] : 0u, x[j], p);
 		}
 	}
 }
@@ -1221,9 +1261,9 @@ MODP_DEV void staged_accumulate(Acc &acc, u32 i, u32 i1, const u32 *sci, const u
 /* The same batch with TWO adjacent words per lane (16-byte gathers: a 128-byte block row of n = 16 u64 words is 8 lanes,
  * a wavefront holds 8 rows instead of 4 and issues half the vector-memory instructions per row).  tools/ubench5: the
  * gather + output-row loop runs 5-9 % faster with 16 bytes per lane than with 8 (profiles/r03_ubench5_*.txt). */
-template <typename W, int VALS, int U>
+template <typename W, int VALS, int U, bool SGN = false>
 MODP_DEV void staged_accumulate2(Acc &a0, Acc &a1, u32 i, u32 i1, const u32 *sci, const u32 *sva, const u32 *spal,
-				 const W *__restrict__ X, int stride, int xw)
+				 const W *__restrict__ X, int stride, int xw, u64 p = 0)
 {
 	typedef W W2 __attribute__((ext_vector_type(2)));
 	const u32 last = i1 - 1;
@@ -1251,8 +1291,8 @@ MODP_DEV void staged_accumulate2(Acc &a0, Acc &a1, u32 i, u32 i1, const u32 *sci
 				acc_add(a0, live ? (u64)x[j].x : 0ull);
 				acc_add(a1, live ? (u64)x[j].y : 0ull);
 			} else {
-				acc_mac32(a0, live ? a[j] : 0u, x[j].x);
-				acc_mac32(a1, live ? a[j] : 0u, x[j].y);
+				acc_mac_val<SGN>(a0, live ? a[j] : 0u, x[j].x, p);
+				acc_mac_val<SGN>(a1, live ? a[j] : 0u, x[j].y, p);
 			}
 		}
 	}
@@ -1260,7 +1300,7 @@ MODP_DEV void staged_accumulate2(Acc &a0, Acc &a1, u32 i, u32 i1, const u32 *sci
 
 /* WPL = words per lane: 1 (a group of G lanes owns a block row of up to G words) or 2 (the row is 2 G words, 16-byte
  * gathers and stores; n = 2 G exactly, no fused inner products, lockstep rows) */
-template <typename W, int G, int MERS, bool DOT, int VALS, int U, bool DYN = false, int WPL = 1>
+template <typename W, int G, int MERS, bool DOT, int VALS, int U, bool DYN = false, int WPL = 1, bool SGN = false>
 __global__ void __launch_bounds__(BLOCK, (DOT && G >= 8) ? 4 : 1)	/* the fused form at n = 8 must keep 4 workgroups per CU (<= 128 VGPRs) */
 k_spmv_staged(const u32 *__restrict__ rp, const u32 *__restrict__ ci, const u32 *__restrict__ va,
 	      const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd,
@@ -1269,6 +1309,7 @@ k_spmv_staged(const u32 *__restrict__ rp, const u32 *__restrict__ ci, const u32 
 {
 	static_assert(!(DYN && DOT), "the dynamic form has no fused inner products (yet)");
 	static_assert(WPL == 1 || (WPL == 2 && !DOT && !DYN && sizeof(W) == 8), "two words per lane: plain lockstep form, 64-bit words");
+	static_assert(!SGN || (sizeof(W) == 8 && VALS != V_ONES), "signed values: 64-bit words, a slab that carries values");
 	if (ctl->stop)
 		return;
 	constexpr int GPW = 64 / G, NS = VALS == V_ARRAY ? 2 : 1, WAVES = BLOCK / 64, NT = DOT ? G : 1;
@@ -1279,7 +1320,10 @@ k_spmv_staged(const u32 *__restrict__ rp, const u32 *__restrict__ ci, const u32 
 	if (VALS == V_PACKED)
 		spal_store[threadIdx.x] = pal[threadIdx.x];
 	__syncthreads();
-	const int t = threadIdx.x, wl = t & 63, wave = t >> 6, lane = wl & (G - 1), grp = wl / G;
+	const int t = threadIdx.x, wl = t & 63, lane = wl & (G - 1), grp = wl / G;
+	/* (the signed instantiations tell the compiler that the wavefront's number is uniform: the tile counters and the staging
+	 * address then live in scalar registers, which pays for the registers the sign handling takes) */
+	const int wave = SGN ? __builtin_amdgcn_readfirstlane(t >> 6) : t >> 6;
 	const int xl = lane < n ? lane : 0, gbase = wl - lane;
 	u32 *const mine = stage + (size_t)wave * 2 * NS * capw;
 	const int TR = tile_rows, rpg = TR / GPW;	/* lockstep form: TR = GPW * rows per group */
@@ -1393,10 +1437,10 @@ k_spmv_staged(const u32 *__restrict__ rp, const u32 *__restrict__ ci, const u32 
 				if (grow >= 0 && gi < ge) {
 					const u32 stop_at = gi + U < ge ? gi + U : ge;
 					if (ge <= (u32)capw)
-						staged_accumulate<W, VALS, U>(acc, gi, stop_at, sci, sva, spal_store, X, n, xl);
+						staged_accumulate<W, VALS, U, SGN>(acc, gi, stop_at, sci, sva, spal_store, X, n, xl, m.p);
 					else		/* the row runs past the staged window: its entries come from global memory */
-						spmv_accumulate<W>(acc, K0 + gi, K0 + stop_at, (const int *)ci, VALS == V_ARRAY ? va : nullptr,
-								   VALS == V_PACKED ? spal_store : nullptr, X, n, xl);
+						spmv_accumulate<W, false, SGN>(acc, K0 + gi, K0 + stop_at, (const int *)ci, VALS == V_ARRAY ? va : nullptr,
+									       VALS == V_PACKED ? spal_store : nullptr, X, n, xl, m.p);
 					gi = stop_at;
 				}
 			}
@@ -1414,7 +1458,7 @@ k_spmv_staged(const u32 *__restrict__ rp, const u32 *__restrict__ ci, const u32 
 					acc_zero(acc);
 					acc_zero(acc1);
 					if (e - K0 <= (u32)capw) {
-						staged_accumulate2<W, VALS, U>(acc, acc1, k - K0, e - K0, sci, sva, spal_store, X, n, 2 * lane);
+						staged_accumulate2<W, VALS, U, SGN>(acc, acc1, k - K0, e - K0, sci, sva, spal_store, X, n, 2 * lane, m.p);
 					} else {	/* the row runs past the staged window: its entries come from global memory */
 						for (u32 q = k; q < e; q++) {
 							const u32 cw = ci[q];
@@ -1424,8 +1468,8 @@ k_spmv_staged(const u32 *__restrict__ rp, const u32 *__restrict__ ci, const u32 
 								acc_add(acc1, (u64)xv.y);
 							} else {
 								const u32 av = VALS == V_PACKED ? spal_store[cw >> 24] : va[q];
-								acc_mac32(acc, av, xv.x);
-								acc_mac32(acc1, av, xv.y);
+								acc_mac_val<SGN>(acc, av, xv.x, m.p);
+								acc_mac_val<SGN>(acc1, av, xv.y, m.p);
 							}
 						}
 					}
@@ -1452,10 +1496,10 @@ k_spmv_staged(const u32 *__restrict__ rp, const u32 *__restrict__ ci, const u32 
 				if (DOT)
 					vi = Vd[(size_t)r * NT + lane];
 				if (e - K0 <= (u32)capw)
-					staged_accumulate<W, VALS, U>(acc, k - K0, e - K0, sci, sva, spal_store, X, n, xl);
+					staged_accumulate<W, VALS, U, SGN>(acc, k - K0, e - K0, sci, sva, spal_store, X, n, xl, m.p);
 				else
-					spmv_accumulate<W>(acc, k, e, (const int *)ci, VALS == V_ARRAY ? va : nullptr,
-							   VALS == V_PACKED ? spal_store : nullptr, X, n, xl);
+					spmv_accumulate<W, false, SGN>(acc, k, e, (const int *)ci, VALS == V_ARRAY ? va : nullptr,
+								       VALS == V_PACKED ? spal_store : nullptr, X, n, xl, m.p);
 				if (lane < n) {
 					if (accum)
 						acc_add(acc, Y[(size_t)r * n + lane]);
@@ -1614,7 +1658,7 @@ void spmv_plan_staged(const KernelCfg &c, const u32 *row_ptr, DevCsr &D, bool al
 	D.st_ok = true;
 }
 
-template <typename W, int MERS, bool DOT, int G, int VALS>
+template <typename W, int MERS, bool DOT, int G, int VALS, bool SGN = false>
 static void staged_launch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum, u64 *partial,
 			  long long blocks, const DevCtl *ctl, hipStream_t s)
 {
@@ -1625,13 +1669,13 @@ static void staged_launch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y,
 	const size_t lds = (size_t)(BLOCK / 64) * 2 * A.st_ns * A.st_capw * sizeof(u32);
 	const bool deep = staged_gathers(c, A, G, DOT, sizeof(W) == 8) == 8;	/* gathers in flight per lane: 8 or 4 */
 #define STAGED_GO(UU, DD)                                                                                              \
-	hipLaunchKernelGGL((k_spmv_staged<W, G, MERS, DOT, VALS, UU, DD>), dim3((unsigned)blocks), dim3(BLOCK), lds, s, A.row_ptr, \
+	hipLaunchKernelGGL((k_spmv_staged<W, G, MERS, DOT, VALS, UU, DD, 1, SGN>), dim3((unsigned)blocks), dim3(BLOCK), lds, s, A.row_ptr, \
 			   (const u32 *)A.col_idx, A.val, A.palette, X, Y, Vd, (long long)A.rows, c.n, A.st_tr, A.st_capw, accum, \
 			   A.heavy_thr, c.m, partial, xt, ctl)
 	if constexpr ((G == 16 || G == 8) && !DOT && sizeof(W) == 8) {
 		if (A.st_pair) {	/* G / 2 lanes of two words per row */
 #define STAGED_PAIR(UU)                                                                                                 \
-	hipLaunchKernelGGL((k_spmv_staged<W, G / 2, MERS, false, VALS, UU, false, 2>), dim3((unsigned)blocks), dim3(BLOCK), lds, s, \
+	hipLaunchKernelGGL((k_spmv_staged<W, G / 2, MERS, false, VALS, UU, false, 2, SGN>), dim3((unsigned)blocks), dim3(BLOCK), lds, s, \
 			   A.row_ptr, (const u32 *)A.col_idx, A.val, A.palette, X, Y, Vd, (long long)A.rows, c.n, A.st_tr, A.st_capw, \
 			   accum, A.heavy_thr, c.m, partial, xt, ctl)
 			if (deep)
@@ -1670,9 +1714,17 @@ static hipError_t staged_dispatch(const KernelCfg &c, const DevCsr &A, const W *
 	if (DOT)
 		*nblocks = (int)(blocks + hb + g.cb + g.mb);
 	const int vals = A.palette ? V_PACKED : (A.val ? V_ARRAY : V_ONES);
+	const bool sgn = sizeof(W) == 8 && A.sgn && vals != V_ONES;
 #define STAGED_G(GG)                                                                                              \
 	case GG:                                                                                                  \
-		if (vals == V_PACKED)                                                                             \
+		if (sgn) {                                                                                        \
+			if constexpr (sizeof(W) == 8) {                                                           \
+				if (vals == V_PACKED)                                                             \
+					staged_launch<W, MERS, DOT, GG, V_PACKED, true>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
+				else                                                                              \
+					staged_launch<W, MERS, DOT, GG, V_ARRAY, true>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
+			}                                                                                         \
+		} else if (vals == V_PACKED)                                                                      \
 			staged_launch<W, MERS, DOT, GG, V_PACKED>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
 		else if (vals == V_ARRAY)                                                                         \
 			staged_launch<W, MERS, DOT, GG, V_ARRAY>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s);  \
@@ -1724,7 +1776,7 @@ static hipError_t staged_dispatch(const KernelCfg &c, const DevCsr &A, const W *
 #define PBLOCK 1024
 #define PANEL_BYTES (128 * 1024)
 
-template <typename W, int G, int MERS, bool DOT, int VALS>
+template <typename W, int G, int MERS, bool DOT, int VALS, bool SGN = false>
 __global__ void __launch_bounds__(PBLOCK)
 k_spmv_panel(const u32 *__restrict__ rp, const u32 *__restrict__ ci, const u32 *__restrict__ va,
 	     const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd, int accum,
@@ -1792,7 +1844,7 @@ k_spmv_panel(const u32 *__restrict__ rp, const u32 *__restrict__ ci, const u32 *
 				if (VALS == V_ONES)
 					acc_add(acc, a[j] ? (u64)x[j] : 0ull);
 				else
-					acc_mac32(acc, a[j], x[j]);
+					acc_mac_val<SGN>(acc, a[j], x[j], m.p);
 			}
 		}
 		if (accum)
@@ -1852,7 +1904,7 @@ void spmv_plan_panel(const KernelCfg &c, const u32 *row_ptr, DevCsr &D, int64_t 
 			D.xr_rows[0] = -1;
 }
 
-template <typename W, int MERS, bool DOT, int G, int VALS>
+template <typename W, int MERS, bool DOT, int G, int VALS, bool SGN = false>
 static void panel_launch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum, u64 *partial,
 			 long long blocks, const DevCtl *ctl, hipStream_t s)
 {
@@ -1860,7 +1912,7 @@ static void panel_launch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, 
 	for (int x = 0; x < 9; x++)
 		xr.begin[x] = A.xr_rows[0] < 0 ? A.rows * x / 8 : A.xr_rows[x];
 	const size_t lds = (size_t)A.panel_rows * G * sizeof(W);
-	auto kern = k_spmv_panel<W, G, MERS, DOT, VALS>;
+	auto kern = k_spmv_panel<W, G, MERS, DOT, VALS, SGN>;
 	static std::atomic<bool> attr_set[64];	/* per instantiation and per device; several threads may ask (setting it twice is harmless) */
 	int dev = 0;
 	(void)hipGetDevice(&dev);
@@ -1886,9 +1938,17 @@ static hipError_t panel_dispatch(const KernelCfg &c, const DevCsr &A, const W *X
 		*nblocks = (int)(blocks + hb + g.cb + g.mb);
 	}
 	const int vals = A.palette ? V_PACKED : (A.val ? V_ARRAY : V_ONES);
+	const bool sgn = sizeof(W) == 8 && A.sgn && vals != V_ONES;
 #define PANEL_G(GG)                                                                                              \
 	case GG:                                                                                                 \
-		if (vals == V_PACKED)                                                                            \
+		if (sgn) {                                                                                       \
+			if constexpr (sizeof(W) == 8) {                                                          \
+				if (vals == V_PACKED)                                                            \
+					panel_launch<W, MERS, DOT, GG, V_PACKED, true>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
+				else                                                                             \
+					panel_launch<W, MERS, DOT, GG, V_ARRAY, true>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
+			}                                                                                        \
+		} else if (vals == V_PACKED)                                                                     \
 			panel_launch<W, MERS, DOT, GG, V_PACKED>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
 		else if (vals == V_ARRAY)                                                                        \
 			panel_launch<W, MERS, DOT, GG, V_ARRAY>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s);  \

@@ -59,7 +59,8 @@ static int next_line(cursor *c, char *buf, size_t cap)
 	return 0;
 }
 
-static inline int next_int(cursor *c, long long *out)
+/* `wide` (may be NULL) is set when the digits ran past 2^40: the value is then no int32 whatever it wrapped to */
+static inline int next_int_wide(cursor *c, long long *out, int *wide)
 {
 	const char *p = c->p, *end = c->end;
 	while (p < end && (*p == ' ' || *p == '\n' || *p == '\t' || *p == '\r' || *p == '\v' || *p == '\f'))
@@ -74,11 +75,27 @@ static inline int next_int(cursor *c, long long *out)
 	if (p >= end || *p < '0' || *p > '9')
 		return -1;
 	unsigned long long acc = 0;
-	while (p < end && *p >= '0' && *p <= '9')
+	int big = 0;
+	while (p < end && *p >= '0' && *p <= '9') {
+		big |= acc > (1ull << 40);
 		acc = acc * 10 + (unsigned)(*p++ - '0');
+	}
 	*out = neg ? -(long long)acc : (long long)acc;
+	if (wide)
+		*wide = big;
 	c->p = p;
 	return 0;
+}
+
+static inline int next_int(cursor *c, long long *out)
+{
+	return next_int_wide(c, out, NULL);
+}
+
+/* signed value mode (blz_mm_load_signed): the entry must be an int32; it is stored as its bit pattern */
+static inline int fits_int32(long long v, int wide)
+{
+	return !wide && v >= INT32_MIN && v <= INT32_MAX;
 }
 
 static inline int is_blank(char ch)
@@ -92,7 +109,7 @@ static inline int is_blank(char ch)
  * tokens was a plain in-range integer; anything else returns 1 WITHOUT an error message and the caller re-reads
  * the file with the sequential reader, which defines the behaviour on irregular input. */
 static int parse_entries_parallel(const char *p, const char *end, long long nr, long long nc, long long nz,
-				  uint64_t prime, blz_coo *out)
+				  uint64_t prime, int sgn, blz_coo *out)
 {
 	int T = omp_get_max_threads();
 	if (T > 64)
@@ -142,8 +159,11 @@ static int parse_entries_parallel(const char *p, const char *end, long long nr, 
 				break;
 			}
 			unsigned long long acc = 0;
-			while (q < stop && *q >= '0' && *q <= '9')
+			int wide = 0;
+			while (q < stop && *q >= '0' && *q <= '9') {
+				wide |= acc > (1ull << 40);
 				acc = acc * 10 + (unsigned)(*q++ - '0');
+			}
 			if (q < stop && !is_blank(*q)) {
 				bad = 1;
 				break;
@@ -159,7 +179,12 @@ static int parse_entries_parallel(const char *p, const char *end, long long nr, 
 				out->j[u] = (int32_t)(val - 1);
 				break;
 			default:	/* sequential/lanczos_modp.c:238-243: "%d" into a u32, then % prime */
-				out->x[u] = (uint32_t)((uint64_t)(uint32_t)(int32_t)val % prime);
+				if (sgn) {	/* the bit pattern; an entry outside int32 goes to the sequential reader, which names it */
+					bad = !fits_int32(val, wide);
+					out->x[u] = (uint32_t)(int32_t)val;
+				} else {
+					out->x[u] = (uint32_t)((uint64_t)(uint32_t)(int32_t)val % prime);
+				}
 			}
 			g++;
 		}
@@ -200,10 +225,9 @@ static int check_banner(const char *line, int want_array)
 	return BLZ_OK;
 }
 
-int blz_mm_load(const char *path, uint64_t prime, blz_coo *out)
+/* sgn != 0: signed value mode -- `prime` is not used, the value field is kept as the int32's bit pattern */
+static int mm_load(const char *path, uint64_t prime, int sgn, blz_coo *out)
 {
-	if (!path || !out || prime < 2)
-		return blz_fail(BLZ_EINVAL, "blz_mm_load: bad argument");
 	memset(out, 0, sizeof *out);
 	int fd = open(path, O_RDONLY);
 	if (fd < 0)
@@ -255,7 +279,7 @@ int blz_mm_load(const char *path, uint64_t prime, blz_coo *out)
 		blz_coo_free(out);
 		return blz_fail(BLZ_ENOMEM, "Cannot allocate sparse matrix");
 	}
-	if (nz >= 200000 && parse_entries_parallel(c.p, c.end, nr, nc, nz, prime, out) == 0) {
+	if (nz >= 200000 && parse_entries_parallel(c.p, c.end, nr, nc, nz, prime, sgn, out) == 0) {
 		munmap(base, (size_t)st.st_size);
 		return BLZ_OK;
 	}
@@ -263,7 +287,8 @@ int blz_mm_load(const char *path, uint64_t prime, blz_coo *out)
 	 * together): the one-token-at-a-time reader below is the definition, and it names the offending entry */
 	for (long long u = 0; u < nz; u++) {
 		long long a, b, v;
-		if (next_int(&c, &a) || next_int(&c, &b) || next_int(&c, &v)) {
+		int wide = 0;
+		if (next_int(&c, &a) || next_int(&c, &b) || next_int_wide(&c, &v, &wide)) {
 			munmap(base, (size_t)st.st_size);
 			blz_coo_free(out);
 			return blz_fail(BLZ_EIO, "parse error entry %lld", u);
@@ -275,11 +300,34 @@ int blz_mm_load(const char *path, uint64_t prime, blz_coo *out)
 		}
 		out->i[u] = (int32_t)(a - 1);	/* MatrixMarket is 1-based, :241-242 */
 		out->j[u] = (int32_t)(b - 1);
+		if (sgn) {
+			if (!fits_int32(v, wide)) {
+				munmap(base, (size_t)st.st_size);
+				blz_coo_free(out);
+				return blz_fail(BLZ_EIO, "entry %lld: the value does not fit an int32 (signed value mode)", u);
+			}
+			out->x[u] = (uint32_t)(int32_t)v;
+			continue;
+		}
 		/* :238-243: "%d" into a u32, then % prime */
 		out->x[u] = (uint32_t)((uint64_t)(uint32_t)(int32_t)v % prime);
 	}
 	munmap(base, (size_t)st.st_size);
 	return BLZ_OK;
+}
+
+int blz_mm_load(const char *path, uint64_t prime, blz_coo *out)
+{
+	if (!path || !out || prime < 2)
+		return blz_fail(BLZ_EINVAL, "blz_mm_load: bad argument");
+	return mm_load(path, prime, 0, out);
+}
+
+int blz_mm_load_signed(const char *path, blz_coo *out)
+{
+	if (!path || !out)
+		return blz_fail(BLZ_EINVAL, "blz_mm_load_signed: bad argument");
+	return mm_load(path, 0, 1, out);
 }
 
 int blz_mm_save_coo(const char *path, const blz_coo *M)
@@ -2022,13 +2070,26 @@ int blz_save_block(const char *path, int64_t nrows, int n, const uint64_t *v)
 
 /* ------------------------------------------------------------------------ kernel checker */
 
-int blz_check_kernel(const char *matrix_path, const char *kernel_path, uint64_t prime, int right, int64_t *bad_row,
-		     int *bad_col)
+/*
+ * Signed value mode on the host: the entry a (an int32 kept as its bit pattern) stands for a mod p.  A product a * x is
+ * summed as |a| * x' with x' = (a < 0) ? p - x : x -- the rule of acc_mac_signed (csrc/modp.h).  |a| <= 2^31 and
+ * x' <= p < 2^62 (x' = p when x = 0: not canonical, still the right residue), so a term is below 2^93 and the unreduced
+ * 128-bit sums hold 2^35 terms, more than the 2^34 entries per row or column the unsigned checkers already assume.
+ */
+static inline unsigned __int128 host_term(uint32_t a, uint64_t x, uint64_t prime, int sgn)
 {
-	if (!matrix_path || !kernel_path || prime < 2)
+	if (sgn && (int32_t)a < 0)
+		return (unsigned __int128)(0u - a) * (prime - x);
+	return (unsigned __int128)a * x;
+}
+
+static int check_kernel(const char *matrix_path, const char *kernel_path, uint64_t prime, int right, int64_t *bad_row,
+			int *bad_col, int sgn)
+{
+	if (!matrix_path || !kernel_path || prime < 2 || (sgn && prime >= (1ull << 62)))
 		return blz_fail(BLZ_EINVAL, "blz_check_kernel: bad argument");
 	blz_coo M;
-	int rc = blz_mm_load(matrix_path, prime, &M);
+	int rc = sgn ? blz_mm_load_signed(matrix_path, &M) : blz_mm_load(matrix_path, prime, &M);
 	if (rc != BLZ_OK)
 		return rc;
 	const int64_t nrows = right ? M.ncols : M.nrows, ncols = right ? M.nrows : M.ncols;	/* :99-104 */
@@ -2102,9 +2163,9 @@ int blz_check_kernel(const char *matrix_path, const char *kernel_path, uint64_t 
 	/* unreduced 128-bit sums, one reduction per word: value < 2^32, x < 2^62, nnz per column < 2^34 */
 	for (int64_t u = 0; u < M.nnz; u++) {
 		const int64_t i = right ? M.j[u] : M.i[u], j = right ? M.i[u] : M.j[u];
-		const uint64_t v = M.x[u];
+		const uint32_t v = M.x[u];
 		for (long long k = 0; k < n; k++)
-			y[j * n + k] += (unsigned __int128)v * x[i * n + k];
+			y[j * n + k] += host_term(v, x[i * n + k], prime, sgn);
 	}
 	for (int64_t j = 0; j < ncols && rc == BLZ_OK; j++)
 		for (long long k = 0; k < n; k++)
@@ -2122,6 +2183,18 @@ done:
 	munmap(base, (size_t)st.st_size);
 	blz_coo_free(&M);
 	return rc;
+}
+
+int blz_check_kernel(const char *matrix_path, const char *kernel_path, uint64_t prime, int right, int64_t *bad_row,
+		     int *bad_col)
+{
+	return check_kernel(matrix_path, kernel_path, prime, right, bad_row, bad_col, 0);
+}
+
+int blz_check_kernel_signed(const char *matrix_path, const char *kernel_path, uint64_t prime, int right, int64_t *bad_row,
+			    int *bad_col)
+{
+	return check_kernel(matrix_path, kernel_path, prime, right, bad_row, bad_col, 1);
 }
 
 /* ---------------------------------------------------------------- right-hand sides and solutions */
@@ -2208,13 +2281,13 @@ int blz_rhs_load(const char *path, uint64_t prime, int64_t len, uint64_t *b)
 	return load_column(path, prime, len, 1, b);
 }
 
-int blz_check_solution(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
-		       int64_t *bad_row)
+static int check_solution(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+			  int64_t *bad_row, int sgn)
 {
 	if (!matrix_path || !rhs_path || !x_path || prime < 2 || prime >= (1ull << 62))
 		return blz_fail(BLZ_EINVAL, "blz_check_solution: bad argument");
 	blz_coo M;
-	int rc = blz_mm_load(matrix_path, prime, &M);
+	int rc = sgn ? blz_mm_load_signed(matrix_path, &M) : blz_mm_load(matrix_path, prime, &M);
 	if (rc != BLZ_OK)
 		return rc;
 	const int64_t xlen = right ? M.ncols : M.nrows, blen = right ? M.nrows : M.ncols;
@@ -2230,7 +2303,7 @@ int blz_check_solution(const char *matrix_path, const char *rhs_path, const char
 		/* unreduced 128-bit sums, one reduction per word: value < 2^32, x < 2^62, entries per row or column < 2^34 */
 		for (int64_t u = 0; u < M.nnz; u++) {
 			const int64_t i = right ? M.j[u] : M.i[u], j = right ? M.i[u] : M.j[u];
-			y[j] += (unsigned __int128)M.x[u] * x[i];
+			y[j] += host_term(M.x[u], x[i], prime, sgn);
 		}
 		for (int64_t j = 0; j < blen; j++)
 			if ((uint64_t)(y[j] % prime) != b[j]) {
@@ -2245,6 +2318,18 @@ int blz_check_solution(const char *matrix_path, const char *rhs_path, const char
 	free(y);
 	blz_coo_free(&M);
 	return rc;
+}
+
+int blz_check_solution(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+		       int64_t *bad_row)
+{
+	return check_solution(matrix_path, rhs_path, x_path, prime, right, bad_row, 0);
+}
+
+int blz_check_solution_signed(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+			      int64_t *bad_row)
+{
+	return check_solution(matrix_path, rhs_path, x_path, prime, right, bad_row, 1);
 }
 
 /* A len x k "array integer general" file, column-major, into out[r * k + i] (row-major), 1 <= k <= kmax; entries as in
@@ -2380,13 +2465,13 @@ int blz_rhs_cut(const uint64_t *b, int64_t len, int k, int kp, uint64_t prime, c
 	return BLZ_OK;
 }
 
-int blz_check_solution_block(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
-			     int *status, int64_t *bad_row)
+static int check_solution_block(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+				int *status, int64_t *bad_row, int sgn)
 {
 	if (!matrix_path || !rhs_path || !x_path || !status || prime < 2 || prime >= (1ull << 62))
 		return blz_fail(BLZ_EINVAL, "blz_check_solution_block: bad argument");
 	blz_coo M;
-	int rc = blz_mm_load(matrix_path, prime, &M);
+	int rc = sgn ? blz_mm_load_signed(matrix_path, &M) : blz_mm_load(matrix_path, prime, &M);
 	if (rc != BLZ_OK)
 		return rc;
 	const int64_t xlen = right ? M.ncols : M.nrows, blen = right ? M.nrows : M.ncols;
@@ -2413,7 +2498,7 @@ int blz_check_solution_block(const char *matrix_path, const char *rhs_path, cons
 	for (int64_t u = 0; u < M.nnz; u++) {
 		const int64_t i = right ? M.j[u] : M.i[u], j = right ? M.i[u] : M.j[u];
 		for (int t = 0; t < k; t++)
-			y[j * k + t] += (unsigned __int128)M.x[u] * x[i * k + t];
+			y[j * k + t] += host_term(M.x[u], x[i * k + t], prime, sgn);
 	}
 	for (int t = 0; t < k; t++) {
 		int zero = 1;
@@ -2437,6 +2522,18 @@ done:
 	free(y);
 	blz_coo_free(&M);
 	return rc;
+}
+
+int blz_check_solution_block(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+			     int *status, int64_t *bad_row)
+{
+	return check_solution_block(matrix_path, rhs_path, x_path, prime, right, status, bad_row, 0);
+}
+
+int blz_check_solution_block_signed(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime,
+				    int right, int *status, int64_t *bad_row)
+{
+	return check_solution_block(matrix_path, rhs_path, x_path, prime, right, status, bad_row, 1);
 }
 
 /* rank of a kernel block: the RREF of its row space, row by row (the GPU's k_rref restated), stopping at full rank */

@@ -6,6 +6,8 @@
  * --rhs FILE (no reference counterpart) checks a solution instead: --kernel names the file of x, and M*x == b (--right)
  * or x*M == b (--left) is asked for the vector b of FILE.  With k > 1 columns in FILE, --kernel holds the k columns of x and
  * each is checked against its own b; an all-zero column of x stands for a system that was not solved and does not fail.
+ * --signed (no reference counterpart) reads the matrix in signed value mode: an entry a (an int32) means a mod P, as
+ * lanczos_modp --signed solves it.
  */
 #define _GNU_SOURCE
 #include <err.h>
@@ -21,11 +23,11 @@ int main(int argc, char **argv)
 		{"matrix", required_argument, NULL, 'm'}, {"kernel", required_argument, NULL, 'k'},
 		{"prime", required_argument, NULL, 'p'}, {"right", no_argument, NULL, 'r'},
 		{"left", no_argument, NULL, 'l'}, {"independent", no_argument, NULL, 'i'},
-		{"rhs", required_argument, NULL, 'b'}, {NULL, 0, NULL, 0}
+		{"rhs", required_argument, NULL, 'b'}, {"signed", no_argument, NULL, 's'}, {NULL, 0, NULL, 0}
 	};
 	char *matrix = NULL, *kernel = NULL, *rhs = NULL;
 	unsigned long long prime = 0;
-	int right = 0, independent = 0, ch;
+	int right = 0, independent = 0, sgn = 0, ch;
 	while ((ch = getopt_long(argc, argv, "", longopts, NULL)) != -1) {
 		switch (ch) {
 		case 'm': matrix = optarg; break;
@@ -35,6 +37,7 @@ int main(int argc, char **argv)
 		case 'l': right = 0; break;
 		case 'i': independent = 1; break;
 		case 'b': rhs = optarg; break;
+		case 's': sgn = 1; break;
 		default: errx(1, "Unknown option\n");
 		}
 	}
@@ -49,6 +52,8 @@ int main(int argc, char **argv)
 		printf("--independent               also check that the kernel vectors are linearly independent\n");
 		printf("--rhs FILENAME              check a solution: --kernel holds x, FILENAME holds b, and M*x == b (--right)\n");
 		printf("                            or x*M == b (--left) is verified\n");
+		printf("--signed                    signed value mode: a matrix entry a (an int32) means a mod P, so -1 is P-1\n");
+		printf("                            (what lanczos_modp --signed solves; P < 2**62)\n");
 		exit(0);
 	}
 	if (rhs) {
@@ -58,7 +63,8 @@ int main(int argc, char **argv)
 		if (k > 1) {
 			int status[BLZ_MAX_RHS], failed = 0;
 			int64_t bad_row[BLZ_MAX_RHS];
-			const int kk = blz_check_solution_block(matrix, rhs, kernel, prime, right, status, bad_row);
+			const int kk = sgn ? blz_check_solution_block_signed(matrix, rhs, kernel, prime, right, status, bad_row)
+					   : blz_check_solution_block(matrix, rhs, kernel, prime, right, status, bad_row);
 			if (kk < 0)
 				errx(1, "%s", blz_last_error());
 			for (int i = 0; i < kk; i++) {
@@ -73,7 +79,8 @@ int main(int argc, char **argv)
 			exit(failed ? EXIT_FAILURE : EXIT_SUCCESS);
 		}
 		int64_t bad = 0;
-		const int rcs = blz_check_solution(matrix, rhs, kernel, prime, right, &bad);
+		const int rcs = sgn ? blz_check_solution_signed(matrix, rhs, kernel, prime, right, &bad)
+				    : blz_check_solution(matrix, rhs, kernel, prime, right, &bad);
 		if (rcs == 0) {
 			printf("OK\n");
 			exit(EXIT_SUCCESS);
@@ -87,7 +94,8 @@ int main(int argc, char **argv)
 	printf("Reading Matrix from %s and kernel from %s\n", matrix, kernel);
 	long long row = 0;
 	int col = 0;
-	const int rc = blz_check_kernel(matrix, kernel, prime, right, (int64_t *)&row, &col);
+	const int rc = sgn ? blz_check_kernel_signed(matrix, kernel, prime, right, (int64_t *)&row, &col)
+			   : blz_check_kernel(matrix, kernel, prime, right, (int64_t *)&row, &col);
 	if (rc == 0) {
 		printf("OK\n");
 		if (independent) {

@@ -29,7 +29,7 @@
 static long n = 1;
 static uint64_t prime;
 static char *matrix_filename, *kernel_filename, *rhs_filename;
-static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis, rhs_gpus_given;
+static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis, rhs_gpus_given, values_signed;
 static int stop_after = -1, checkpoint_timer = 60, device, gpus = 1, rhs_gpus;
 
 static double wtime(void)
@@ -81,6 +81,11 @@ static void usage(char **argv)
 	printf("                            output has k columns, zero where a system has no solution\n");
 	printf("--rhs-gpus G                with --rhs: row-partition the bordered matrix over G GPUs, as --gpus G does for a plain\n");
 	printf("                            run (the border's k x N words are all-reduced once more per iteration)\n");
+	printf("--signed                    signed value mode: a matrix entry a (an int32; anything wider is an error) means the\n");
+	printf("                            residue a mod P, so -1 is P-1.  Without it an entry goes through a u32 as in the\n");
+	printf("                            reference, and -1 is (2**32 - 1) mod P.  Works with every other option; check the\n");
+	printf("                            result with checker_modp --signed.  A checkpoint holds v and p, not the matrix: the\n");
+	printf("                            mode is NOT recorded in it, so give --load-checkpoint the flag the first run had\n");
 	printf("--device D                  first HIP device to run on [default 0]\n");
 	printf("--gpus G                    row-partition the matrix over G GPUs of this node (devices D..D+G-1), RCCL\n");
 	printf("                            all-gather of the block before each product [default 1]\n");
@@ -104,7 +109,7 @@ static void process_command_line_options(int argc, char **argv)
 		{"load-checkpoint", no_argument, NULL, 'L'}, {"device", required_argument, NULL, 'd'},
 		{"gpus", required_argument, NULL, 'g'}, {"verify", no_argument, NULL, 'V'},
 		{"cache", no_argument, NULL, 'C'}, {"basis", no_argument, NULL, 'B'}, {"rhs", required_argument, NULL, 'R'},
-		{"rhs-gpus", required_argument, NULL, 'G'},
+		{"rhs-gpus", required_argument, NULL, 'G'}, {"signed", no_argument, NULL, 'S'},
 		{"help", no_argument, NULL, 'h'}, {NULL, 0, NULL, 0}
 	};
 	int ch;
@@ -132,6 +137,7 @@ static void process_command_line_options(int argc, char **argv)
 		case 'B': basis = true; break;
 		case 'R': rhs_filename = optarg; break;
 		case 'G': rhs_gpus = atoi(optarg); rhs_gpus_given = true; break;
+		case 'S': values_signed = true; break;
 		case 'h': usage(argv); break;
 		default: errx(1, "Unknown option\n");
 		}
@@ -261,6 +267,8 @@ static void *team_worker(void *arg)
 	 * reported before its peers enter the next, instead of leaving them inside ncclCommInitRank for ever */
 	case OP_CREATE:
 		rc = blz_create(&team.ctx[g], team.loop ? device : device + g, prime, (int)n);
+		if (rc == BLZ_OK && values_signed)
+			rc = blz_set_values_signed(team.ctx[g], 1);
 		break;
 	case OP_COMM:
 		rc = team.loop ? blz_comm_init_loopback(team.ctx[g], team.loop, g)
@@ -426,7 +434,10 @@ int main(int argc, char **argv)
 	fflush(stdout);
 	blz_coo M;
 	const double t_load = wtime();
-	CHECK(blz_mm_load(matrix_filename, prime, &M));
+	if (values_signed)
+		CHECK(blz_mm_load_signed(matrix_filename, &M));
+	else
+		CHECK(blz_mm_load(matrix_filename, prime, &M));
 	fprintf(stderr, "  - [matrix coordinate integer general] %ld x %ld with %ld nz\n", (long)M.nrows, (long)M.ncols,
 		(long)M.nnz);
 	fprintf(stderr, "  - Read in %.2fs\n", wtime() - t_load);

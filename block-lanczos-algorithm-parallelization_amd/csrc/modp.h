@@ -80,6 +80,28 @@ MODP_DEV void acc_mac32(Acc &a, u32 v, u64 x)
 	a.hi = (u64)(t >> 64);
 }
 
+/*
+ * Signed value mode: v is the BIT PATTERN of an int32 matrix entry a, and the term is (a mod p) * x.  It is accumulated as
+ * |a| * x' with x' = (a < 0) ? p - x : x  (a * x = |a| * (-x) = |a| * (p - x) mod p): one 64-bit subtract-and-select per
+ * gathered word, then acc_mac32 as before.
+ * Bounds: |a| <= 2^31 (a = INT32_MIN) and x' <= p (x' = p when x = 0: not canonical, but below 2^62 and the right residue),
+ * so a term is at most 2^31 * p -- SMALLER than the unsigned path's (2^32 - 1)(p - 1).  Every sum the unsigned path keeps
+ * unreduced (128-bit row sums, the outlier tiers' partial sums, the one reduction per output word, the Barrett bound
+ * T < nnz_row * 2^32 * p) therefore holds for every row length that path supports, at every reducer class.  A slot that is
+ * switched off by v = 0 stays off: |0| = 0.
+ * SGN is a compile-time choice: with SGN = false this IS acc_mac32 and p is not read.
+ */
+template <bool SGN>
+MODP_DEV void acc_mac_val(Acc &a, u32 v, u64 x, u64 p)
+{
+	if (SGN) {
+		const bool neg = (int32_t)v < 0;
+		acc_mac32(a, neg ? 0u - v : v, neg ? p - x : x);
+	} else {
+		acc_mac32(a, v, x);
+	}
+}
+
 /* a += x (pattern matrices: every entry is 1) */
 MODP_DEV void acc_add(Acc &a, u64 x)
 {

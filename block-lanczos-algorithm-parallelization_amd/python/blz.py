@@ -131,6 +131,13 @@ class Matrix:
         return Matrix._take(M)
 
     @staticmethod
+    def load_signed(path):
+        """blz_mm_load_signed(): x holds the int32 bit pattern of every entry (signed value mode; no prime)."""
+        M = Coo()
+        check(lib().blz_mm_load_signed(path.encode(), C.byref(M)))
+        return Matrix._take(M)
+
+    @staticmethod
     def synth(nrows, ncols, nnz, seed, prime, pattern=False):
         M = Coo()
         check(lib().blz_synth_coo(C.c_int64(nrows), C.c_int64(ncols), C.c_int64(nnz), C.c_uint64(seed),
@@ -338,13 +345,17 @@ def save_block(path, nrows, n, v):
     check(lib().blz_save_block(path.encode(), C.c_int64(nrows), C.c_int(n), ptr(u64(v))))
 
 
-def check_kernel(matrix_path, kernel_path, prime, right=False):
-    """blz_check_kernel(): 0 OK, 1 all-zero kernel, 2 product not zero; raises on file/format errors."""
+def check_kernel(matrix_path, kernel_path, prime, right=False, signed=False, where=False):
+    """blz_check_kernel(): 0 OK, 1 all-zero kernel, 2 product not zero; raises on file/format errors.
+    signed=True: the matrix in signed value mode (blz_check_kernel_signed).  where=True: (rc, row, column), the place
+    of the first non-zero word when rc == 2."""
     row, col = C.c_int64(0), C.c_int(0)
-    rc = lib().blz_check_kernel(matrix_path.encode(), kernel_path.encode(), C.c_uint64(prime), C.c_int(int(right)),
-                                C.byref(row), C.byref(col))
+    fn = lib().blz_check_kernel_signed if signed else lib().blz_check_kernel
+    rc = fn(matrix_path.encode(), kernel_path.encode(), C.c_uint64(prime), C.c_int(int(right)), C.byref(row), C.byref(col))
     if rc < 0:
         check(rc)
+    if where:
+        return rc, (int(row.value) if rc == 2 else None), (int(col.value) if rc == 2 else None)
     return rc
 
 
@@ -362,12 +373,12 @@ def rhs_load(path, prime, length):
     return b[:length]
 
 
-def check_solution(matrix_path, rhs_path, x_path, prime, right=False):
+def check_solution(matrix_path, rhs_path, x_path, prime, right=False, signed=False):
     """blz_check_solution(): (0, None) when M x == b (right) / x M == b, else (2, first differing row); raises on
-    file / format errors."""
+    file / format errors.  signed=True: the matrix in signed value mode."""
     row = C.c_int64(-1)
-    rc = lib().blz_check_solution(matrix_path.encode(), rhs_path.encode(), x_path.encode(), C.c_uint64(prime),
-                                  C.c_int(int(right)), C.byref(row))
+    fn = lib().blz_check_solution_signed if signed else lib().blz_check_solution
+    rc = fn(matrix_path.encode(), rhs_path.encode(), x_path.encode(), C.c_uint64(prime), C.c_int(int(right)), C.byref(row))
     if rc < 0:
         check(rc)
     return rc, (int(row.value) if rc == 2 else None)
@@ -385,13 +396,13 @@ def rhs_load_block(path, prime, length, kmax=MAX_RHS):
     return b[:length * k.value].reshape(length, k.value)
 
 
-def check_solution_block(matrix_path, rhs_path, x_path, prime, right=False):
+def check_solution_block(matrix_path, rhs_path, x_path, prime, right=False, signed=False):
     """blz_check_solution_block(): one (status, row) per right-hand side -- (0, None) equal, (2, first differing row),
-    (3, None) the x column is all zero; raises on file / format errors."""
+    (3, None) the x column is all zero; raises on file / format errors.  signed=True: the matrix in signed value mode."""
     status = (C.c_int * MAX_RHS)()
     rows = (C.c_int64 * MAX_RHS)()
-    k = lib().blz_check_solution_block(matrix_path.encode(), rhs_path.encode(), x_path.encode(), C.c_uint64(prime),
-                                       C.c_int(int(right)), status, rows)
+    fn = lib().blz_check_solution_block_signed if signed else lib().blz_check_solution_block
+    k = fn(matrix_path.encode(), rhs_path.encode(), x_path.encode(), C.c_uint64(prime), C.c_int(int(right)), status, rows)
     if k < 0:
         check(k)
     return [(int(status[i]), int(rows[i]) if status[i] == 2 else None) for i in range(k)]
@@ -476,6 +487,21 @@ class Context:
     @property
     def word_bytes(self):
         return int(lib().blz_word_bytes(self.h))
+
+    def set_values_signed(self, on=True):
+        """blz_set_values_signed(): signed value mode -- the x of every matrix set afterwards is an int32 bit pattern
+        (Matrix.load_signed) and an entry a means a mod p.  Before the matrix is set."""
+        check(lib().blz_set_values_signed(self.h, C.c_int(int(bool(on)))))
+
+    def values_signed(self):
+        return bool(lib().blz_values_signed(self.h))
+
+    def slab_signed(self, transpose, piece=0):
+        """blz_slab_signed(): True when that slab's products run the signed instantiations of the SpMV kernels."""
+        rc = int(lib().blz_slab_signed(self.h, C.c_int(int(transpose)), C.c_int(piece)))
+        if rc < 0:
+            check(rc)
+        return bool(rc)
 
     def set_matrix(self, M, right=False, rank=0, nranks=1):
         check(lib().blz_set_matrix(self.h, C.byref(M.c), C.c_int(int(right)), C.c_int(rank), C.c_int(nranks)))
@@ -751,9 +777,12 @@ def comm_unique_id():
     return bytes(buf)
 
 
-def solve_rhs(M, b, prime, n, right=False, batch=16, device=0):
-    """M x = b (right) / x M = b on one GPU: dict(status, x, iterations, final_check)."""
+def solve_rhs(M, b, prime, n, right=False, batch=16, device=0, signed=False):
+    """M x = b (right) / x M = b on one GPU: dict(status, x, iterations, final_check).
+    signed=True: M.x holds int32 bit patterns (signed value mode)."""
     with Context(prime, n, device) as ctx:
+        if signed:
+            ctx.set_values_signed()
         ctx.set_matrix_rhs(M, b, right)
         ctx.init_v()
         while not ctx.iterate(batch)[1]:
@@ -763,13 +792,16 @@ def solve_rhs(M, b, prime, n, right=False, batch=16, device=0):
         return dict(status=status, x=x, iterations=ctx.iterations, final_check=fc)
 
 
-def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0, basis=False):
+def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0, basis=False, signed=False):
     """block_lanczos(), sequential/lanczos_modp.c:585-669, on one GPU.  Returns dict(v, tmp, iterations).
     basis=True (not with stop_after): also reduce the final block to independent kernel vectors (blz_kernel_basis) --
-    adds basis (rows x k array), k and z to the result; v, tmp and p stay those of the plain solve."""
+    adds basis (rows x k array), k and z to the result; v, tmp and p stay those of the plain solve.
+    signed=True: M.x holds int32 bit patterns (Matrix.load_signed) and an entry a means a mod p."""
     if basis and stop_after > 0:
         raise ValueError("basis=True needs a run to the end (stop_after < 0)")
     with Context(prime, n, device) as ctx:
+        if signed:
+            ctx.set_values_signed()
         ctx.set_matrix(M, right)
         ctx.init_v()
         while True:

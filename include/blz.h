@@ -72,8 +72,15 @@ typedef struct {
  * "matrix coordinate integer general" (:216-221, BLZ_EFORMAT otherwise); entries are parsed as
  * C ints, stored into a u32 and reduced `% prime` (:238-243) -- negative entries therefore wrap
  * to 2^32-|x| before the reduction, exactly as in the reference and in checker_modp.c:170-175.
- * Unlike the reference, out-of-range indices are an error (BLZ_EIO) instead of undefined behaviour. */
+ * Unlike the reference, out-of-range indices are an error (BLZ_EIO) instead of undefined behaviour.
+ * So -1 is stored as (2^32 - 1) % prime, which is p - 1 for no prime: a user who means the integer matrix mod p
+ * wants blz_mm_load_signed below and a context in signed value mode (blz_set_values_signed). */
 int blz_mm_load(const char *path, uint64_t prime, blz_coo *out);
+/* Signed value mode: the same files, but x[k] is the entry's int32 BIT PATTERN (two's complement), to be read as the
+ * residue a mod p by a context in signed value mode and by the *_signed checkers below.  No prime: nothing is reduced here.
+ * An entry outside int32 is BLZ_EIO, never a silent wrap; int32 is the whole domain of the mode.  (For prime >= 2^32
+ * blz_mm_load stores the same words: `% prime` is the identity on a u32.) */
+int blz_mm_load_signed(const char *path, blz_coo *out);
 void blz_coo_free(blz_coo *M);
 
 /* Write triplets as a MatrixMarket "coordinate integer general" file (1-based, values as stored).  Used to hand a
@@ -82,7 +89,9 @@ int blz_mm_save_coo(const char *path, const blz_coo *M);
 
 /* Seeded synthetic stand-in for a SuiteSparse matrix that is not on the box:
  * row r gets floor(nnz/R) + (r < nnz mod R) distinct uniform columns; values from
- * {1,1,1,2,3,-1,-2} (pattern=0, canonicalised like the loader does) or all 1 (pattern=1). */
+ * {1,1,1,2,3,-1,-2} (pattern=0, canonicalised like the loader does) or all 1 (pattern=1).
+ * For prime >= 2^32 the stored words are the bit patterns of those values, i.e. what blz_mm_load_signed would store: the
+ * same triplets serve a context in signed value mode unchanged (below 2^32 they are already reduced and do not). */
 int blz_synth_coo(int64_t nrows, int64_t ncols, int64_t nnz, uint64_t seed, int pattern,
 		  uint64_t prime, blz_coo *out);
 /* The entries of that same matrix in rows [r0, r1) and columns [c0, c1), global indices, without making the rest
@@ -208,6 +217,10 @@ int blz_save_block(const char *path, int64_t nrows, int n, const uint64_t *v);
  * non-zero word.  Negative returns are BLZ_E* errors (file, format, dimension mismatch). */
 int blz_check_kernel(const char *matrix_path, const char *kernel_path, uint64_t prime, int right,
 		     int64_t *bad_row, int *bad_col);
+/* The same for the integer matrix mod p: the matrix is read with blz_mm_load_signed and an entry a stands for a mod p
+ * (-1 is p - 1).  prime < 2^62.  Same return values. */
+int blz_check_kernel_signed(const char *matrix_path, const char *kernel_path, uint64_t prime, int right,
+			    int64_t *bad_row, int *bad_col);
 
 /* Rank of a kernel block file (MatrixMarket "array integer general", column-major, as blz_save_block writes it) mod
  * prime: *rank = rank of its *cols columns, found by a row-by-row reduced echelon that stops once the rank equals the
@@ -243,6 +256,11 @@ int blz_check_solution(const char *matrix_path, const char *rhs_path, const char
  * Returns k, or a negative BLZ_E* code. */
 int blz_check_solution_block(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
 			     int *status, int64_t *bad_row);
+/* Both for the integer matrix mod p (blz_mm_load_signed; an entry a stands for a mod p): same arguments and returns. */
+int blz_check_solution_signed(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+			      int64_t *bad_row);
+int blz_check_solution_block_signed(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime,
+				    int right, int *status, int64_t *bad_row);
 
 /* TEST HOOKS, not part of the supported interface (they may change or go with the layout they describe; callers use
  * blz_set_rhs_ranks): two pieces of host arithmetic of the bordered solve on several ranks, visible so that tests can hold
@@ -284,6 +302,19 @@ int blz_device_count(void);	/* 0 when no GPU is visible; never fails */
 int blz_create(blz_ctx **out, int device, uint64_t prime, int n);
 void blz_destroy(blz_ctx *ctx);
 int blz_word_bytes(const blz_ctx *ctx);	/* 4 if prime < 2^32 else 8: width of a residue in HBM */
+
+/* Signed value mode (opt-in, sticky): every matrix this context is given afterwards -- blz_set_matrix, _prepared, the
+ * _rhs* families, blz_prepare_for -- carries in x the int32 bit pattern of its entries (blz_mm_load_signed), and an entry a
+ * means the residue a mod p.  Without it x is a u32 as blz_mm_load stores it.  Must be called before a matrix is set:
+ * BLZ_EINVAL once one is resident.  The stream, palette, CSR and cache layouts are the same in both modes; blz_prepare_key
+ * mixes the mode in, so a cache written in one mode is never loaded in the other.  Checkpoints hold v and p, not the
+ * matrix: the mode is not recorded in them.  blz_values_signed: 0 / 1 = the mode of the context. */
+int blz_set_values_signed(blz_ctx *ctx, int on);
+int blz_values_signed(const blz_ctx *ctx);
+/* 1 when that slab (arguments as blz_slab_plan; the short-side slab of a product in that form) runs the signed
+ * instantiations of the SpMV kernels, 0 when it runs the unsigned ones -- any slab of an unsigned context, a slab without
+ * negative entries, and every slab of 4-byte words (values canonicalised at upload) -- negative = BLZ_EINVAL. */
+int blz_slab_signed(const blz_ctx *ctx, int transpose, int piece);
 
 /* Upload M for the solve x*M=0 (right=0) or M*x=0 (right=1), as block_lanczos(M, n, transpose)
  * receives it (sequential/lanczos_modp.c:585).  Builds CSR(M) and CSR(M^T) on the host, keeps
