@@ -161,6 +161,9 @@ struct blz_ctx {
 	hipStream_t stream = nullptr;
 	hipEvent_t ev0 = nullptr, ev1 = nullptr;
 	bool have_matrix = false;
+	bool values_wide = false;	/* wide value mode: the matrix was (or the next one will be) set with high limbs; one rank, one piece */
+	const u32 *wide_hi = nullptr;	/* borrowed until the next matrix-setting call has consumed it */
+	int64_t wide_nnz = 0;
 	bool values_signed = false;	/* signed value mode: matrix values are int32 bit patterns, an entry a means a mod p */
 	int right = 0, rank = 0, nranks = 1;
 	int64_t glob_rows[2] = { 0, 0 };		/* side 0: N, side 1: C */
@@ -319,6 +322,7 @@ static void free_csr(DevCsr &A)
 	if (A.row_ptr) hipFree(A.row_ptr);
 	if (A.col_idx) hipFree(A.col_idx);
 	if (A.val) hipFree(A.val);
+	if (A.val_hi) hipFree(A.val_hi);
 	if (A.palette) hipFree(A.palette);
 	if (A.heavy) hipFree(A.heavy);
 	if (A.heavy_multi) hipFree(A.heavy_multi);
@@ -534,13 +538,52 @@ extern "C" int blz_set_values_signed(blz_ctx *c, int on)
 		return blz_fail(BLZ_EINVAL, "blz_set_values_signed: NULL context");
 	if (c->have_matrix)
 		return blz_fail(BLZ_EINVAL, "blz_set_values_signed: a matrix is resident; choose the value mode before the matrix is set");
+	if (on && c->values_wide)
+		return blz_fail(BLZ_EINVAL, "blz_set_values_signed: the context is in wide value mode; the two never combine");
 	c->values_signed = on != 0;
 	return BLZ_OK;
 }
 
+static int wide_refuse_ranks(const blz_ctx *c, const char *who, int nranks)
+{
+	if (nranks > 1 || c->comm || c->loop || c->force_comm)
+		return blz_fail(BLZ_EINVAL, "%s: wide matrix entries need a single rank in one piece, without a communicator, a loopback "
+				"group or BLZ_FORCE_COMM (the high limbs are not distributed: see DESIGN.md section 14)", who);
+	return BLZ_OK;
+}
+
+extern "C" int blz_set_values_wide(blz_ctx *c, const uint32_t *x_hi, int64_t nnz)
+{
+	if (!c)
+		return blz_fail(BLZ_EINVAL, "blz_set_values_wide: NULL context");
+	if (c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "blz_set_values_wide: a matrix is resident; hand the high limbs over before the matrix is set");
+	if (!x_hi) {
+		c->values_wide = false;
+		c->wide_hi = nullptr;
+		c->wide_nnz = 0;
+		return BLZ_OK;
+	}
+	if (c->values_signed)
+		return blz_fail(BLZ_EINVAL, "blz_set_values_wide: the context is in signed value mode; the two never combine");
+	if (nnz < 0)
+		return blz_fail(BLZ_EINVAL, "blz_set_values_wide: nnz = %lld", (long long)nnz);
+	const int rc = wide_refuse_ranks(c, "blz_set_values_wide", 1);
+	if (rc != BLZ_OK)
+		return rc;
+	c->values_wide = true;
+	c->wide_hi = x_hi;
+	c->wide_nnz = nnz;
+	return BLZ_OK;
+}
+
+extern "C" int blz_values_wide(const blz_ctx *c) { return c && c->values_wide ? 1 : 0; }
+
 extern "C" int blz_values_signed(const blz_ctx *c) { return c && c->values_signed ? 1 : 0; }
 
-static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows = 0, bool dot_slab = false, double locality = 1.0)
+/* hi0: wide value mode, the high limbs of H0.val (host) */
+static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows = 0, bool dot_slab = false, double locality = 1.0,
+		      const u32 *hi0 = nullptr)
 {
 	free_csr(D);
 	/* Signed value mode: H0.val holds int32 bit patterns.  64-bit words: they travel as they are and the slab's products run
@@ -564,6 +607,21 @@ static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows
 		}
 	}
 	D.sgn = sgn;
+	/* Wide value mode: the slab runs the wide instantiations only when it really has an entry with a non-zero high limb (and
+	 * the words are 8 bytes: below 2^32 no residue has one).  Otherwise the high array is dropped and today's kernels run. */
+	const u32 *hi = nullptr;
+	if (hi0 && H0.val && c->cfg.word == 8) {
+		for (int64_t k = 0; k < H0.nnz && !hi; k++)
+			if (hi0[k])
+				hi = hi0;
+	}
+	if (hi) {
+		for (int64_t r = 0; r < H0.rows; r++)
+			if (H0.row_ptr[r + 1] - H0.row_ptr[r] > (1u << 30))
+				return blz_fail(BLZ_EINVAL, "a row of a wide slab has more than 2^30 entries: its unreduced sum is not bounded "
+						"(csrc/modp.h)");
+	}
+	D.wide = hi != nullptr;
 	D.locality = locality;
 	D.rows = H.rows;
 	D.cols = H.cols;
@@ -577,14 +635,14 @@ static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows
 	 * fabric requests, and this halves those of the matrix stream.  BLZ_NO_PACK=1 keeps the plain arrays. */
 	bool packed = false;
 	if (H.val && c->pack && H.cols < (1 << 24)) {
-		std::vector<u32> pal;
+		std::vector<u32> pal, pal_hi;	/* (wide: 256 low limbs, then 256 high limbs) */
 		std::vector<u32> pk((size_t)H.nnz);
 		std::vector<int> slot(4096, -1);	/* open-addressing hash: value -> palette index */
 		packed = true;
 		for (int64_t k = 0; k < H.nnz && packed; k++) {
-			const u32 v = H.val[k];
-			u32 h = (v * 2654435761u) >> 20;
-			while (slot[h] >= 0 && pal[(size_t)slot[h]] != v)
+			const u32 v = H.val[k], vh = hi ? hi[k] : 0u;
+			u32 h = ((v ^ vh * 0x9E3779B1u) * 2654435761u) >> 20;
+			while (slot[h] >= 0 && (pal[(size_t)slot[h]] != v || (hi && pal_hi[(size_t)slot[h]] != vh)))
 				h = (h + 1) & 4095u;
 			if (slot[h] < 0) {
 				if (pal.size() == 256) {
@@ -593,13 +651,19 @@ static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows
 				}
 				slot[h] = (int)pal.size();
 				pal.push_back(v);
+				if (hi)
+					pal_hi.push_back(vh);
 			}
 			pk[(size_t)k] = (u32)H.col_idx[k] | ((u32)slot[h] << 24);
 		}
 		if (packed) {
 			pal.resize(256, 0);
-			HIPCHK(hipMalloc(&D.palette, 256 * sizeof(u32)));
-			HIPCHK(hipMemcpy(D.palette, pal.data(), 256 * sizeof(u32), hipMemcpyHostToDevice));
+			if (hi) {
+				pal_hi.resize(256, 0);
+				pal.insert(pal.end(), pal_hi.begin(), pal_hi.end());
+			}
+			HIPCHK(hipMalloc(&D.palette, pal.size() * sizeof(u32)));
+			HIPCHK(hipMemcpy(D.palette, pal.data(), pal.size() * sizeof(u32), hipMemcpyHostToDevice));
 			HIPCHK(hipMemcpy(D.col_idx, pk.data(), (size_t)H.nnz * sizeof(u32), hipMemcpyHostToDevice));
 		}
 	}
@@ -609,6 +673,11 @@ static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows
 			HIPCHK(hipMalloc(&D.val, (size_t)(H.nnz + BLZ_STREAM_PAD) * sizeof(u32)));
 			HIPCHK(hipMemset(D.val + H.nnz, 0, BLZ_STREAM_PAD * sizeof(u32)));
 			HIPCHK(hipMemcpy(D.val, H.val, (size_t)H.nnz * sizeof(u32), hipMemcpyHostToDevice));
+			if (hi) {
+				HIPCHK(hipMalloc(&D.val_hi, (size_t)(H.nnz + BLZ_STREAM_PAD) * sizeof(u32)));
+				HIPCHK(hipMemset(D.val_hi + H.nnz, 0, BLZ_STREAM_PAD * sizeof(u32)));
+				HIPCHK(hipMemcpy(D.val_hi, hi, (size_t)H.nnz * sizeof(u32), hipMemcpyHostToDevice));
+			}
 		}
 	}
 	D.heavy_thr = spmv_heavy_threshold(c->cfg, H.rows, H.nnz);
@@ -754,6 +823,13 @@ static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool
 		return blz_fail(BLZ_EINVAL, "nranks * p must not exceed 2**64 (u64 all-reduce of residues)");
 	if (K > 1 && nranks == 1 && !c->force_comm)
 		return blz_fail(BLZ_EINVAL, "blz_set_matrix_prepared: the matrix was prepared in %d pieces for a single rank", K);
+	if (P->val_hi[0] || P->val_hi[1]) {
+		if (K > 1)
+			return blz_fail(BLZ_EINVAL, "blz_set_matrix_prepared: wide matrix entries need the products in one piece");
+		const int rcw = wide_refuse_ranks(c, "blz_set_matrix_prepared", nranks);
+		if (rcw != BLZ_OK)
+			return rcw;
+	}
 	if (c->loop && (rank != c->loop_rank || nranks != c->loop->nranks))
 		return blz_fail(BLZ_EINVAL, "blz_set_matrix_prepared: rank %d of %d, but the context is rank %d of %d in its loopback communicator",
 				rank, nranks, c->loop_rank, c->loop->nranks);
@@ -849,7 +925,8 @@ static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool
 		if (K == 1) {
 			/* product t gathers block rows by the column index of its slab: columns of M for t = 0, rows of M for t = 1 */
 			const int64_t hot_t = c->cfg.panel ? P->hot[t == 0 ? 1 : 0] : 0;
-			rc = upload_csr(c, slab, c->csr[t][0], hot_t, dot_slab, nranks == 1 ? c->locality[t] : 1.0);
+			rc = upload_csr(c, slab, c->csr[t][0], hot_t, dot_slab, nranks == 1 ? c->locality[t] : 1.0,
+					whole ? P->val_hi[t] : nullptr);
 			{
 				/* Gathers that mostly hit (a banded / well-ordered matrix: the locality rule of spmv_plan_staged): the product
 				 * is paced by the kernel, and there the staged form with 16-byte lanes plus the inner products as their own
@@ -857,7 +934,7 @@ static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool
 				 * 389 (profiles/r03_band_switches.txt).  Where the fabric paces the gathers the fused form stays (the inner
 				 * products ride along for 20 us). */
 				DevCsr &D = c->csr[t][0];
-				if (rc == BLZ_OK && dot_slab && nranks == 1 && block_dot_mfma_supported(c->cfg) && D.panel_rows == 0 &&
+				if (rc == BLZ_OK && dot_slab && nranks == 1 && !D.wide && block_dot_mfma_supported(c->cfg) && D.panel_rows == 0 &&
 				    D.locality < 0.3 && !D.uneven && D.outlier_share < 0.02) {
 					spmv_plan_staged(c->cfg, slab.row_ptr, D, true);
 					c->fuse_local_off = D.st_ok;
@@ -943,6 +1020,9 @@ static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool
 
 extern "C" int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank)
 {
+	if (c && c->wide_hi)	/* (a prepared object was made without them: the matrix would be that of the low limbs alone) */
+		return blz_fail(BLZ_EINVAL, "blz_set_matrix_prepared: high limbs are pending (blz_set_values_wide); they go with "
+				"blz_set_matrix, blz_set_matrix_rhs or blz_set_matrix_rhs_block");
 	return set_matrix_prepared(c, P, rank, true);
 }
 
@@ -955,7 +1035,54 @@ extern "C" int blz_set_matrix(blz_ctx *c, const blz_coo *M, int right, int rank,
 	if (nranks < 1 || rank < 0 || rank >= nranks)
 		return blz_fail(BLZ_EINVAL, "blz_set_matrix: rank %d of %d", rank, nranks);
 	blz_prepared *P = nullptr;
-	int rc = blz_prepare_for(c, M, right, nranks, &P);
+	int rc;
+	if (c->wide_hi) {
+		/* Wide value mode: the pending high limbs belong to this matrix and are consumed here, whatever comes of the call
+		 * (a call that fails leaves the context out of the mode: no matrix of it is resident or pending).
+		 * The whole preparation runs on the entry NUMBERS in place of the values; one gather at the end fills both limbs. */
+		const u32 *hi = c->wide_hi;
+		const int64_t hn = c->wide_nnz;
+		c->wide_hi = nullptr;
+		c->wide_nnz = 0;
+		c->values_wide = false;
+		if ((rc = wide_refuse_ranks(c, "blz_set_matrix", nranks)) != BLZ_OK)
+			return rc;
+		if (hn != M->nnz)
+			return blz_fail(BLZ_EINVAL, "blz_set_matrix: %lld high limbs for a matrix of %lld entries (blz_set_values_wide)",
+					(long long)hn, (long long)M->nnz);
+		if (M->nnz > 0xFFFFFFFFll)
+			return blz_fail(BLZ_EINVAL, "blz_set_matrix: too many entries");
+		for (int64_t k = 0; k < M->nnz; k++)
+			if ((((uint64_t)hi[k] << 32) | M->x[k]) >= c->prime)
+				return blz_fail(BLZ_EINVAL, "blz_set_matrix: entry %lld is not a residue below p (wide value mode)", (long long)k);
+		bool any_hi = false;
+		for (int64_t k = 0; k < M->nnz && !any_hi; k++)
+			any_hi = hi[k] != 0;
+		if (!any_hi) {
+			/* every high limb is zero: the ordinary path, value-dependent choices (a matrix of ones is a pattern) included --
+			 * the plans and the words are those of a context that was never given a high array */
+			if ((rc = blz_prepare_for(c, M, right, nranks, &P)) != BLZ_OK)
+				return rc;
+			rc = blz_set_matrix_prepared(c, P, rank);
+			blz_prepared_free(P);
+			c->values_wide = rc == BLZ_OK;
+			return rc;
+		}
+		std::vector<u32> number((size_t)std::max<int64_t>(M->nnz, 1));
+		for (int64_t k = 0; k < M->nnz; k++)
+			number[(size_t)k] = (u32)k;
+		blz_coo Mn = *M;
+		Mn.x = number.data();
+		if ((rc = blz_prepare_for(c, &Mn, right, nranks, &P)) != BLZ_OK)
+			return rc;
+		if ((rc = blz_prepared_fill_wide(P, M->x, hi)) == BLZ_OK)
+			rc = blz_set_matrix_prepared(c, P, rank);
+		blz_prepared_free(P);
+		c->values_wide = rc == BLZ_OK;
+		return rc;
+	}
+	c->values_wide = false;		/* (an ordinary matrix: the mode describes the matrix that is resident or about to be set) */
+	rc = blz_prepare_for(c, M, right, nranks, &P);
 	if (rc != BLZ_OK)
 		return rc;
 	rc = blz_set_matrix_prepared(c, P, rank);
@@ -1303,6 +1430,8 @@ extern "C" int blz_set_matrix_rhs_ranks(blz_ctx *c, const blz_coo *M, int right,
 		return rc;
 	if (nranks == 1 && !c->comm && !c->loop && !c->force_comm)
 		return blz_set_matrix_rhs_block(c, M, right, k, b);
+	if (c->wide_hi)		/* (pending high limbs on several ranks: set_values_wide refused the communicator, this refuses nranks) */
+		return wide_refuse_ranks(c, "blz_set_matrix_rhs_ranks", nranks > 1 ? nranks : 2);
 	if (c->external_exchange)
 		return blz_fail(BLZ_EINVAL, "blz_set_matrix_rhs_ranks: the context is in external-exchange mode (the all-reduce of the "
 				"border words is the library's own)");
@@ -1444,13 +1573,25 @@ extern "C" int blz_slab_signed(const blz_ctx *c, int transpose, int piece)
 	return A.sgn ? 1 : 0;
 }
 
+extern "C" int blz_slab_wide(const blz_ctx *c, int transpose, int piece)
+{
+	if (!c || !c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "blz_slab_wide: no context or no matrix");
+	const int t = transpose ? 1 : 0;
+	const bool sh = c->short_side[t];
+	if (piece < 0 || piece >= (sh ? 1 : (int)c->csr[t].size()))
+		return blz_fail(BLZ_EINVAL, "blz_slab_wide: piece %d of %d", piece, sh ? 1 : (int)c->csr[t].size());
+	const DevCsr &A = sh ? c->csr_short[t] : c->csr[t][(size_t)piece];
+	return A.wide ? 1 : 0;
+}
+
 extern "C" int64_t blz_matrix_stream_bytes(const blz_ctx *c, int transpose)
 {
 	if (!c || !c->have_matrix)
 		return -1;
 	int64_t bytes = 0;
 	for (const auto &A : c->csr[transpose ? 1 : 0])
-		bytes += (A.rows + 1) * 4 + A.nnz * 4 + (A.val ? A.nnz * 4 : 0);
+		bytes += (A.rows + 1) * 4 + A.nnz * 4 + (A.val ? A.nnz * 4 : 0) + (A.val_hi ? A.nnz * 4 : 0);
 	return bytes;
 }
 
@@ -2782,6 +2923,8 @@ extern "C" int blz_comm_init(blz_ctx *c, const void *id, size_t id_bytes, int ra
 {
 	if (!c || !id || id_bytes < sizeof(ncclUniqueId) || nranks < 1 || rank < 0 || rank >= nranks)
 		return blz_fail(BLZ_EINVAL, "blz_comm_init: bad argument");
+	if (c->values_wide)
+		return blz_fail(BLZ_EINVAL, "blz_comm_init: the context is in wide value mode, which needs a single rank without a communicator");
 	HIPCHK(hipSetDevice(c->device));
 	int rc = rccl_load();
 	if (rc != BLZ_OK)
@@ -2862,6 +3005,8 @@ extern "C" int blz_comm_init_loopback(blz_ctx *c, blz_loop_group *g, int rank)
 {
 	if (!c || !g || rank < 0 || rank >= g->nranks)
 		return blz_fail(BLZ_EINVAL, "blz_comm_init_loopback: bad argument");
+	if (c->values_wide)
+		return blz_fail(BLZ_EINVAL, "blz_comm_init_loopback: the context is in wide value mode, which needs a single rank without a communicator");
 	if (c->comm || c->loop)
 		return blz_fail(BLZ_EINVAL, "blz_comm_init_loopback: the context has a communicator already");
 	HIPCHK(hipSetDevice(c->device));

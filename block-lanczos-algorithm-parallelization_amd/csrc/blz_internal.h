@@ -42,7 +42,11 @@ struct blz_prepared {
 	int64_t full_first[2];			/* ... row q of full[t] being global row full_first[t] + q */
 	void *map;
 	size_t map_len;
+	uint32_t *val_hi[2];			/* wide value mode: the high limbs of full[t].val (malloc'ed, never in a cache file); NULL otherwise */
 };
+
+/* wide value mode: P was prepared with x[k] = k; replace the entry numbers by lo[] and build val_hi[] from hi[] */
+BLZ_LOCAL int blz_prepared_fill_wide(struct blz_prepared *P, const uint32_t *lo, const uint32_t *hi);
 
 #ifdef __cplusplus
 }

@@ -30,6 +30,11 @@ struct DevCsr {
 	u32 *palette = nullptr;	/* 256 values: col_idx then holds  column | (palette index << 24)  */
 	bool sgn = false;	/* signed value mode AND the slab has a negative entry AND 64-bit words: its values are int32 bit
 				 * patterns and its products run the signed instantiations (acc_mac_val<true>, modp.h) */
+	u32 *val_hi = nullptr;	/* wide value mode: the high limbs, parallel to val (value array; BLZ_STREAM_PAD spare entries too) */
+	bool wide = false;	/* wide value mode AND 64-bit words AND the slab has an entry with a non-zero high limb: an entry is
+				 * val + 2^32 * val_hi (or palette[i] + 2^32 * palette[256 + i]: the palette then has 512 entries) and
+				 * its products run the wide instantiations of k_spmv, k_spmv_dot, k_spmv_wave and k_spmv_heavy
+				 * (acc_mac_wide, modp.h) -- the plain form only: spmv_form().  Never together with sgn. */
 	HeavySeg *heavy = nullptr;	/* segments of the rows longer than heavy_thr: handled by k_spmv_heavy */
 	int n_heavy = 0;
 	HeavyRow *heavy_multi = nullptr;	/* the rows among them that span several segments */

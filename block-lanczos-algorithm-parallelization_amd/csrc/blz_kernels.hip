@@ -104,21 +104,28 @@ MODP_DEV u64 shfl_xor64(u64 x, int mask)
  * shortens the dependent chain of a row -- relat8 shape, 15 us products: 17.0 -> 15.8 us; structured workload, gathers that
  * hit: 663 -> 647 us -- and costs the fabric-bound uniform shapes their dead slots (GL7d19 shape: 656 -> 664 us), so the
  * slab's plan asks for it only where the gathers hit or the product is a few launches' worth of latency (round 3). */
-/* SGN: signed value mode (acc_mac_val, modp.h); `p` is read by that form only */
-template <typename W, bool TAILB = false, bool SGN = false>
+/* VM: the value mode (modp.h: VM_U32, VM_SIGNED, VM_WIDE; a `bool SGN` of a caller converts to the first two).  `m` is read by
+ * the signed form (m.p) and the wide form only.  VM_WIDE: the high limbs come from `vh` (value array) or from the second 256
+ * entries of `spal` (palette); MERS chooses the form of x' = 2^32 * x mod p.  A dead slot of the tail batch gets BOTH limbs
+ * zeroed. */
+#define SPMV_HI_PAL(pw) (VM == VM_WIDE ? spal[256 + ((pw) >> 24)] : 0u)
+#define SPMV_HI_ARR(q) (VM == VM_WIDE ? vh[q] : 0u)
+template <typename W, bool TAILB = false, int VM = VM_U32, int MERS = 0>
 MODP_DEV void spmv_accumulate(Acc &acc, u32 k, u32 e, const int *__restrict__ ci, const u32 *__restrict__ va,
-			      const u32 *spal, const W *__restrict__ X, int stride, int xl, u64 p = 0)
+			      const u32 *spal, const W *__restrict__ X, int stride, int xl, const ModP &m,
+			      const u32 *__restrict__ vh = nullptr)
 {
+	static_assert(VM != VM_WIDE || sizeof(W) == 8, "wide values: 64-bit words only");
 	if (spal) {
 		/* packed stream: one u32 per entry = column (24 bits) | index into the value palette (8 bits, in LDS) */
 		for (; k + 4 <= e; k += 4) {
 			const u32 p0 = (u32)ci[k], p1 = (u32)ci[k + 1], p2 = (u32)ci[k + 2], p3 = (u32)ci[k + 3];
 			const W x0 = X[(size_t)(p0 & 0xFFFFFFu) * stride + xl], x1 = X[(size_t)(p1 & 0xFFFFFFu) * stride + xl];
 			const W x2 = X[(size_t)(p2 & 0xFFFFFFu) * stride + xl], x3 = X[(size_t)(p3 & 0xFFFFFFu) * stride + xl];
-			acc_mac_val<SGN>(acc, spal[p0 >> 24], x0, p);
-			acc_mac_val<SGN>(acc, spal[p1 >> 24], x1, p);
-			acc_mac_val<SGN>(acc, spal[p2 >> 24], x2, p);
-			acc_mac_val<SGN>(acc, spal[p3 >> 24], x3, p);
+			acc_mac_entry<VM, MERS>(acc, spal[p0 >> 24], SPMV_HI_PAL(p0), x0, m);
+			acc_mac_entry<VM, MERS>(acc, spal[p1 >> 24], SPMV_HI_PAL(p1), x1, m);
+			acc_mac_entry<VM, MERS>(acc, spal[p2 >> 24], SPMV_HI_PAL(p2), x2, m);
+			acc_mac_entry<VM, MERS>(acc, spal[p3 >> 24], SPMV_HI_PAL(p3), x3, m);
 		}
 		if (TAILB) {
 			if (k < e) {
@@ -127,26 +134,27 @@ MODP_DEV void spmv_accumulate(Acc &acc, u32 k, u32 e, const int *__restrict__ ci
 				const u32 p0 = (u32)ci[k], p1 = (u32)ci[q1], p2 = (u32)ci[q2];
 				const W x0 = X[(size_t)(p0 & 0xFFFFFFu) * stride + xl], x1 = X[(size_t)(p1 & 0xFFFFFFu) * stride + xl];
 				const W x2 = X[(size_t)(p2 & 0xFFFFFFu) * stride + xl];
-				acc_mac_val<SGN>(acc, spal[p0 >> 24], x0, p);
-				acc_mac_val<SGN>(acc, k + 1 < e ? spal[p1 >> 24] : 0u, x1, p);
-				acc_mac_val<SGN>(acc, k + 2 < e ? spal[p2 >> 24] : 0u, x2, p);
+				acc_mac_entry<VM, MERS>(acc, spal[p0 >> 24], SPMV_HI_PAL(p0), x0, m);
+				acc_mac_entry<VM, MERS>(acc, k + 1 < e ? spal[p1 >> 24] : 0u, k + 1 < e ? SPMV_HI_PAL(p1) : 0u, x1, m);
+				acc_mac_entry<VM, MERS>(acc, k + 2 < e ? spal[p2 >> 24] : 0u, k + 2 < e ? SPMV_HI_PAL(p2) : 0u, x2, m);
 			}
 		} else {
 			for (; k < e; k++) {
 				const u32 pk = (u32)ci[k];
-				acc_mac_val<SGN>(acc, spal[pk >> 24], X[(size_t)(pk & 0xFFFFFFu) * stride + xl], p);
+				acc_mac_entry<VM, MERS>(acc, spal[pk >> 24], SPMV_HI_PAL(pk), X[(size_t)(pk & 0xFFFFFFu) * stride + xl], m);
 			}
 		}
 	} else if (va) {
 		for (; k + 4 <= e; k += 4) {
 			const int c0 = ci[k], c1 = ci[k + 1], c2 = ci[k + 2], c3 = ci[k + 3];
 			const u32 a0 = va[k], a1 = va[k + 1], a2 = va[k + 2], a3 = va[k + 3];
+			const u32 h0 = SPMV_HI_ARR(k), h1 = SPMV_HI_ARR(k + 1), h2 = SPMV_HI_ARR(k + 2), h3 = SPMV_HI_ARR(k + 3);
 			const W x0 = X[(size_t)c0 * stride + xl], x1 = X[(size_t)c1 * stride + xl];
 			const W x2 = X[(size_t)c2 * stride + xl], x3 = X[(size_t)c3 * stride + xl];
-			acc_mac_val<SGN>(acc, a0, x0, p);
-			acc_mac_val<SGN>(acc, a1, x1, p);
-			acc_mac_val<SGN>(acc, a2, x2, p);
-			acc_mac_val<SGN>(acc, a3, x3, p);
+			acc_mac_entry<VM, MERS>(acc, a0, h0, x0, m);
+			acc_mac_entry<VM, MERS>(acc, a1, h1, x1, m);
+			acc_mac_entry<VM, MERS>(acc, a2, h2, x2, m);
+			acc_mac_entry<VM, MERS>(acc, a3, h3, x3, m);
 		}
 		if (TAILB) {
 			if (k < e) {
@@ -154,14 +162,15 @@ MODP_DEV void spmv_accumulate(Acc &acc, u32 k, u32 e, const int *__restrict__ ci
 				const u32 q1 = k + 1 < e ? k + 1 : last, q2 = k + 2 < e ? k + 2 : last;
 				const int c0 = ci[k], c1 = ci[q1], c2 = ci[q2];
 				const u32 a0 = va[k], a1 = va[q1], a2 = va[q2];
+				const u32 h0 = SPMV_HI_ARR(k), h1 = SPMV_HI_ARR(q1), h2 = SPMV_HI_ARR(q2);
 				const W x0 = X[(size_t)c0 * stride + xl], x1 = X[(size_t)c1 * stride + xl], x2 = X[(size_t)c2 * stride + xl];
-				acc_mac_val<SGN>(acc, a0, x0, p);
-				acc_mac_val<SGN>(acc, k + 1 < e ? a1 : 0u, x1, p);
-				acc_mac_val<SGN>(acc, k + 2 < e ? a2 : 0u, x2, p);
+				acc_mac_entry<VM, MERS>(acc, a0, h0, x0, m);
+				acc_mac_entry<VM, MERS>(acc, k + 1 < e ? a1 : 0u, k + 1 < e ? h1 : 0u, x1, m);
+				acc_mac_entry<VM, MERS>(acc, k + 2 < e ? a2 : 0u, k + 2 < e ? h2 : 0u, x2, m);
 			}
 		} else {
 			for (; k < e; k++)
-				acc_mac_val<SGN>(acc, va[k], X[(size_t)ci[k] * stride + xl], p);
+				acc_mac_entry<VM, MERS>(acc, va[k], SPMV_HI_ARR(k), X[(size_t)ci[k] * stride + xl], m);
 		}
 	} else {
 		for (; k + 4 <= e; k += 4) {
@@ -189,6 +198,8 @@ MODP_DEV void spmv_accumulate(Acc &acc, u32 k, u32 e, const int *__restrict__ ci
 		}
 	}
 }
+#undef SPMV_HI_PAL
+#undef SPMV_HI_ARR
 
 MODP_DEV void acc_add_acc(Acc &a, u64 olo, u64 ohi)
 {
@@ -208,9 +219,10 @@ MODP_DEV void acc_add_acc(Acc &a, u64 olo, u64 ohi)
  */
 
 /* all threads of the block: sum entries [k0, e0) over BLOCK/G slices; group 0 returns the 128-bit total */
-template <typename W, int G, bool SGN = false>
+template <typename W, int G, int VM = VM_U32, int MERS = 0>
 MODP_DEV Acc heavy_range_sum(u32 k0, u32 e0, const int *__restrict__ ci, const u32 *__restrict__ va, const u32 *spal,
-			     const W *__restrict__ X, int stride, int xl, Acc (*slices)[G], u64 p = 0)
+			     const W *__restrict__ X, int stride, int xl, Acc (*slices)[G], const ModP &m,
+			     const u32 *__restrict__ vh = nullptr)
 {
 	constexpr int GPB = BLOCK / G;
 	const int grp = threadIdx.x / G, lane = threadIdx.x & (G - 1);
@@ -218,7 +230,7 @@ MODP_DEV Acc heavy_range_sum(u32 k0, u32 e0, const int *__restrict__ ci, const u
 	const u32 lo = k0 + (u32)grp * per;
 	Acc acc;
 	acc_zero(acc);
-	spmv_accumulate<W, false, SGN>(acc, lo < e0 ? lo : e0, (lo + per) < e0 ? (lo + per) : e0, ci, va, spal, X, stride, xl, p);
+	spmv_accumulate<W, false, VM, MERS>(acc, lo < e0 ? lo : e0, (lo + per) < e0 ? (lo + per) : e0, ci, va, spal, X, stride, xl, m, vh);
 	slices[grp][lane] = acc;
 	__syncthreads();
 	if (grp == 0)
@@ -228,9 +240,9 @@ MODP_DEV Acc heavy_range_sum(u32 k0, u32 e0, const int *__restrict__ ci, const u
 	return acc;
 }
 
-template <typename W, int G, int MERS, bool DOT, bool SGN = false>
+template <typename W, int G, int MERS, bool DOT, int VM = VM_U32>
 __global__ void __launch_bounds__(BLOCK)
-k_spmv_heavy(const int *__restrict__ ci, const u32 *__restrict__ va, const u32 *__restrict__ pal,
+k_spmv_heavy(const int *__restrict__ ci, const u32 *__restrict__ va, const u32 *__restrict__ vh, const u32 *__restrict__ pal,
 	     const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd, const HeavySeg *__restrict__ segs,
 	     int nseg, u64 *__restrict__ scratch, int n, int accum, ModP m, u64 *__restrict__ partial, int slot0,
 	     const DevCtl *__restrict__ ctl);
@@ -240,10 +252,10 @@ k_spmv_heavy_combine(const HeavyRow *__restrict__ mrows, int nm, const u64 *__re
 		     const W *__restrict__ Vd, int n, int accum, ModP m, u64 *__restrict__ partial, int slot0,
 		     const DevCtl *__restrict__ ctl);
 
-template <typename W, int G, int MERS, bool DOT, bool SGN = false>
+template <typename W, int G, int MERS, bool DOT, int VM = VM_U32>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_wave(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__restrict__ va,
-	    const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd,
+	    const u32 *__restrict__ vh, const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd,
 	    const int *__restrict__ list, int nlist, int n, int accum, ModP m, u64 *__restrict__ partial, int slot0,
 	    const DevCtl *__restrict__ ctl);
 
@@ -277,7 +289,7 @@ static void heavy_fork(const KernelCfg &c, const DevCsr &A, hipStream_t s)
 		(void)hipEventRecord(c.ev_fork, s);
 }
 
-template <typename W, int G, int MERS, bool DOT, bool SGN>
+template <typename W, int G, int MERS, bool DOT, int VM>
 static void launch_heavy_as(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum, u64 *partial,
 			    int slot0, long long hb, const DevCtl *ctl, hipStream_t main_stream)
 {
@@ -298,45 +310,53 @@ static void launch_heavy_as(const KernelCfg &c, const DevCsr &A, const W *X, W *
 		}
 	} join{ c, s, main_stream };
 	if (hb)
-		hipLaunchKernelGGL((k_spmv_heavy<W, G, MERS, DOT, SGN>), dim3((unsigned)hb), dim3(BLOCK), 0, s, A.col_idx, A.val,
-				   A.palette, X, Y, Vd, A.heavy, A.n_heavy, A.heavy_scratch, c.n, accum, c.m, partial, slot0, ctl);
+		hipLaunchKernelGGL((k_spmv_heavy<W, G, MERS, DOT, VM>), dim3((unsigned)hb), dim3(BLOCK), 0, s, A.col_idx, A.val,
+				   A.val_hi, A.palette, X, Y, Vd, A.heavy, A.n_heavy, A.heavy_scratch, c.n, accum, c.m, partial, slot0, ctl);
 	const long long cb = A.n_multi ? combine_blocks(A, G) : 0;
 	if (cb)
 		hipLaunchKernelGGL((k_spmv_heavy_combine<W, G, MERS, DOT>), dim3((unsigned)cb), dim3(BLOCK),
 				   0, s, A.heavy_multi, A.n_multi, A.heavy_scratch, Y, Vd, c.n, accum, c.m, partial,
 				   slot0 + (int)hb, ctl);
 	if (A.n_medium)
-		hipLaunchKernelGGL((k_spmv_wave<W, G, MERS, DOT, SGN>), dim3((unsigned)medium_blocks(c, A)), dim3(BLOCK), 0, s,
-				   A.row_ptr, A.col_idx, A.val, A.palette, X, Y, Vd, A.medium_rows, A.n_medium, c.n, accum, c.m,
+		hipLaunchKernelGGL((k_spmv_wave<W, G, MERS, DOT, VM>), dim3((unsigned)medium_blocks(c, A)), dim3(BLOCK), 0, s,
+				   A.row_ptr, A.col_idx, A.val, A.val_hi, A.palette, X, Y, Vd, A.medium_rows, A.n_medium, c.n, accum, c.m,
 				   partial, slot0 + (int)(hb + cb), ctl);
 }
 
-/* the signed instantiations exist for 64-bit words only (DevCsr::sgn is never set on a slab of 4-byte words) */
+/* the signed and the wide instantiations exist for 64-bit words only (DevCsr::sgn and DevCsr::wide are never set on a slab
+ * of 4-byte words, and never both) */
 template <typename W, int G, int MERS, bool DOT>
 static void launch_heavy(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum, u64 *partial,
 			 int slot0, long long hb, const DevCtl *ctl, hipStream_t main_stream)
 {
 	if constexpr (sizeof(W) == 8) {
+		if (A.wide) {
+			launch_heavy_as<W, G, MERS, DOT, VM_WIDE>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
+			return;
+		}
 		if (A.sgn) {
-			launch_heavy_as<W, G, MERS, DOT, true>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
+			launch_heavy_as<W, G, MERS, DOT, VM_SIGNED>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
 			return;
 		}
 	}
-	launch_heavy_as<W, G, MERS, DOT, false>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
+	launch_heavy_as<W, G, MERS, DOT, VM_U32>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
 }
 
-template <typename W, int G, int MERS, bool TAILB, bool SGN = false>
+template <typename W, int G, int MERS, bool TAILB, int VM = VM_U32>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__restrict__ va,
-       const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, long long rows, int n, int split_log2,
+       const u32 *__restrict__ vh, const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, long long rows, int n, int split_log2,
        int accum, u32 heavy, ModP m, XcdRows xr, const DevCtl *__restrict__ ctl)
 {
 	if (ctl->stop)
 		return;
-	__shared__ u32 spal_store[BLOCK];
+	__shared__ u32 spal_store[VM == VM_WIDE ? 2 * BLOCK : BLOCK];	/* wide: the 256 low limbs, then the 256 high limbs */
 	const u32 *spal = pal ? spal_store : nullptr;
-	if (pal)
+	if (pal) {
 		spal_store[threadIdx.x] = pal[threadIdx.x];
+		if (VM == VM_WIDE)
+			spal_store[BLOCK + threadIdx.x] = pal[BLOCK + threadIdx.x];
+	}
 	__syncthreads();
 	const int lane = threadIdx.x & (G - 1);
 	const int xl = lane < n ? lane : 0;
@@ -367,7 +387,7 @@ k_spmv(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__rest
 		}
 		Acc acc;
 		acc_zero(acc);
-		spmv_accumulate<W, TAILB, SGN>(acc, k, e, ci, va, spal, X, n, xl, m.p);
+		spmv_accumulate<W, TAILB, VM, MERS>(acc, k, e, ci, va, spal, X, n, xl, m, vh);
 		for (int off = G; off < (G << split_log2); off <<= 1)
 			acc_add_acc(acc, shfl_xor64(acc.lo, off), shfl_xor64(acc.hi, off));
 		if (lane < n && part == 0) {
@@ -547,6 +567,8 @@ static SpmvGrids panel_grids(const KernelCfg &c, const DevCsr &A, bool dot, int 
 /* which form a product of the slab takes (the order the dispatch functions test in) */
 static inline int spmv_form(const KernelCfg &c, const DevCsr &A, bool dot)
 {
+	if (A.wide)	/* k_spmv_staged and k_spmv_panel have no wide instantiation: a wide slab runs the plain form, whatever its plans say */
+		return SPMV_FORM_STREAM;
 	if (A.panel_rows > 0 && c.panel)
 		return SPMV_FORM_PANEL;
 	if (A.st_ok && c.staged && !(dot && A.st_dyn))	/* (a slab planned for dynamic rows has tiles the lockstep form cannot walk) */
@@ -602,24 +624,31 @@ static hipError_t spmv_dispatch(const KernelCfg &c, const DevCsr &A, const W *X,
 	if (g.xcd)
 		for (int x = 0; x < 9; x++)
 			xr.begin[x] = A.xr_rows[x];
-	const bool sgn = sizeof(W) == 8 && A.sgn;
+	const bool sgn = sizeof(W) == 8 && A.sgn, wide = sizeof(W) == 8 && A.wide;
 #define SPMV_GO(GG, TT, SS)                                                                                     \
 	hipLaunchKernelGGL((k_spmv<W, GG, MERS, TT, SS>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, A.row_ptr,          \
-			   A.col_idx, A.val, A.palette, X, Y, (long long)A.rows, c.n, split_log2, accum,                  \
+			   A.col_idx, A.val, A.val_hi, A.palette, X, Y, (long long)A.rows, c.n, split_log2, accum,                  \
 			   A.heavy_thr, c.m, xr, ctl)
 #define SPMV_CASE(GG)                                                                                           \
 	case GG:                                                                                                  \
-		if (sgn) {                                                                                        \
+		if (wide) {                                                                                       \
 			if constexpr (sizeof(W) == 8) {                                                           \
 				if (A.tail_batch)                                                                 \
-					SPMV_GO(GG, true, true);                                                  \
+					SPMV_GO(GG, true, VM_WIDE);                                               \
 				else                                                                              \
-					SPMV_GO(GG, false, true);                                                 \
+					SPMV_GO(GG, false, VM_WIDE);                                              \
+			}                                                                                         \
+		} else if (sgn) {                                                                                 \
+			if constexpr (sizeof(W) == 8) {                                                           \
+				if (A.tail_batch)                                                                 \
+					SPMV_GO(GG, true, VM_SIGNED);                                             \
+				else                                                                              \
+					SPMV_GO(GG, false, VM_SIGNED);                                            \
 			}                                                                                         \
 		} else if (A.tail_batch)                                                                          \
-			SPMV_GO(GG, true, false);                                                                 \
+			SPMV_GO(GG, true, VM_U32);                                                                \
 		else                                                                                              \
-			SPMV_GO(GG, false, false);                                                                \
+			SPMV_GO(GG, false, VM_U32);                                                               \
 		if (A.n_heavy || A.n_medium)                                                                      \
 			launch_heavy<W, GG, MERS, false>(c, A, X, Y, (const W *)nullptr, accum, (u64 *)nullptr, 0,   \
 							 g.hb, ctl, s);                                               \
@@ -931,10 +960,10 @@ k_block_dot_64(const W *__restrict__ V, const W *__restrict__ AV, long long rows
  * per lane cost more occupancy than the saved pass is worth (measured: 15.8 ms fused against 12.4 + 2.3 ms apart on
  * the config-5 shape), so that width runs k_spmv and k_block_dot_fast.
  */
-template <typename W, int MERS, int NT, bool TAILB, bool SGN = false>
+template <typename W, int MERS, int NT, bool TAILB, int VM = VM_U32>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_dot(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__restrict__ va,
-	   const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd,
+	   const u32 *__restrict__ vh, const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd,
 	   long long rows, int accum, u32 heavy, ModP m, u64 *__restrict__ partial, XcdRows xr,
 	   const DevCtl *__restrict__ ctl)
 {
@@ -942,10 +971,13 @@ k_spmv_dot(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__
 		return;
 	using DS = DotState<typename std::conditional<sizeof(W) == 4, AccS, Acc>::type, MERS, NT, BLOCK, true>;
 	__shared__ u64 red[DS::WAVES][DS::SLOTS][NT];
-	__shared__ u32 spal_store[BLOCK];
+	__shared__ u32 spal_store[VM == VM_WIDE ? 2 * BLOCK : BLOCK];	/* wide: the 256 low limbs, then the 256 high limbs */
 	const u32 *spal = pal ? spal_store : nullptr;
-	if (pal)
+	if (pal) {
 		spal_store[threadIdx.x] = pal[threadIdx.x];
+		if (VM == VM_WIDE)
+			spal_store[BLOCK + threadIdx.x] = pal[BLOCK + threadIdx.x];
+	}
 	__syncthreads();
 	const int t = threadIdx.x, lane = t & (NT - 1), gbase = (t & 63) - lane;
 	long long r = ((long long)blockIdx.x * BLOCK + t) / NT;
@@ -965,7 +997,7 @@ k_spmv_dot(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__
 		const u64 vi = Vd[(size_t)r * NT + lane];
 		Acc acc;
 		acc_zero(acc);
-		spmv_accumulate<W, TAILB, SGN>(acc, k, e, ci, va, spal, X, NT, lane, m.p);
+		spmv_accumulate<W, TAILB, VM, MERS>(acc, k, e, ci, va, spal, X, NT, lane, m, vh);
 		if (accum)
 			acc_add(acc, Y[(size_t)r * NT + lane]);
 		const u64 y = acc_reduce<MERS>(acc, m);
@@ -979,9 +1011,9 @@ k_spmv_dot(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__
  * A row that is one segment is finished here; the 128-bit sums of a split row go to `scratch` and
  * k_spmv_heavy_combine adds them.  DOT: the launches follow k_spmv_dot and add these rows' share of v^T Av and
  * Av^T Av as partial rows slot0 + blockIdx.x (n = G). */
-template <typename W, int G, int MERS, bool DOT, bool SGN>
+template <typename W, int G, int MERS, bool DOT, int VM>
 __global__ void __launch_bounds__(BLOCK)
-k_spmv_heavy(const int *__restrict__ ci, const u32 *__restrict__ va, const u32 *__restrict__ pal,
+k_spmv_heavy(const int *__restrict__ ci, const u32 *__restrict__ va, const u32 *__restrict__ vh, const u32 *__restrict__ pal,
 	     const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd, const HeavySeg *__restrict__ segs,
 	     int nseg, u64 *__restrict__ scratch, int n, int accum, ModP m, u64 *__restrict__ partial, int slot0,
 	     const DevCtl *__restrict__ ctl)
@@ -992,10 +1024,13 @@ k_spmv_heavy(const int *__restrict__ ci, const u32 *__restrict__ va, const u32 *
 	using DS = DotState<typename std::conditional<sizeof(W) == 4, AccS, Acc>::type, MERS, NT, BLOCK, true>;
 	__shared__ u64 red[DS::WAVES][DS::SLOTS][NT];
 	__shared__ Acc slices[BLOCK / G][G];
-	__shared__ u32 spal_store[BLOCK];
+	__shared__ u32 spal_store[VM == VM_WIDE ? 2 * BLOCK : BLOCK];	/* wide: the 256 low limbs, then the 256 high limbs */
 	const u32 *spal = pal ? spal_store : nullptr;
-	if (pal)
+	if (pal) {
 		spal_store[threadIdx.x] = pal[threadIdx.x];
+		if (VM == VM_WIDE)
+			spal_store[BLOCK + threadIdx.x] = pal[BLOCK + threadIdx.x];
+	}
 	__syncthreads();
 	const int lane = threadIdx.x & (G - 1);
 	const int xl = lane < n ? lane : 0;
@@ -1004,7 +1039,7 @@ k_spmv_heavy(const int *__restrict__ ci, const u32 *__restrict__ va, const u32 *
 		ds.init();
 	for (int h = blockIdx.x; h < nseg; h += gridDim.x) {
 		const HeavySeg sg = segs[h];
-		Acc acc = heavy_range_sum<W, G, SGN>(sg.k0, sg.k1, ci, va, spal, X, n, xl, slices, m.p);
+		Acc acc = heavy_range_sum<W, G, VM, MERS>(sg.k0, sg.k1, ci, va, spal, X, n, xl, slices, m, vh);
 		if (threadIdx.x < G && lane < n) {
 			if (!sg.whole_row) {
 				scratch[((size_t)h * G + lane) * 2] = acc.lo;
@@ -1064,10 +1099,10 @@ k_spmv_heavy_combine(const HeavyRow *__restrict__ mrows, int nm, const u64 *__re
 /* Medium rows (longer than the outlier threshold, at most 256 entries per lane group of a wavefront): one wavefront
  * per row -- its 64/G lane groups each sum a slice, the slices are added across lanes, group 0 finishes the row.  A
  * workgroup per row (k_spmv_heavy) spends most of its time in barriers on rows of a few hundred entries. */
-template <typename W, int G, int MERS, bool DOT, bool SGN>
+template <typename W, int G, int MERS, bool DOT, int VM>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_wave(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__restrict__ va,
-	    const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd,
+	    const u32 *__restrict__ vh, const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd,
 	    const int *__restrict__ list, int nlist, int n, int accum, ModP m, u64 *__restrict__ partial, int slot0,
 	    const DevCtl *__restrict__ ctl)
 {
@@ -1076,10 +1111,13 @@ k_spmv_wave(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *_
 	constexpr int NT = DOT ? G : 1, GPW = 64 / G;
 	using DS = DotState<typename std::conditional<sizeof(W) == 4, AccS, Acc>::type, MERS, NT, BLOCK, true>;
 	__shared__ u64 red[DS::WAVES][DS::SLOTS][NT];
-	__shared__ u32 spal_store[BLOCK];
+	__shared__ u32 spal_store[VM == VM_WIDE ? 2 * BLOCK : BLOCK];	/* wide: the 256 low limbs, then the 256 high limbs */
 	const u32 *spal = pal ? spal_store : nullptr;
-	if (pal)
+	if (pal) {
 		spal_store[threadIdx.x] = pal[threadIdx.x];
+		if (VM == VM_WIDE)
+			spal_store[BLOCK + threadIdx.x] = pal[BLOCK + threadIdx.x];
+	}
 	__syncthreads();
 	const int lane = threadIdx.x & (G - 1), wl = threadIdx.x & 63, grp = wl / G;
 	const int xl = lane < n ? lane : 0;
@@ -1093,7 +1131,7 @@ k_spmv_wave(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *_
 		const u32 per = (e0 - k0 + GPW - 1) / GPW, lo = k0 + (u32)grp * per;
 		Acc acc;
 		acc_zero(acc);
-		spmv_accumulate<W, false, SGN>(acc, lo < e0 ? lo : e0, (lo + per) < e0 ? (lo + per) : e0, ci, va, spal, X, n, xl, m.p);
+		spmv_accumulate<W, false, VM, MERS>(acc, lo < e0 ? lo : e0, (lo + per) < e0 ? (lo + per) : e0, ci, va, spal, X, n, xl, m, vh);
 #pragma unroll
 		for (int off = G; off < 64; off <<= 1)
 			acc_add_acc(acc, shfl_xor64(acc.lo, off), shfl_xor64(acc.hi, off));
@@ -1128,23 +1166,30 @@ static hipError_t spmv_dot_dispatch(const KernelCfg &c, const DevCsr &A, const W
 		for (int x = 0; x < 9; x++)
 			xr.begin[x] = A.xr_rows[x];
 	*nblocks = (int)(blocks + hb + cb + mb);
-	const bool sgn = sizeof(W) == 8 && A.sgn;
+	const bool sgn = sizeof(W) == 8 && A.sgn, wide = sizeof(W) == 8 && A.wide;
 #define SPMV_DOT_GO(NN, TT, SS)                                                                                      \
 	hipLaunchKernelGGL((k_spmv_dot<W, MERS, NN, TT, SS>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, A.row_ptr, A.col_idx, \
-			   A.val, A.palette, X, Y, Vd, (long long)A.rows, accum, A.heavy_thr, c.m, partial, xr, ctl)
+			   A.val, A.val_hi, A.palette, X, Y, Vd, (long long)A.rows, accum, A.heavy_thr, c.m, partial, xr, ctl)
 #define SPMV_DOT(NN)                                                                                                \
 	case NN:                                                                                                    \
-		if (sgn) {                                                                                          \
+		if (wide) {                                                                                         \
 			if constexpr (sizeof(W) == 8) {                                                             \
 				if (A.tail_batch)                                                                   \
-					SPMV_DOT_GO(NN, true, true);                                                \
+					SPMV_DOT_GO(NN, true, VM_WIDE);                                             \
 				else                                                                                \
-					SPMV_DOT_GO(NN, false, true);                                               \
+					SPMV_DOT_GO(NN, false, VM_WIDE);                                            \
+			}                                                                                           \
+		} else if (sgn) {                                                                                   \
+			if constexpr (sizeof(W) == 8) {                                                             \
+				if (A.tail_batch)                                                                   \
+					SPMV_DOT_GO(NN, true, VM_SIGNED);                                           \
+				else                                                                                \
+					SPMV_DOT_GO(NN, false, VM_SIGNED);                                          \
 			}                                                                                           \
 		} else if (A.tail_batch)                                                                            \
-			SPMV_DOT_GO(NN, true, false);                                                               \
+			SPMV_DOT_GO(NN, true, VM_U32);                                                              \
 		else                                                                                                \
-			SPMV_DOT_GO(NN, false, false);                                                              \
+			SPMV_DOT_GO(NN, false, VM_U32);                                                             \
 		if (hb || mb)                                                                                       \
 			launch_heavy<W, NN, MERS, true>(c, A, X, Y, Vd, accum, partial, (int)blocks, hb, ctl, s);      \
 		break;
@@ -1440,7 +1485,7 @@ k_spmv_staged(const u32 *__restrict__ rp, const u32 *__restrict__ ci, const u32 
 						staged_accumulate<W, VALS, U, SGN>(acc, gi, stop_at, sci, sva, spal_store, X, n, xl, m.p);
 					else		/* the row runs past the staged window: its entries come from global memory */
 						spmv_accumulate<W, false, SGN>(acc, K0 + gi, K0 + stop_at, (const int *)ci, VALS == V_ARRAY ? va : nullptr,
-									       VALS == V_PACKED ? spal_store : nullptr, X, n, xl, m.p);
+									       VALS == V_PACKED ? spal_store : nullptr, X, n, xl, m);
 					gi = stop_at;
 				}
 			}
@@ -1499,7 +1544,7 @@ k_spmv_staged(const u32 *__restrict__ rp, const u32 *__restrict__ ci, const u32 
 					staged_accumulate<W, VALS, U, SGN>(acc, k - K0, e - K0, sci, sva, spal_store, X, n, xl, m.p);
 				else
 					spmv_accumulate<W, false, SGN>(acc, k, e, (const int *)ci, VALS == V_ARRAY ? va : nullptr,
-								       VALS == V_PACKED ? spal_store : nullptr, X, n, xl, m.p);
+								       VALS == V_PACKED ? spal_store : nullptr, X, n, xl, m);
 				if (lane < n) {
 					if (accum)
 						acc_add(acc, Y[(size_t)r * n + lane]);

@@ -92,6 +92,36 @@ static inline int next_int(cursor *c, long long *out)
 	return next_int_wide(c, out, NULL);
 }
 
+/* wide value mode (blz_mm_load_wide): any decimal integer that fits an int64, sign included; *over is set when it does
+ * not (the token is still consumed) -- never a wrap */
+static inline int next_int64(cursor *c, int64_t *out, int *over)
+{
+	const char *p = c->p, *end = c->end;
+	while (p < end && (*p == ' ' || *p == '\n' || *p == '\t' || *p == '\r' || *p == '\v' || *p == '\f'))
+		p++;
+	int neg = 0;
+	if (p < end && (*p == '-' || *p == '+')) {
+		neg = *p == '-';
+		p++;
+	}
+	if (p >= end || *p < '0' || *p > '9')
+		return -1;
+	const uint64_t lim = neg ? (1ull << 63) : (1ull << 63) - 1;
+	uint64_t acc = 0;
+	int big = 0;
+	while (p < end && *p >= '0' && *p <= '9') {
+		const unsigned d = (unsigned)(*p++ - '0');
+		if (acc > (lim - d) / 10)
+			big = 1;
+		else
+			acc = acc * 10 + d;
+	}
+	*out = neg ? (int64_t)(0 - acc) : (int64_t)acc;
+	*over = big;
+	c->p = p;
+	return 0;
+}
+
 /* signed value mode (blz_mm_load_signed): the entry must be an int32; it is stored as its bit pattern */
 static inline int fits_int32(long long v, int wide)
 {
@@ -225,10 +255,15 @@ static int check_banner(const char *line, int want_array)
 	return BLZ_OK;
 }
 
-/* sgn != 0: signed value mode -- `prime` is not used, the value field is kept as the int32's bit pattern */
-static int mm_load(const char *path, uint64_t prime, int sgn, blz_coo *out)
+/* sgn == 1: signed value mode -- `prime` is not used, the value field is kept as the int32's bit pattern.
+ * x_hi != NULL (sgn == 0): wide value mode -- the value field is an int64 a, stored as the canonical residue a mod prime in two
+ * limbs, the low one in out->x and the high one in *x_hi (NULL when no residue reaches 2^32).  Such files go through the
+ * one-token-at-a-time reader whatever their size. */
+static int mm_load(const char *path, uint64_t prime, int sgn, blz_coo *out, uint32_t **x_hi)
 {
 	memset(out, 0, sizeof *out);
+	if (x_hi)
+		*x_hi = NULL;
 	int fd = open(path, O_RDONLY);
 	if (fd < 0)
 		return blz_fail(BLZ_EIO, "impossible d'ouvrir %s: %s", path, strerror(errno));
@@ -274,10 +309,47 @@ static int mm_load(const char *path, uint64_t prime, int sgn, blz_coo *out)
 	out->i = malloc(cap * sizeof *out->i);
 	out->j = malloc(cap * sizeof *out->j);
 	out->x = malloc(cap * sizeof *out->x);
-	if (!out->i || !out->j || !out->x) {
+	uint32_t *hi = x_hi ? malloc(cap * sizeof *hi) : NULL;
+	if (!out->i || !out->j || !out->x || (x_hi && !hi)) {
 		munmap(base, (size_t)st.st_size);
 		blz_coo_free(out);
+		free(hi);
 		return blz_fail(BLZ_ENOMEM, "Cannot allocate sparse matrix");
+	}
+	if (x_hi) {
+		uint32_t any_hi = 0;
+		for (long long u = 0; u < nz; u++) {
+			long long a, b;
+			int64_t v = 0;
+			int over = 0, bad = next_int(&c, &a) || next_int(&c, &b) || next_int64(&c, &v, &over);
+			if (!bad && !over && a >= 1 && a <= nr && b >= 1 && b <= nc) {
+				out->i[u] = (int32_t)(a - 1);
+				out->j[u] = (int32_t)(b - 1);
+				const int64_t r = v % (int64_t)prime;		/* prime < 2^62 */
+				const uint64_t res = (uint64_t)(r < 0 ? r + (int64_t)prime : r);
+				out->x[u] = (uint32_t)res;
+				hi[u] = (uint32_t)(res >> 32);
+				any_hi |= hi[u];
+				continue;
+			}
+			long long line_no = 1;
+			for (const char *q = base; q < c.p && q < c.end; q++)
+				line_no += *q == '\n';
+			munmap(base, (size_t)st.st_size);
+			blz_coo_free(out);
+			free(hi);
+			if (bad)
+				return blz_fail(BLZ_EIO, "parse error entry %lld (line %lld)", u, line_no);
+			if (over)
+				return blz_fail(BLZ_EIO, "entry %lld (line %lld): the value does not fit an int64 (wide value mode)", u, line_no);
+			return blz_fail(BLZ_EIO, "entry %lld: index (%lld, %lld) outside %lld x %lld", u, a, b, nr, nc);
+		}
+		munmap(base, (size_t)st.st_size);
+		if (any_hi)
+			*x_hi = hi;
+		else
+			free(hi);
+		return BLZ_OK;
 	}
 	if (nz >= 200000 && parse_entries_parallel(c.p, c.end, nr, nc, nz, prime, sgn, out) == 0) {
 		munmap(base, (size_t)st.st_size);
@@ -320,15 +392,24 @@ int blz_mm_load(const char *path, uint64_t prime, blz_coo *out)
 {
 	if (!path || !out || prime < 2)
 		return blz_fail(BLZ_EINVAL, "blz_mm_load: bad argument");
-	return mm_load(path, prime, 0, out);
+	return mm_load(path, prime, 0, out, NULL);
 }
 
 int blz_mm_load_signed(const char *path, blz_coo *out)
 {
 	if (!path || !out)
 		return blz_fail(BLZ_EINVAL, "blz_mm_load_signed: bad argument");
-	return mm_load(path, 0, 1, out);
+	return mm_load(path, 0, 1, out, NULL);
 }
+
+int blz_mm_load_wide(const char *path, uint64_t prime, blz_coo *out, uint32_t **x_hi)
+{
+	if (!path || !out || !x_hi || prime < 2 || prime >= (1ull << 62))
+		return blz_fail(BLZ_EINVAL, "blz_mm_load_wide: bad argument");
+	return mm_load(path, prime, 0, out, x_hi);
+}
+
+void blz_values_free(uint32_t *x_hi) { free(x_hi); }
 
 int blz_mm_save_coo(const char *path, const blz_coo *M)
 {
@@ -1472,6 +1553,8 @@ void blz_prepared_free(blz_prepared *P)
 			blz_csr_free(&P->full[q]);
 		}
 	}
+	free(P->val_hi[0]);
+	free(P->val_hi[1]);
 	free(P);
 }
 
@@ -1544,6 +1627,33 @@ int blz_prepare(const blz_coo *M, int right, int nranks, int chunks, int reorder
 		return rc;
 	}
 	*out = P;
+	return BLZ_OK;
+}
+
+/* Wide value mode.  P was prepared from triplets whose x[k] was k, the number of the entry, instead of its value (they fit a
+ * u32 because row_ptr is one): every function that moves values moved the numbers.  One gather through them puts the low
+ * limbs where the numbers are and builds the parallel arrays of high limbs -- one set of perms and one pair of CSRs serve
+ * both limbs. */
+int blz_prepared_fill_wide(blz_prepared *P, const uint32_t *lo, const uint32_t *hi)
+{
+	if (!P || !lo || !hi || P->map || P->only_rank >= 0)
+		return blz_fail(BLZ_EINVAL, "blz_prepared_fill_wide: bad argument");
+	for (int t = 0; t < 2; t++) {
+		blz_csr *A = &P->full[t];
+		if (!A->val)
+			continue;	/* no entries */
+		free(P->val_hi[t]);
+		P->val_hi[t] = malloc((size_t)(A->nnz ? A->nnz : 1) * sizeof(uint32_t));
+		if (!P->val_hi[t])
+			return blz_fail(BLZ_ENOMEM, "blz_prepared_fill_wide: out of memory");
+		for (int64_t k = 0; k < A->nnz; k++) {
+			const uint32_t e = A->val[k];
+			if ((int64_t)e >= P->nnz)
+				return blz_fail(BLZ_EINVAL, "blz_prepared_fill_wide: entry number out of range");
+			A->val[k] = lo[e];
+			P->val_hi[t][k] = hi[e];
+		}
+	}
 	return BLZ_OK;
 }
 
@@ -1734,6 +1844,8 @@ int blz_prepared_save(const blz_prepared *P, const char *path, uint64_t key)
 		return blz_fail(BLZ_EINVAL, "blz_prepared_save: bad argument");
 	if (P->only_rank >= 0)
 		return blz_fail(BLZ_EINVAL, "blz_prepared_save: a one-rank object (blz_prepare_rank) is not a cache of the matrix");
+	if (P->val_hi[0] || P->val_hi[1])
+		return blz_fail(BLZ_EINVAL, "blz_prepared_save: the matrix has wide entries (high limbs); the cache format does not hold them");
 	prep_header h;
 	memset(&h, 0, sizeof h);
 	memcpy(h.magic, PREP_MAGIC, 8);
@@ -2076,8 +2188,30 @@ int blz_save_block(const char *path, int64_t nrows, int n, const uint64_t *v)
  * x' <= p < 2^62 (x' = p when x = 0: not canonical, still the right residue), so a term is below 2^93 and the unreduced
  * 128-bit sums hold 2^35 terms, more than the 2^34 entries per row or column the unsigned checkers already assume.
  */
-static inline unsigned __int128 host_term(uint32_t a, uint64_t x, uint64_t prime, int sgn)
+/*
+ * Wide value mode on the host (sgn == 2): the entry is the residue a + 2^32 * hi, and the term is a * x + hi * x' with
+ * x' = 2^32 * x mod p -- the rule of acc_mac_wide (csrc/modp.h).  A term pair is below 1.25 * 2^32 * p < 2^95, so the
+ * unreduced 128-bit sums hold 2^33 terms; the GPU's own limit is 2^30 entries per row.
+ */
+static inline unsigned __int128 host_term_wide(uint32_t a, uint32_t hi, uint64_t x, uint64_t prime)
 {
+	const uint64_t xs = (uint64_t)(((unsigned __int128)x << 32) % prime);
+	return (unsigned __int128)a * x + (unsigned __int128)hi * xs;
+}
+
+/* the matrix of a checker: sgn = 0 as blz_mm_load, 1 as blz_mm_load_signed, 2 as blz_mm_load_wide (*hi: its high limbs) */
+static int checker_load(const char *path, uint64_t prime, int sgn, blz_coo *M, uint32_t **hi)
+{
+	*hi = NULL;
+	if (sgn == 2)
+		return blz_mm_load_wide(path, prime, M, hi);
+	return sgn ? blz_mm_load_signed(path, M) : blz_mm_load(path, prime, M);
+}
+
+static inline unsigned __int128 host_term(uint32_t a, const uint32_t *hi, int64_t u, uint64_t x, uint64_t prime, int sgn)
+{
+	if (sgn == 2)
+		return host_term_wide(a, hi ? hi[u] : 0u, x, prime);
 	if (sgn && (int32_t)a < 0)
 		return (unsigned __int128)(0u - a) * (prime - x);
 	return (unsigned __int128)a * x;
@@ -2089,7 +2223,8 @@ static int check_kernel(const char *matrix_path, const char *kernel_path, uint64
 	if (!matrix_path || !kernel_path || prime < 2 || (sgn && prime >= (1ull << 62)))
 		return blz_fail(BLZ_EINVAL, "blz_check_kernel: bad argument");
 	blz_coo M;
-	int rc = sgn ? blz_mm_load_signed(matrix_path, &M) : blz_mm_load(matrix_path, prime, &M);
+	uint32_t *Mhi = NULL;
+	int rc = checker_load(matrix_path, prime, sgn, &M, &Mhi);
 	if (rc != BLZ_OK)
 		return rc;
 	const int64_t nrows = right ? M.ncols : M.nrows, ncols = right ? M.nrows : M.ncols;	/* :99-104 */
@@ -2100,12 +2235,14 @@ static int check_kernel(const char *matrix_path, const char *kernel_path, uint64
 		if (fd >= 0)
 			close(fd);
 		blz_coo_free(&M);
+		free(Mhi);
 		return blz_fail(BLZ_EIO, "cannot open %s", kernel_path);
 	}
 	char *base = mmap(NULL, (size_t)st.st_size, PROT_READ, MAP_PRIVATE, fd, 0);
 	close(fd);
 	if (base == MAP_FAILED) {
 		blz_coo_free(&M);
+		free(Mhi);
 		return blz_fail(BLZ_EIO, "mmap %s: %s", kernel_path, strerror(errno));
 	}
 	cursor c = { base, base + st.st_size };
@@ -2165,7 +2302,7 @@ static int check_kernel(const char *matrix_path, const char *kernel_path, uint64
 		const int64_t i = right ? M.j[u] : M.i[u], j = right ? M.i[u] : M.j[u];
 		const uint32_t v = M.x[u];
 		for (long long k = 0; k < n; k++)
-			y[j * n + k] += host_term(v, x[i * n + k], prime, sgn);
+			y[j * n + k] += host_term(v, Mhi, u, x[i * n + k], prime, sgn);
 	}
 	for (int64_t j = 0; j < ncols && rc == BLZ_OK; j++)
 		for (long long k = 0; k < n; k++)
@@ -2182,6 +2319,7 @@ done:
 	free(y);
 	munmap(base, (size_t)st.st_size);
 	blz_coo_free(&M);
+	free(Mhi);
 	return rc;
 }
 
@@ -2195,6 +2333,12 @@ int blz_check_kernel_signed(const char *matrix_path, const char *kernel_path, ui
 			    int *bad_col)
 {
 	return check_kernel(matrix_path, kernel_path, prime, right, bad_row, bad_col, 1);
+}
+
+int blz_check_kernel_wide(const char *matrix_path, const char *kernel_path, uint64_t prime, int right, int64_t *bad_row,
+			  int *bad_col)
+{
+	return check_kernel(matrix_path, kernel_path, prime, right, bad_row, bad_col, 2);
 }
 
 /* ---------------------------------------------------------------- right-hand sides and solutions */
@@ -2287,7 +2431,8 @@ static int check_solution(const char *matrix_path, const char *rhs_path, const c
 	if (!matrix_path || !rhs_path || !x_path || prime < 2 || prime >= (1ull << 62))
 		return blz_fail(BLZ_EINVAL, "blz_check_solution: bad argument");
 	blz_coo M;
-	int rc = sgn ? blz_mm_load_signed(matrix_path, &M) : blz_mm_load(matrix_path, prime, &M);
+	uint32_t *Mhi = NULL;
+	int rc = checker_load(matrix_path, prime, sgn, &M, &Mhi);
 	if (rc != BLZ_OK)
 		return rc;
 	const int64_t xlen = right ? M.ncols : M.nrows, blen = right ? M.nrows : M.ncols;
@@ -2303,7 +2448,7 @@ static int check_solution(const char *matrix_path, const char *rhs_path, const c
 		/* unreduced 128-bit sums, one reduction per word: value < 2^32, x < 2^62, entries per row or column < 2^34 */
 		for (int64_t u = 0; u < M.nnz; u++) {
 			const int64_t i = right ? M.j[u] : M.i[u], j = right ? M.i[u] : M.j[u];
-			y[j] += host_term(M.x[u], x[i], prime, sgn);
+			y[j] += host_term(M.x[u], Mhi, u, x[i], prime, sgn);
 		}
 		for (int64_t j = 0; j < blen; j++)
 			if ((uint64_t)(y[j] % prime) != b[j]) {
@@ -2317,6 +2462,7 @@ static int check_solution(const char *matrix_path, const char *rhs_path, const c
 	free(b);
 	free(y);
 	blz_coo_free(&M);
+	free(Mhi);
 	return rc;
 }
 
@@ -2330,6 +2476,12 @@ int blz_check_solution_signed(const char *matrix_path, const char *rhs_path, con
 			      int64_t *bad_row)
 {
 	return check_solution(matrix_path, rhs_path, x_path, prime, right, bad_row, 1);
+}
+
+int blz_check_solution_wide(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+			    int64_t *bad_row)
+{
+	return check_solution(matrix_path, rhs_path, x_path, prime, right, bad_row, 2);
 }
 
 /* A len x k "array integer general" file, column-major, into out[r * k + i] (row-major), 1 <= k <= kmax; entries as in
@@ -2471,7 +2623,8 @@ static int check_solution_block(const char *matrix_path, const char *rhs_path, c
 	if (!matrix_path || !rhs_path || !x_path || !status || prime < 2 || prime >= (1ull << 62))
 		return blz_fail(BLZ_EINVAL, "blz_check_solution_block: bad argument");
 	blz_coo M;
-	int rc = sgn ? blz_mm_load_signed(matrix_path, &M) : blz_mm_load(matrix_path, prime, &M);
+	uint32_t *Mhi = NULL;
+	int rc = checker_load(matrix_path, prime, sgn, &M, &Mhi);
 	if (rc != BLZ_OK)
 		return rc;
 	const int64_t xlen = right ? M.ncols : M.nrows, blen = right ? M.nrows : M.ncols;
@@ -2498,7 +2651,7 @@ static int check_solution_block(const char *matrix_path, const char *rhs_path, c
 	for (int64_t u = 0; u < M.nnz; u++) {
 		const int64_t i = right ? M.j[u] : M.i[u], j = right ? M.i[u] : M.j[u];
 		for (int t = 0; t < k; t++)
-			y[j * k + t] += host_term(M.x[u], x[i * k + t], prime, sgn);
+			y[j * k + t] += host_term(M.x[u], Mhi, u, x[i * k + t], prime, sgn);
 	}
 	for (int t = 0; t < k; t++) {
 		int zero = 1;
@@ -2521,6 +2674,7 @@ done:
 	free(b);
 	free(y);
 	blz_coo_free(&M);
+	free(Mhi);
 	return rc;
 }
 
@@ -2534,6 +2688,12 @@ int blz_check_solution_block_signed(const char *matrix_path, const char *rhs_pat
 				    int right, int *status, int64_t *bad_row)
 {
 	return check_solution_block(matrix_path, rhs_path, x_path, prime, right, status, bad_row, 1);
+}
+
+int blz_check_solution_block_wide(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime,
+				  int right, int *status, int64_t *bad_row)
+{
+	return check_solution_block(matrix_path, rhs_path, x_path, prime, right, status, bad_row, 2);
 }
 
 /* rank of a kernel block: the RREF of its row space, row by row (the GPU's k_rref restated), stopping at full rank */

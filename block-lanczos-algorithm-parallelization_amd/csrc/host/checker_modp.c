@@ -8,6 +8,8 @@
  * each is checked against its own b; an all-zero column of x stands for a system that was not solved and does not fail.
  * --signed (no reference counterpart) reads the matrix in signed value mode: an entry a (an int32) means a mod P, as
  * lanczos_modp --signed solves it.
+ * --wide (no reference counterpart) reads the matrix in wide value mode: an entry is any int64 and means its residue mod P,
+ * as lanczos_modp --wide solves it.
  */
 #define _GNU_SOURCE
 #include <err.h>
@@ -23,11 +25,12 @@ int main(int argc, char **argv)
 		{"matrix", required_argument, NULL, 'm'}, {"kernel", required_argument, NULL, 'k'},
 		{"prime", required_argument, NULL, 'p'}, {"right", no_argument, NULL, 'r'},
 		{"left", no_argument, NULL, 'l'}, {"independent", no_argument, NULL, 'i'},
-		{"rhs", required_argument, NULL, 'b'}, {"signed", no_argument, NULL, 's'}, {NULL, 0, NULL, 0}
+		{"rhs", required_argument, NULL, 'b'}, {"signed", no_argument, NULL, 's'}, {"wide", no_argument, NULL, 'w'},
+		{NULL, 0, NULL, 0}
 	};
 	char *matrix = NULL, *kernel = NULL, *rhs = NULL;
 	unsigned long long prime = 0;
-	int right = 0, independent = 0, sgn = 0, ch;
+	int right = 0, independent = 0, sgn = 0, wide = 0, ch;
 	while ((ch = getopt_long(argc, argv, "", longopts, NULL)) != -1) {
 		switch (ch) {
 		case 'm': matrix = optarg; break;
@@ -38,10 +41,11 @@ int main(int argc, char **argv)
 		case 'i': independent = 1; break;
 		case 'b': rhs = optarg; break;
 		case 's': sgn = 1; break;
+		case 'w': wide = 1; break;
 		default: errx(1, "Unknown option\n");
 		}
 	}
-	if (matrix == NULL || kernel == NULL || prime == 0) {
+	if (matrix == NULL || kernel == NULL || prime == 0 || (wide && sgn)) {
 		printf("%s [OPTIONS]\n\n", argv[0]);
 		printf("Options:\n");
 		printf("--matrix FILENAME           MatrixMarket file containing the sparse matrix\n");
@@ -54,6 +58,8 @@ int main(int argc, char **argv)
 		printf("                            or x*M == b (--left) is verified\n");
 		printf("--signed                    signed value mode: a matrix entry a (an int32) means a mod P, so -1 is P-1\n");
 		printf("                            (what lanczos_modp --signed solves; P < 2**62)\n");
+		printf("--wide                      wide value mode: a matrix entry is any int64 and means its residue mod P\n");
+		printf("                            (what lanczos_modp --wide solves; P < 2**62; not with --signed)\n");
 		exit(0);
 	}
 	if (rhs) {
@@ -63,7 +69,8 @@ int main(int argc, char **argv)
 		if (k > 1) {
 			int status[BLZ_MAX_RHS], failed = 0;
 			int64_t bad_row[BLZ_MAX_RHS];
-			const int kk = sgn ? blz_check_solution_block_signed(matrix, rhs, kernel, prime, right, status, bad_row)
+			const int kk = wide ? blz_check_solution_block_wide(matrix, rhs, kernel, prime, right, status, bad_row)
+				     : sgn ? blz_check_solution_block_signed(matrix, rhs, kernel, prime, right, status, bad_row)
 					   : blz_check_solution_block(matrix, rhs, kernel, prime, right, status, bad_row);
 			if (kk < 0)
 				errx(1, "%s", blz_last_error());
@@ -79,7 +86,8 @@ int main(int argc, char **argv)
 			exit(failed ? EXIT_FAILURE : EXIT_SUCCESS);
 		}
 		int64_t bad = 0;
-		const int rcs = sgn ? blz_check_solution_signed(matrix, rhs, kernel, prime, right, &bad)
+		const int rcs = wide ? blz_check_solution_wide(matrix, rhs, kernel, prime, right, &bad)
+				: sgn ? blz_check_solution_signed(matrix, rhs, kernel, prime, right, &bad)
 				    : blz_check_solution(matrix, rhs, kernel, prime, right, &bad);
 		if (rcs == 0) {
 			printf("OK\n");
@@ -94,7 +102,8 @@ int main(int argc, char **argv)
 	printf("Reading Matrix from %s and kernel from %s\n", matrix, kernel);
 	long long row = 0;
 	int col = 0;
-	const int rc = sgn ? blz_check_kernel_signed(matrix, kernel, prime, right, (int64_t *)&row, &col)
+	const int rc = wide ? blz_check_kernel_wide(matrix, kernel, prime, right, (int64_t *)&row, &col)
+		     : sgn ? blz_check_kernel_signed(matrix, kernel, prime, right, (int64_t *)&row, &col)
 			   : blz_check_kernel(matrix, kernel, prime, right, (int64_t *)&row, &col);
 	if (rc == 0) {
 		printf("OK\n");

@@ -29,7 +29,7 @@
 static long n = 1;
 static uint64_t prime;
 static char *matrix_filename, *kernel_filename, *rhs_filename;
-static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis, rhs_gpus_given, values_signed;
+static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis, rhs_gpus_given, values_signed, values_wide;
 static int stop_after = -1, checkpoint_timer = 60, device, gpus = 1, rhs_gpus;
 
 static double wtime(void)
@@ -86,6 +86,10 @@ static void usage(char **argv)
 	printf("                            reference, and -1 is (2**32 - 1) mod P.  Works with every other option; check the\n");
 	printf("                            result with checker_modp --signed.  A checkpoint holds v and p, not the matrix: the\n");
 	printf("                            mode is NOT recorded in it, so give --load-checkpoint the flag the first run had\n");
+	printf("--wide                      wide value mode: a matrix entry is any integer that fits an int64 and means its residue\n");
+	printf("                            mod P, so every element of F_P can be an entry (-1 is P-1, P is 0).  One GPU only: not\n");
+	printf("                            with --cache, --gpus above 1, --rhs-gpus or --signed.  Check the result with\n");
+	printf("                            checker_modp --wide.  Like --signed, the mode is NOT recorded in a checkpoint\n");
 	printf("--device D                  first HIP device to run on [default 0]\n");
 	printf("--gpus G                    row-partition the matrix over G GPUs of this node (devices D..D+G-1), RCCL\n");
 	printf("                            all-gather of the block before each product [default 1]\n");
@@ -110,6 +114,7 @@ static void process_command_line_options(int argc, char **argv)
 		{"gpus", required_argument, NULL, 'g'}, {"verify", no_argument, NULL, 'V'},
 		{"cache", no_argument, NULL, 'C'}, {"basis", no_argument, NULL, 'B'}, {"rhs", required_argument, NULL, 'R'},
 		{"rhs-gpus", required_argument, NULL, 'G'}, {"signed", no_argument, NULL, 'S'},
+		{"wide", no_argument, NULL, 'W'},
 		{"help", no_argument, NULL, 'h'}, {NULL, 0, NULL, 0}
 	};
 	int ch;
@@ -138,6 +143,7 @@ static void process_command_line_options(int argc, char **argv)
 		case 'R': rhs_filename = optarg; break;
 		case 'G': rhs_gpus = atoi(optarg); rhs_gpus_given = true; break;
 		case 'S': values_signed = true; break;
+		case 'W': values_wide = true; break;
 		case 'h': usage(argv); break;
 		default: errx(1, "Unknown option\n");
 		}
@@ -151,6 +157,8 @@ static void process_command_line_options(int argc, char **argv)
 	if (rhs_filename != NULL && (stop_after > 0 || basis || gpus > 1))
 		usage(argv);
 	if (rhs_gpus_given && (rhs_filename == NULL || gpus > 1))
+		usage(argv);
+	if (values_wide && (use_cache || gpus > 1 || rhs_gpus_given || values_signed))
 		usage(argv);
 	if (prime >= (1ull << 62))
 		errx(1, "p is capped at 2**62 - 1.");
@@ -434,7 +442,10 @@ int main(int argc, char **argv)
 	fflush(stdout);
 	blz_coo M;
 	const double t_load = wtime();
-	if (values_signed)
+	uint32_t *x_hi = NULL;		/* --wide: the high limbs of the residues (NULL when none reaches 2**32) */
+	if (values_wide)
+		CHECK(blz_mm_load_wide(matrix_filename, prime, &M, &x_hi));
+	else if (values_signed)
 		CHECK(blz_mm_load_signed(matrix_filename, &M));
 	else
 		CHECK(blz_mm_load(matrix_filename, prime, &M));
@@ -497,7 +508,13 @@ int main(int argc, char **argv)
 		if (fh && blz_prepared_load(cache_path, key, &P) == BLZ_OK)
 			fprintf(stderr, "  - Set-up mapped from %s in %.2fs\n", cache_path, wtime() - t_prep);
 	}
-	if (!P) {
+	if (x_hi) {
+		/* the one-call form carries the high limbs through the renumbering and the CSR builds (one GPU, no cache) */
+		CHECK(blz_set_values_wide(ctx, x_hi, M.nnz));
+		CHECK(blz_set_matrix(ctx, &M, right_kernel, 0, 1));
+		fprintf(stderr, "  - Renumbering, CSR(M), CSR(M^T), partition: %.2fs\n", wtime() - t_prep);
+		blz_values_free(x_hi);
+	} else if (!P) {
 		CHECK(blz_prepare_for(ctx, &M, right_kernel, gpus, &P));
 		fprintf(stderr, "  - Renumbering, CSR(M), CSR(M^T), partition: %.2fs\n", wtime() - t_prep);
 		if (use_cache) {
@@ -508,7 +525,8 @@ int main(int argc, char **argv)
 		}
 	}
 	team.P = P;
-	team_run(OP_MATRIX);
+	if (P)
+		team_run(OP_MATRIX);
 	if (rhs && rhs_gpus_given) {
 		team.rhs = rhs;
 		team.rhs_k = rhs_k;

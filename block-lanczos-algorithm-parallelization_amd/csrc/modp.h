@@ -102,6 +102,56 @@ MODP_DEV void acc_mac_val(Acc &a, u32 v, u64 x, u64 p)
 	}
 }
 
+template <int MERS>
+MODP_DEV u64 reduce128(u64 hi, u64 lo, const ModP &m);
+
+/*
+ * Wide value mode: a matrix entry is any canonical residue a, 0 <= a < p < 2^62, kept as two 32-bit limbs
+ * a = lo + 2^32 * hi with hi < 2^(k-32) (k = bit length of p).  The term a * x goes into the SAME 128-bit accumulator as
+ *     acc += lo * x + hi * x'        x' = 2^32 * x mod p
+ * i.e. one x' and one more acc_mac32 per gathered word.
+ *   MERS == 61: 2^61 = 1 (mod p), so x' is the 61-bit word rotated left by 32: ((x & (2^29 - 1)) << 32) | (x >> 29).  It is
+ *               below 2^61 and the right residue; it need not be canonical.  The rotation needs x < 2^61: the words of the
+ *               gathered block must be residues.  Every kernel writes canonical words (reduce128), so the blocks of an
+ *               iteration are; blz_set_block does not validate what the caller gives it, and its contract (blz.h) asks for
+ *               words below p -- the unsigned forms happen to tolerate any u64 word, this one does not.
+ *   otherwise:  reduce128<0>(x >> 32, x << 32, m), i.e. Barrett on T = 2^32 * x < 2^94.  Barrett wants T < 2^(63+k), which
+ *               holds because 8-byte words mean p >= 2^32, i.e. k >= 33 and 63 + k >= 96.  The result is canonical.
+ * Bound: lo <= 2^32 - 1, hi <= 2^(k-32) - 1 and x, x' <= p, so a term PAIR is below (2^32 + 2^(k-32)) * p <= 1.25 * 2^32 * p
+ * (k <= 62).  A row of up to 2^30 entries therefore sums to less than 1.25 * 2^62 * p: plus `accum`'s one residue that is
+ * below 2^63 * p <= 2^(63+k) (Barrett's bound, p < 2^k) and below 2^125 (the 128 bits), at every reducer class.
+ * upload_csr refuses a wide slab with a longer row.  Partial sums (split rows, the outlier tiers' slices and scratch) add
+ * terms of the same sum, so they stay as they are, and there is still one reduction per output word.
+ * A slot switched off by a zero multiplier must have BOTH limbs zeroed.
+ */
+template <int MERS>
+MODP_DEV u64 shift32_modp(u64 x, const ModP &m)
+{
+	if (MERS == 61)
+		return ((x & ((1ull << 29) - 1)) << 32) | (x >> 29);
+	return reduce128<0>(x >> 32, x << 32, m);
+}
+
+template <int MERS>
+MODP_DEV void acc_mac_wide(Acc &a, u32 lo, u32 hi, u64 x, const ModP &m)
+{
+	acc_mac32(a, lo, x);
+	acc_mac32(a, hi, shift32_modp<MERS>(x, m));
+}
+
+/* The value modes of the SpMV kernels, a compile-time choice: one entry point for all three.  VM_U32 is acc_mac32 (nothing
+ * else is read), VM_SIGNED is acc_mac_val<true> (reads m.p), VM_WIDE is acc_mac_wide (reads hi and m). */
+enum { VM_U32 = 0, VM_SIGNED = 1, VM_WIDE = 2 };
+
+template <int VM, int MERS>
+MODP_DEV void acc_mac_entry(Acc &a, u32 v, u32 hi, u64 x, const ModP &m)
+{
+	if (VM == VM_WIDE)
+		acc_mac_wide<MERS>(a, v, hi, x, m);
+	else
+		acc_mac_val<VM == VM_SIGNED>(a, v, x, m.p);
+}
+
 /* a += x (pattern matrices: every entry is 1) */
 MODP_DEV void acc_add(Acc &a, u64 x)
 {

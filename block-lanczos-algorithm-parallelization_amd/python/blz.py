@@ -82,6 +82,7 @@ def lib():
         L.blz_destroy.restype = None
         L.blz_coo_free.restype = None
         L.blz_csr_free.restype = None
+        L.blz_values_free.restype = None
         _lib = L
     return _lib
 
@@ -106,7 +107,10 @@ def device_count():
 class Matrix:
     """struct sparsematrix_t of the reference (sequential/lanczos_modp.c:55-62) as numpy arrays."""
 
-    def __init__(self, nrows, ncols, i, j, x):
+    def __init__(self, nrows, ncols, i, j, x, x_hi=None):
+        """x_hi (wide value mode): the high limbs of the entries, parallel to x -- entry k is x[k] + 2**32 * x_hi[k]."""
+        self.x_hi = None if x_hi is None else np.ascontiguousarray(x_hi, dtype=np.uint32)
+        assert self.x_hi is None or self.x_hi.shape == (len(i),)
         self.i = np.ascontiguousarray(i, dtype=np.int32)
         self.j = np.ascontiguousarray(j, dtype=np.int32)
         self.x = np.ascontiguousarray(x, dtype=np.uint32)
@@ -136,6 +140,26 @@ class Matrix:
         M = Coo()
         check(lib().blz_mm_load_signed(path.encode(), C.byref(M)))
         return Matrix._take(M)
+
+    @staticmethod
+    def load_wide(path, prime):
+        """blz_mm_load_wide(): every entry an int64 read as its residue mod prime; x holds the low limbs and x_hi the high
+        ones (None when no residue reaches 2**32)."""
+        M = Coo()
+        hi = C.POINTER(C.c_uint32)()
+        check(lib().blz_mm_load_wide(path.encode(), C.c_uint64(prime), C.byref(M), C.byref(hi)))
+        n = int(M.nnz)
+        x_hi = np.ctypeslib.as_array(hi, (max(n, 1),))[:n].copy() if hi else None
+        lib().blz_values_free(hi)
+        out = Matrix._take(M)
+        if x_hi is not None:
+            out.x_hi = x_hi
+        return out
+
+    def residues(self):
+        """the entries as Python-sized integers in an int64 array (x + 2**32 * x_hi)"""
+        r = self.x.astype(np.int64)
+        return r if self.x_hi is None else r + (self.x_hi.astype(np.int64) << 32)
 
     @staticmethod
     def synth(nrows, ncols, nnz, seed, prime, pattern=False):
@@ -345,12 +369,12 @@ def save_block(path, nrows, n, v):
     check(lib().blz_save_block(path.encode(), C.c_int64(nrows), C.c_int(n), ptr(u64(v))))
 
 
-def check_kernel(matrix_path, kernel_path, prime, right=False, signed=False, where=False):
+def check_kernel(matrix_path, kernel_path, prime, right=False, signed=False, where=False, wide=False):
     """blz_check_kernel(): 0 OK, 1 all-zero kernel, 2 product not zero; raises on file/format errors.
     signed=True: the matrix in signed value mode (blz_check_kernel_signed).  where=True: (rc, row, column), the place
     of the first non-zero word when rc == 2."""
     row, col = C.c_int64(0), C.c_int(0)
-    fn = lib().blz_check_kernel_signed if signed else lib().blz_check_kernel
+    fn = lib().blz_check_kernel_wide if wide else lib().blz_check_kernel_signed if signed else lib().blz_check_kernel
     rc = fn(matrix_path.encode(), kernel_path.encode(), C.c_uint64(prime), C.c_int(int(right)), C.byref(row), C.byref(col))
     if rc < 0:
         check(rc)
@@ -373,11 +397,11 @@ def rhs_load(path, prime, length):
     return b[:length]
 
 
-def check_solution(matrix_path, rhs_path, x_path, prime, right=False, signed=False):
+def check_solution(matrix_path, rhs_path, x_path, prime, right=False, signed=False, wide=False):
     """blz_check_solution(): (0, None) when M x == b (right) / x M == b, else (2, first differing row); raises on
     file / format errors.  signed=True: the matrix in signed value mode."""
     row = C.c_int64(-1)
-    fn = lib().blz_check_solution_signed if signed else lib().blz_check_solution
+    fn = lib().blz_check_solution_wide if wide else lib().blz_check_solution_signed if signed else lib().blz_check_solution
     rc = fn(matrix_path.encode(), rhs_path.encode(), x_path.encode(), C.c_uint64(prime), C.c_int(int(right)), C.byref(row))
     if rc < 0:
         check(rc)
@@ -396,12 +420,13 @@ def rhs_load_block(path, prime, length, kmax=MAX_RHS):
     return b[:length * k.value].reshape(length, k.value)
 
 
-def check_solution_block(matrix_path, rhs_path, x_path, prime, right=False, signed=False):
+def check_solution_block(matrix_path, rhs_path, x_path, prime, right=False, signed=False, wide=False):
     """blz_check_solution_block(): one (status, row) per right-hand side -- (0, None) equal, (2, first differing row),
     (3, None) the x column is all zero; raises on file / format errors.  signed=True: the matrix in signed value mode."""
     status = (C.c_int * MAX_RHS)()
     rows = (C.c_int64 * MAX_RHS)()
-    fn = lib().blz_check_solution_block_signed if signed else lib().blz_check_solution_block
+    fn = (lib().blz_check_solution_block_wide if wide else
+          lib().blz_check_solution_block_signed if signed else lib().blz_check_solution_block)
     k = fn(matrix_path.encode(), rhs_path.encode(), x_path.encode(), C.c_uint64(prime), C.c_int(int(right)), status, rows)
     if k < 0:
         check(k)
@@ -503,7 +528,32 @@ class Context:
             check(rc)
         return bool(rc)
 
+    def set_values_wide(self, x_hi, nnz=None):
+        """blz_set_values_wide(): the high limbs of the next matrix's entries (None clears the mode)."""
+        if x_hi is None:
+            check(lib().blz_set_values_wide(self.h, None, C.c_int64(0)))
+            return
+        x_hi = np.ascontiguousarray(x_hi, dtype=np.uint32)
+        self._x_hi = x_hi       # borrowed by the library until the matrix is set
+        check(lib().blz_set_values_wide(self.h, x_hi.ctypes.data_as(C.POINTER(C.c_uint32)),
+                                        C.c_int64(x_hi.size if nnz is None else nnz)))
+
+    def values_wide(self):
+        return bool(lib().blz_values_wide(self.h))
+
+    def slab_wide(self, transpose, piece=0):
+        """blz_slab_wide(): True when that slab's products run the wide instantiations of the SpMV kernels."""
+        rc = int(lib().blz_slab_wide(self.h, C.c_int(int(transpose)), C.c_int(piece)))
+        if rc < 0:
+            check(rc)
+        return bool(rc)
+
+    def _hand_over_wide(self, M):
+        if getattr(M, "x_hi", None) is not None:
+            self.set_values_wide(M.x_hi)
+
     def set_matrix(self, M, right=False, rank=0, nranks=1):
+        self._hand_over_wide(M)
         check(lib().blz_set_matrix(self.h, C.byref(M.c), C.c_int(int(right)), C.c_int(rank), C.c_int(nranks)))
         self.right = bool(right)
 
@@ -518,6 +568,7 @@ class Context:
         operator; rows(V) then counts the border row."""
         b = u64(b)
         assert b.size == (M.nrows if right else M.ncols), (b.size, M.nrows, M.ncols, right)
+        self._hand_over_wide(M)
         check(lib().blz_set_matrix_rhs(self.h, C.byref(M.c), C.c_int(int(right)), ptr(b)))
         self.right = bool(right)
 
@@ -543,6 +594,7 @@ class Context:
         in one bordered operator; rows(V) then counts the k border rows."""
         b = np.ascontiguousarray(b, dtype=np.uint64)
         assert b.ndim == 2 and b.shape[0] == (M.nrows if right else M.ncols), (b.shape, M.nrows, M.ncols, right)
+        self._hand_over_wide(M)
         check(lib().blz_set_matrix_rhs_block(self.h, C.byref(M.c), C.c_int(int(right)), C.c_int(b.shape[1]), ptr(b.reshape(-1))))
         self.right = bool(right)
 
@@ -777,9 +829,11 @@ def comm_unique_id():
     return bytes(buf)
 
 
-def solve_rhs(M, b, prime, n, right=False, batch=16, device=0, signed=False):
+def solve_rhs(M, b, prime, n, right=False, batch=16, device=0, signed=False, wide=False):
     """M x = b (right) / x M = b on one GPU: dict(status, x, iterations, final_check).
-    signed=True: M.x holds int32 bit patterns (signed value mode)."""
+    signed=True: M.x holds int32 bit patterns (signed value mode).
+    wide: the wide value mode comes from the matrix (M.x_hi, handed over by set_matrix_rhs); the argument only says so at
+    the call site and changes nothing -- a matrix whose residues all fit 32 bits has x_hi None and is an ordinary one."""
     with Context(prime, n, device) as ctx:
         if signed:
             ctx.set_values_signed()
@@ -792,11 +846,13 @@ def solve_rhs(M, b, prime, n, right=False, batch=16, device=0, signed=False):
         return dict(status=status, x=x, iterations=ctx.iterations, final_check=fc)
 
 
-def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0, basis=False, signed=False):
+def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0, basis=False, signed=False, wide=False):
     """block_lanczos(), sequential/lanczos_modp.c:585-669, on one GPU.  Returns dict(v, tmp, iterations).
     basis=True (not with stop_after): also reduce the final block to independent kernel vectors (blz_kernel_basis) --
     adds basis (rows x k array), k and z to the result; v, tmp and p stay those of the plain solve.
-    signed=True: M.x holds int32 bit patterns (Matrix.load_signed) and an entry a means a mod p."""
+    signed=True: M.x holds int32 bit patterns (Matrix.load_signed) and an entry a means a mod p.
+    wide: the wide value mode comes from the matrix (M.x_hi, handed over by set_matrix); the argument only says so at the
+    call site and changes nothing -- a matrix whose residues all fit 32 bits has x_hi None and is an ordinary one."""
     if basis and stop_after > 0:
         raise ValueError("basis=True needs a run to the end (stop_after < 0)")
     with Context(prime, n, device) as ctx:

@@ -81,6 +81,13 @@ int blz_mm_load(const char *path, uint64_t prime, blz_coo *out);
  * An entry outside int32 is BLZ_EIO, never a silent wrap; int32 is the whole domain of the mode.  (For prime >= 2^32
  * blz_mm_load stores the same words: `% prime` is the identity on a u32.) */
 int blz_mm_load_signed(const char *path, blz_coo *out);
+/* Wide value mode: the same files and banner rules, but an entry is any decimal integer that fits an int64, sign included,
+ * and what is stored is its canonical residue a mod prime (2 <= prime < 2^62): -1 is p - 1, p is 0, p + 5 is 5.  The residue
+ * travels as two 32-bit limbs: the low one in out->x[k], the high one in (*x_hi)[k] -- an array parallel to x, to be handed to
+ * blz_set_values_wide and freed with blz_values_free.  *x_hi is NULL when no residue reaches 2^32 (always so for prime < 2^32):
+ * the triplets are then ordinary ones.  A token outside int64 is BLZ_EIO, naming the entry and its line, never a wrap. */
+int blz_mm_load_wide(const char *path, uint64_t prime, blz_coo *out, uint32_t **x_hi);
+void blz_values_free(uint32_t *x_hi);
 void blz_coo_free(blz_coo *M);
 
 /* Write triplets as a MatrixMarket "coordinate integer general" file (1-based, values as stored).  Used to hand a
@@ -221,6 +228,9 @@ int blz_check_kernel(const char *matrix_path, const char *kernel_path, uint64_t 
  * (-1 is p - 1).  prime < 2^62.  Same return values. */
 int blz_check_kernel_signed(const char *matrix_path, const char *kernel_path, uint64_t prime, int right,
 			    int64_t *bad_row, int *bad_col);
+/* The same for a matrix with wide entries: read with blz_mm_load_wide, every entry a residue below prime < 2^62. */
+int blz_check_kernel_wide(const char *matrix_path, const char *kernel_path, uint64_t prime, int right,
+			  int64_t *bad_row, int *bad_col);
 
 /* Rank of a kernel block file (MatrixMarket "array integer general", column-major, as blz_save_block writes it) mod
  * prime: *rank = rank of its *cols columns, found by a row-by-row reduced echelon that stops once the rank equals the
@@ -261,6 +271,11 @@ int blz_check_solution_signed(const char *matrix_path, const char *rhs_path, con
 			      int64_t *bad_row);
 int blz_check_solution_block_signed(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime,
 				    int right, int *status, int64_t *bad_row);
+/* Both for a matrix with wide entries (blz_mm_load_wide): same arguments and returns. */
+int blz_check_solution_wide(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime, int right,
+			    int64_t *bad_row);
+int blz_check_solution_block_wide(const char *matrix_path, const char *rhs_path, const char *x_path, uint64_t prime,
+				  int right, int *status, int64_t *bad_row);
 
 /* TEST HOOKS, not part of the supported interface (they may change or go with the layout they describe; callers use
  * blz_set_rhs_ranks): two pieces of host arithmetic of the bordered solve on several ranks, visible so that tests can hold
@@ -315,6 +330,24 @@ int blz_values_signed(const blz_ctx *ctx);
  * instantiations of the SpMV kernels, 0 when it runs the unsigned ones -- any slab of an unsigned context, a slab without
  * negative entries, and every slab of 4-byte words (values canonicalised at upload) -- negative = BLZ_EINVAL. */
 int blz_slab_signed(const blz_ctx *ctx, int transpose, int piece);
+
+/* Wide value mode (opt-in, per matrix): any residue below p as a matrix entry.  x_hi[k] is the high limb of entry k of the
+ * triplets that the NEXT matrix-setting call (blz_set_matrix, blz_set_matrix_rhs, blz_set_matrix_rhs_block) is given: the
+ * entry is x[k] + 2^32 * x_hi[k], a canonical residue (BLZ_EINVAL from that call otherwise).  The pointer is borrowed until
+ * that call returns and is consumed by it.  Must be called before a matrix is set.  BLZ_EINVAL: an nnz that does not match
+ * (reported by the matrix-setting call), a resident matrix, a context in signed value mode, and a context with a
+ * communicator, a loopback group or BLZ_FORCE_COMM -- a wide matrix lives on one rank in one piece (so does nranks > 1 in
+ * the matrix-setting call).  While high limbs are pending, blz_set_matrix_prepared and the several-rank form of
+ * blz_set_matrix_rhs_ranks answer BLZ_EINVAL (they cannot carry them) and leave them pending.  A matrix-setting call that
+ * fails leaves the context out of the mode.  A high array of zeros is accepted: the matrix is then prepared exactly as an
+ * ordinary one.  x_hi = NULL clears the mode.  The SpMV of a slab with wide entries runs the plain form only
+ * (no staged and no panel form); blz_prepared_save refuses a prepared object that carries high limbs.  Checkpoints hold v
+ * and p, not the matrix: the mode is not recorded in them.  blz_values_wide: 0 / 1 = the mode of the context. */
+int blz_set_values_wide(blz_ctx *ctx, const uint32_t *x_hi, int64_t nnz);
+int blz_values_wide(const blz_ctx *ctx);
+/* 1 when that slab (arguments as blz_slab_plan) runs the wide instantiations of the SpMV kernels, 0 when it runs the
+ * unsigned ones -- a slab without an entry of 2^32 or more, and every slab of 4-byte words -- negative = BLZ_EINVAL. */
+int blz_slab_wide(const blz_ctx *ctx, int transpose, int piece);
 
 /* Upload M for the solve x*M=0 (right=0) or M*x=0 (right=1), as block_lanczos(M, n, transpose)
  * receives it (sequential/lanczos_modp.c:585).  Builds CSR(M) and CSR(M^T) on the host, keeps
@@ -461,7 +494,10 @@ int blz_init_v(blz_ctx *ctx);
 
 /* Copy a whole block (global rows x n, original row numbering) host->device / device->host.  With
  * nranks > 1 set_block fills the whole padded layout (so it doubles as an emulated all-gather); get_block
- * writes only the rows this rank owns and leaves the rest of `host` untouched. */
+ * writes only the rows this rank owns and leaves the rest of `host` untouched.
+ * The words given to set_block must be residues below p; they are not validated.  Every kernel writes canonical words,
+ * so the blocks of an iteration are.  The products of a slab with wide entries (blz_slab_wide) rely on it: their x' = 2^32 x
+ * mod p is a rotation of the 61-bit word at p = 2^61 - 1 and a Barrett reduction of 2^32 x < 2^94 otherwise. */
 int blz_set_block(blz_ctx *ctx, int block, const uint64_t *host);
 int blz_get_block(blz_ctx *ctx, int block, uint64_t *host);
 int blz_set_small(blz_ctx *ctx, int which, const uint64_t *host);
