@@ -11,6 +11,7 @@
  *   stream while piece k+1 is still in flight on the exchange stream.
  *   csr[0][k] / csr[1][k] = this rank's rows of M / M^T restricted to the columns of piece k.
  *   small  = [vtAv | vtAAv | winv | d | c | vtAvd], 6*n*n words;  ctl = DevCtl.
+ *   slab[4 + side] (one rank, allocated on first use): the scratch slabs blz_apply_device multiplies in, never a caller's block.
  */
 #include <dlfcn.h>
 #include <unistd.h>
@@ -29,6 +30,7 @@
 #include "blz_internal.h"
 #include "blz_kernels.h"
 #include "blz_border.h"
+#include "blz_devio.h"
 
 #define HIPCHK(expr)                                                                                     \
 	do {                                                                                             \
@@ -171,8 +173,9 @@ struct blz_ctx {
 	std::vector<int64_t> bounds[2];
 	std::vector<DevCsr> csr[2];			/* column pieces of this rank's rows of M / M^T */
 	int row_side[2] = { 0, 1 };			/* side of the rows of csr[t] */
-	void *slab[4] = { nullptr, nullptr, nullptr, nullptr };
-	size_t slab_bytes[4] = { 0, 0, 0, 0 };	/* several ranks: each block sized by its own side (V, AV, P: rows of v; TMP: the other side) */
+	/* slab[APPLY_SLAB + side] (hidden block numbers, never a caller's): the two scratch slabs of blz_apply_device */
+	void *slab[6] = { nullptr, nullptr, nullptr, nullptr, nullptr, nullptr };
+	size_t slab_bytes[6] = { 0, 0, 0, 0, 0, 0 };	/* several ranks: each block sized by its own side (V, AV, P: rows of v; TMP: the other side) */
 	void *gath[2] = { nullptr, nullptr };		/* gathered operands (nranks > 1) */
 	int gath_holds[2] = { -1, -1 };			/* which block each one currently holds */
 	int ag_chunks = 0;				/* pieces per all-gather: BLZ_AG_CHUNKS, 0 = choose from the slab size */
@@ -251,7 +254,16 @@ struct blz_ctx {
 	std::vector<int64_t> border_own;
 	long long *border_own_dev = nullptr;
 	u64 *border_send = nullptr, *border_recv = nullptr;	/* BLZ_MAX_RHS x cfg.n words each */
+	/* device blocks (blz_set_block_device, blz_get_block_device, blz_apply_device) */
+	int32_t *inv_dev[2] = { nullptr, nullptr };	/* inv[side] on the device: uploaded on first use, freed with the matrix */
+	bool inv_ready = false;
+	hipEvent_t ev_caller = nullptr, ev_ours = nullptr;	/* the caller's stream has reached the call / our work is enqueued */
+	unsigned long long *bad_dev = nullptr;		/* words not below p seen by a validating import */
+	DevCtl *apply_ctl = nullptr;			/* control words of blz_apply_device's products: the stop flag never up */
 };
+
+enum { APPLY_SLAB = 4 };
+static void devio_release_matrix(blz_ctx *c);
 
 /* HIP-event span around one enqueue on the context's stream (only while profiling is on). */
 struct Span {
@@ -483,6 +495,10 @@ extern "C" void blz_destroy(blz_ctx *c)
 	for (auto &A : c->csr_short)
 		free_csr(A);
 	if (c->part) hipFree(c->part);
+	devio_release_matrix(c);
+	if (c->ev_caller) hipEventDestroy(c->ev_caller);
+	if (c->ev_ours) hipEventDestroy(c->ev_ours);
+	if (c->bad_dev) hipFree(c->bad_dev);
 	for (void *&b : c->slab)
 		if (b) hipFree(b);
 	for (void *&b : c->gath)
@@ -838,6 +854,7 @@ static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool
 		hipGraphExecDestroy(c->iter_graph);
 		c->iter_graph = nullptr;
 	}
+	devio_release_matrix(c);	/* the scratch slabs and the device copy of the numbering belong to the matrix they were made for */
 	c->right = right;
 	c->rank = rank;
 	c->nranks = nranks;
@@ -3022,5 +3039,250 @@ extern "C" int blz_comm_init_loopback(blz_ctx *c, blz_loop_group *g, int rank)
 	c->rank = rank;
 	const char *f = getenv("BLZ_FORCE_COMM");
 	c->force_comm = f && f[0] == '1';
+	return BLZ_OK;
+}
+
+/* ---- device blocks: set, get and apply M on caller-owned device memory (kernels: blz_devio.hip) ---- */
+
+/* what belongs to the resident matrix: the scratch slabs of blz_apply_device, their control words, the numbering on the device */
+static void devio_release_matrix(blz_ctx *c)
+{
+	if (c->stream && (c->slab[APPLY_SLAB] || c->slab[APPLY_SLAB + 1] || c->apply_ctl || c->inv_ready))
+		hipStreamSynchronize(c->stream);	/* a product or a pass enqueued by the last call may still be running */
+	for (int sd = 0; sd < 2; sd++) {
+		if (c->slab[APPLY_SLAB + sd])
+			hipFree(c->slab[APPLY_SLAB + sd]);
+		c->slab[APPLY_SLAB + sd] = nullptr;
+		c->slab_bytes[APPLY_SLAB + sd] = 0;
+		if (c->inv_dev[sd])
+			hipFree(c->inv_dev[sd]);
+		c->inv_dev[sd] = nullptr;
+	}
+	c->inv_ready = false;
+	if (c->apply_ctl)
+		hipFree(c->apply_ctl);
+	c->apply_ctl = nullptr;
+}
+
+static int devio_refuse_ranks(const blz_ctx *c, const char *who)
+{
+	if (!c)
+		return blz_fail(BLZ_EINVAL, "%s: NULL context", who);
+	if (c->nranks > 1 || c->comm || c->loop || c->force_comm)
+		return blz_fail(BLZ_EINVAL, "%s: device blocks need a single rank without a communicator, a loopback group or "
+				"BLZ_FORCE_COMM (see DESIGN.md section 15)", who);
+	return BLZ_OK;
+}
+
+/* No kernel is launched on memory the library has not checked: the words [ptr, ptr + ((rows - 1) * ld + n) * 8) must lie
+ * inside ONE allocation of the context's device.  A host pointer, another device's memory, managed or pinned host memory,
+ * a range that runs past its allocation and ld < n are all BLZ_EINVAL, named by argument.  *bytes_out = the size checked. */
+static int devio_check_range(const blz_ctx *c, const char *who, const char *arg, const void *ptr, int64_t rows, int64_t ld,
+			     size_t *bytes_out)
+{
+	const int n = c->un;
+	if (!ptr)
+		return blz_fail(BLZ_EINVAL, "%s: %s is NULL", who, arg);
+	if (ld < n)
+		return blz_fail(BLZ_EINVAL, "%s: the row stride of %s is %lld words, less than n = %d", who, arg, (long long)ld, n);
+	if (((uintptr_t)ptr & 7) != 0)
+		return blz_fail(BLZ_EINVAL, "%s: %s is not aligned to 8 bytes", who, arg);
+	if (rows < 1 || ld > ((int64_t)1 << 40))
+		return blz_fail(BLZ_EINVAL, "%s: %s: %lld rows with a row stride of %lld words", who, arg, (long long)rows, (long long)ld);
+	const size_t bytes = ((size_t)(rows - 1) * (size_t)ld + (size_t)n) * 8;
+	hipPointerAttribute_t at;
+	memset(&at, 0, sizeof at);
+	if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
+		(void)hipGetLastError();	/* (a plain host pointer is an error of the query on some runtimes, an unregistered type on others) */
+		return blz_fail(BLZ_EINVAL, "%s: %s = %p is not device memory (a host pointer?)", who, arg, ptr);
+	}
+	if (at.type != hipMemoryTypeDevice)
+		return blz_fail(BLZ_EINVAL, "%s: %s = %p is not device memory (memory type %d; a host pointer?)", who, arg, ptr, (int)at.type);
+	if (at.device != c->device)
+		return blz_fail(BLZ_EINVAL, "%s: %s lives on device %d, the context on device %d", who, arg, at.device, c->device);
+	hipDeviceptr_t base = nullptr;
+	size_t size = 0;
+	if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) != hipSuccess || !base) {
+		(void)hipGetLastError();
+		return blz_fail(BLZ_EINVAL, "%s: the allocation of %s = %p cannot be found", who, arg, ptr);
+	}
+	const size_t off = (size_t)((const char *)ptr - (const char *)base);
+	if (off > size || bytes > size - off)
+		return blz_fail(BLZ_EINVAL, "%s: %s needs %zu bytes (%lld rows, row stride %lld, n = %d) but its allocation ends after %zu",
+				who, arg, bytes, (long long)rows, (long long)ld, n, off > size ? (size_t)0 : size - off);
+	if (bytes_out)
+		*bytes_out = bytes;
+	return BLZ_OK;
+}
+
+/* Ordering on the caller's stream, without the host: our stream waits for everything the caller has enqueued so far
+ * (devio_enter), the caller's stream for everything we enqueue (devio_leave).  A capturing stream is refused: the work
+ * runs on the context's own streams and cannot become part of the caller's graph. */
+static int devio_refuse_capture(const char *who, hipStream_t caller)
+{
+	hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+	HIPCHK(hipStreamIsCapturing(caller, &cap));
+	if (cap != hipStreamCaptureStatusNone)
+		return blz_fail(BLZ_EINVAL, "%s: the stream is capturing a graph", who);
+	return BLZ_OK;
+}
+
+static int devio_enter(blz_ctx *c, hipStream_t caller)
+{
+	if (!c->ev_caller) {
+		HIPCHK(hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming));
+		HIPCHK(hipEventCreateWithFlags(&c->ev_ours, hipEventDisableTiming));
+	}
+	if (!c->inv_ready) {	/* once per matrix */
+		for (int sd = 0; sd < 2; sd++) {
+			if (c->inv[sd].empty())
+				continue;
+			HIPCHK(hipMalloc((void **)&c->inv_dev[sd], c->inv[sd].size() * sizeof(int32_t)));
+			HIPCHK(hipMemcpy(c->inv_dev[sd], c->inv[sd].data(), c->inv[sd].size() * sizeof(int32_t), hipMemcpyHostToDevice));
+		}
+		c->inv_ready = true;
+	}
+	HIPCHK(hipEventRecord(c->ev_caller, caller));
+	HIPCHK(hipStreamWaitEvent(c->stream, c->ev_caller, 0));
+	return BLZ_OK;
+}
+
+static int devio_leave(blz_ctx *c, hipStream_t caller)
+{
+	HIPCHK(hipEventRecord(c->ev_ours, c->stream));
+	HIPCHK(hipStreamWaitEvent(caller, c->ev_ours, 0));
+	return BLZ_OK;
+}
+
+extern "C" int blz_set_block_device(blz_ctx *c, int block, const uint64_t *dev, int64_t ld, void *stream, int64_t *bad)
+{
+	int rc = devio_refuse_ranks(c, "blz_set_block_device");
+	if (rc != BLZ_OK)
+		return rc;
+	NEED_MATRIX(c);
+	if ((rc = devio_refuse_capture("blz_set_block_device", (hipStream_t)stream)) != BLZ_OK)
+		return rc;
+	if (block < 0 || block > 3)
+		return blz_fail(BLZ_EINVAL, "blz_set_block_device: block %d is not one of V, TMP, AV, P", block);
+	const int sd = side_of(block);
+	if ((rc = devio_check_range(c, "blz_set_block_device", "dev", dev, c->glob_rows[sd], ld, nullptr)) != BLZ_OK)
+		return rc;
+	if (bad && !c->bad_dev)
+		HIPCHK(hipMalloc((void **)&c->bad_dev, sizeof(unsigned long long)));
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_enter(c, caller)) != BLZ_OK)
+		return rc;
+	if (block == BLZ_P) {	/* p is what the caller says from here on (explicit_p_state, on the stream) */
+		HIPCHK(launch_identity_tail(c->small, c->cfg.n, c->stream));
+		c->p_implicit = false;
+	}
+	if (bad)
+		HIPCHK(hipMemsetAsync(c->bad_dev, 0, sizeof(unsigned long long), c->stream));
+	HIPCHK(launch_block_import(c->cfg, c->slab[block], dev, ld, c->inv_dev[sd], c->count[sd], c->un, bad ? c->bad_dev : nullptr,
+				   c->stream));
+	if ((rc = devio_leave(c, caller)) != BLZ_OK)
+		return rc;
+	if (bad) {
+		unsigned long long cnt = 0;
+		HIPCHK(hipStreamSynchronize(c->stream));
+		HIPCHK(hipMemcpy(&cnt, c->bad_dev, sizeof cnt, hipMemcpyDeviceToHost));
+		*bad = (int64_t)cnt;
+		if (cnt)
+			return blz_fail(BLZ_EINVAL, "blz_set_block_device: %llu words of the block are not residues below p", cnt);
+	}
+	return BLZ_OK;
+}
+
+extern "C" int blz_get_block_device(blz_ctx *c, int block, uint64_t *dev, int64_t ld, void *stream)
+{
+	int rc = devio_refuse_ranks(c, "blz_get_block_device");
+	if (rc != BLZ_OK)
+		return rc;
+	NEED_MATRIX(c);
+	if ((rc = devio_refuse_capture("blz_get_block_device", (hipStream_t)stream)) != BLZ_OK)
+		return rc;
+	if (block < 0 || block > 3)
+		return blz_fail(BLZ_EINVAL, "blz_get_block_device: block %d is not one of V, TMP, AV, P", block);
+	const int sd = side_of(block);
+	if ((rc = devio_check_range(c, "blz_get_block_device", "dev", dev, c->glob_rows[sd], ld, nullptr)) != BLZ_OK)
+		return rc;
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_enter(c, caller)) != BLZ_OK)
+		return rc;
+	if (block == BLZ_P && c->p_implicit) {	/* materialize_p, on the stream */
+		const int np = c->cfg.n;
+		HIPCHK(launch_block_mul(c->cfg, c->slab[BLZ_P], c->count[0], np, np, c->small + small_E(np), c->stream));
+		HIPCHK(launch_identity_tail(c->small, np, c->stream));
+		c->p_implicit = false;
+	}
+	HIPCHK(launch_block_export(c->cfg, dev, ld, c->slab[block], c->inv_dev[sd], c->count[sd], c->un, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_apply_rows(const blz_ctx *c, int transpose, int64_t *x_rows, int64_t *y_rows)
+{
+	if (!c || !c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "no matrix loaded (blz_set_matrix)");
+	const int ys = c->row_side[transpose ? 1 : 0];
+	if (x_rows)
+		*x_rows = c->glob_rows[1 - ys];
+	if (y_rows)
+		*y_rows = c->glob_rows[ys];
+	return BLZ_OK;
+}
+
+extern "C" int blz_apply_device(blz_ctx *c, int transpose, const uint64_t *x, int64_t ldx, uint64_t *y, int64_t ldy, void *stream)
+{
+	int rc = devio_refuse_ranks(c, "blz_apply_device");
+	if (rc != BLZ_OK)
+		return rc;
+	NEED_MATRIX(c);
+	if ((rc = devio_refuse_capture("blz_apply_device", (hipStream_t)stream)) != BLZ_OK)
+		return rc;
+	const int t = transpose ? 1 : 0, ys = c->row_side[t], xs = 1 - ys;
+	size_t xb = 0, yb = 0;
+	if ((rc = devio_check_range(c, "blz_apply_device", "x", x, c->glob_rows[xs], ldx, &xb)) != BLZ_OK ||
+	    (rc = devio_check_range(c, "blz_apply_device", "y", y, c->glob_rows[ys], ldy, &yb)) != BLZ_OK)
+		return rc;
+	if ((const char *)x < (const char *)y + yb && (const char *)y < (const char *)x + xb)
+		return blz_fail(BLZ_EINVAL, "blz_apply_device: x and y overlap");
+	/* two scratch slabs of the context's own, one per side, and control words whose stop flag is never up */
+	for (int sd = 0; sd < 2; sd++)
+		if (!c->slab[APPLY_SLAB + sd]) {
+			const size_t bytes = (size_t)std::max<int64_t>(c->stride[sd], 1) * c->cfg.n * c->cfg.word;
+			HIPCHK(hipMalloc(&c->slab[APPLY_SLAB + sd], bytes));
+			HIPCHK(hipMemset(c->slab[APPLY_SLAB + sd], 0, bytes));
+			c->slab_bytes[APPLY_SLAB + sd] = bytes;
+		}
+	if (!c->apply_ctl) {
+		HIPCHK(hipMalloc((void **)&c->apply_ctl, sizeof(DevCtl)));
+		HIPCHK(hipMemset(c->apply_ctl, 0, sizeof(DevCtl)));
+	}
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_enter(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_block_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, c->inv_dev[xs], c->count[xs], c->un, nullptr, c->stream));
+	if ((rc = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_block_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], c->inv_dev[ys], c->count[ys], c->un, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_apply_release(blz_ctx *c)
+{
+	if (!c)
+		return blz_fail(BLZ_EINVAL, "blz_apply_release: NULL context");
+	HIPCHK(hipSetDevice(c->device));
+	if (c->stream)
+		HIPCHK(hipStreamSynchronize(c->stream));
+	for (int sd = 0; sd < 2; sd++) {
+		if (c->slab[APPLY_SLAB + sd])
+			HIPCHK(hipFree(c->slab[APPLY_SLAB + sd]));
+		c->slab[APPLY_SLAB + sd] = nullptr;
+		c->slab_bytes[APPLY_SLAB + sd] = 0;
+	}
+	if (c->apply_ctl)
+		HIPCHK(hipFree(c->apply_ctl));
+	c->apply_ctl = nullptr;
 	return BLZ_OK;
 }

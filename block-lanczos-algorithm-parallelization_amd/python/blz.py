@@ -104,6 +104,43 @@ def device_count():
     return int(lib().blz_device_count())
 
 
+DEVICE_DTYPES = ("torch.uint64", "torch.int64")     # the same 64 bits either way: no conversion
+
+
+def device_block(t, n, rows=None, device=None):
+    """(pointer, rows, ld, device index) of a block held by a torch tensor -- or by any object with data_ptr(), shape,
+    stride(), dtype and device, which is all this looks at: torch is not imported here.  Two layouts: 2-D (rows, n) with
+    strides (ld, 1), ld >= n, or 1-D contiguous with rows * n elements.  rows / device, when given, are what the caller
+    expects (the block's row count, the context's device index).  Anything else is a ValueError that names the fault."""
+    if str(t.dtype) not in DEVICE_DTYPES:
+        raise ValueError(f"device block: dtype {t.dtype} is not one of {', '.join(DEVICE_DTYPES)}")
+    if getattr(t.device, "type", None) != "cuda":
+        raise ValueError(f"device block: the tensor lives on {t.device}, not on a GPU")
+    index = t.device.index if t.device.index is not None else 0
+    if device is not None and index != device:
+        raise ValueError(f"device block: the tensor lives on device {index}, the context on device {device}")
+    shape, stride = tuple(t.shape), tuple(t.stride())
+    if len(shape) == 2:
+        if shape[1] != n:
+            raise ValueError(f"device block: {shape[1]} columns, the block width is {n}")
+        if n > 1 and stride[1] != 1:
+            raise ValueError(f"device block: inner stride {stride[1]}, rows must be contiguous")
+        got, ld = shape[0], (stride[0] if shape[0] > 1 else max(stride[0], n))
+        if ld < n:
+            raise ValueError(f"device block: row stride ld = {ld} is less than n = {n}")
+    elif len(shape) == 1:
+        if stride[0] != 1 and shape[0] > 1:
+            raise ValueError(f"device block: a 1-D block must be contiguous (stride {stride[0]})")
+        if shape[0] % n:
+            raise ValueError(f"device block: {shape[0]} elements are not a whole number of rows of {n}")
+        got, ld = shape[0] // n, n
+    else:
+        raise ValueError(f"device block: {len(shape)} dimensions; a block is (rows, n) or flat")
+    if rows is not None and got != rows:
+        raise ValueError(f"device block: {got} rows, the block has {rows}")
+    return int(t.data_ptr()), int(got), int(ld), int(index)
+
+
 class Matrix:
     """struct sparsematrix_t of the reference (sequential/lanczos_modp.c:55-62) as numpy arrays."""
 
@@ -489,7 +526,7 @@ class Context:
 
     def __init__(self, prime, n, device=0):
         self.h = C.c_void_p()
-        self.prime, self.n = int(prime), int(n)
+        self.prime, self.n, self.device = int(prime), int(n), int(device)
         check(lib().blz_create(C.byref(self.h), C.c_int(device), C.c_uint64(prime), C.c_int(n)))
 
     def close(self):
@@ -715,6 +752,60 @@ class Context:
         out = np.zeros(self.rows(block) * self.n, dtype=np.uint64)
         check(lib().blz_get_block(self.h, C.c_int(block), ptr(out)))
         return out
+
+    # ---- device blocks: torch tensors (uint64 or int64) on the context's device; torch is imported here and only here
+
+    def _stream(self, stream):
+        if stream is None:
+            import torch
+            return int(torch.cuda.current_stream(self.device).cuda_stream)
+        return int(getattr(stream, "cuda_stream", stream))
+
+    def _new_block(self, rows):
+        import torch
+        return torch.empty((rows, self.n), dtype=torch.uint64, device=f"cuda:{self.device}")
+
+    def set_block_device(self, block, t, validate=False, stream=None):
+        """blz_set_block_device(): block <- the tensor t, (rows(block), n) with strides (ld, 1) or flat, ordered on `stream`
+        (default: torch's current stream) without a host synchronisation.  validate=True counts the words that are not
+        below p (synchronises) and returns the count, 0; a count that is not 0 raises BlzError(EINVAL) with it."""
+        rows = self.rows(block) if 0 <= block <= 3 else None
+        p, _, ld, _ = device_block(t, self.n, rows, self.device)
+        bad = C.c_int64(-1)
+        check(lib().blz_set_block_device(self.h, C.c_int(block), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream)),
+                                         C.byref(bad) if validate else None))
+        return int(bad.value) if validate else None
+
+    def get_block_device(self, block, out=None, stream=None):
+        """blz_get_block_device(): the block as a tensor on the device (out, or a new (rows, n) torch.uint64 one)."""
+        rows = self.rows(block) if 0 <= block <= 3 else None
+        if out is None:
+            out = self._new_block(rows if rows is not None else 1)
+        p, _, ld, _ = device_block(out, self.n, rows, self.device)
+        check(lib().blz_get_block_device(self.h, C.c_int(block), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream))))
+        return out
+
+    def apply_rows(self, transpose):
+        """blz_apply_rows(): (rows of x, rows of y) of y = M x (transpose False) / M^T x."""
+        xr, yr = C.c_int64(0), C.c_int64(0)
+        check(lib().blz_apply_rows(self.h, C.c_int(int(bool(transpose))), C.byref(xr), C.byref(yr)))
+        return int(xr.value), int(yr.value)
+
+    def apply(self, transpose, x, out=None, stream=None):
+        """blz_apply_device(): out = M x (transpose False) / M^T x on tensors of the context's device, ordered on `stream`;
+        the blocks and the state of a solve are left alone.  Returns out (a new torch.uint64 tensor when not given)."""
+        xr, yr = self.apply_rows(transpose)
+        px, _, ldx, _ = device_block(x, self.n, xr, self.device)
+        if out is None:
+            out = self._new_block(yr)
+        py, _, ldy, _ = device_block(out, self.n, yr, self.device)
+        check(lib().blz_apply_device(self.h, C.c_int(int(bool(transpose))), C.c_void_p(px), C.c_int64(ldx), C.c_void_p(py),
+                                     C.c_int64(ldy), C.c_void_p(self._stream(stream))))
+        return out
+
+    def apply_release(self):
+        """blz_apply_release(): free the two scratch slabs apply() works in (they come back on the next call)."""
+        check(lib().blz_apply_release(self.h))
 
     def set_small(self, which, host):
         check(lib().blz_set_small(self.h, C.c_int(which), ptr(u64(host))))

@@ -503,6 +503,41 @@ int blz_get_block(blz_ctx *ctx, int block, uint64_t *host);
 int blz_set_small(blz_ctx *ctx, int which, const uint64_t *host);
 int blz_get_small(blz_ctx *ctx, int which, uint64_t *host);
 
+/* Device blocks: the same blocks handed over and taken back as DEVICE pointers -- a torch tensor, the output of the caller's
+ * own kernel, the next vector of a Krylov method built on the operator -- without a trip through the host.  `dev` is
+ * blz_rows(ctx, block) x n words of uint64_t in the ORIGINAL row numbering (border rows count on a bordered context), row-major
+ * with a row stride of ld >= n words; words n .. ld-1 of a row are never read and never written.  The renumbering, the padded
+ * width and the word width in HBM stay hidden, as for host blocks: one kernel gathers / scatters whole rows (DESIGN.md
+ * section 15).  blz_set_block_device and blz_get_block_device mean what blz_set_block / blz_get_block mean (P explicit after
+ * a set, materialised before a get); a blz_get_block after a device set, and a device get after blz_set_block, return the
+ * same words.
+ *   stream  the caller's hipStream_t (NULL = the null stream).  The call is ordered on it without synchronising the host: the
+ *           library's stream waits for what the caller has enqueued so far, and the caller's stream waits for what the call
+ *           enqueues.  A stream that is capturing a graph is BLZ_EINVAL.  (The first call after a matrix is set uploads the
+ *           numbering once, synchronously.)
+ *   bad     NULL: the words are not validated; the contract is blz_set_block's, residues below p.  Not NULL: the import counts
+ *           the words >= p, the call synchronises, stores the count in *bad and, when it is not 0, returns BLZ_EINVAL with the
+ *           count in the message -- the block then holds the words as given (truncated to 32 bits where p < 2^32).  The
+ *           products of a slab with wide entries (blz_slab_wide) rely on canonical words: validate what is not known to be.
+ * Every device pointer is checked on the host before anything is enqueued: the whole range ((rows - 1) * ld + n) * 8 bytes
+ * must lie inside one allocation of the context's device.  A host pointer, memory of another device, a range that runs past
+ * its allocation and ld < n are BLZ_EINVAL, and the message names the argument.
+ * One rank only: a context with nranks > 1, a communicator, a loopback group or BLZ_FORCE_COMM answers BLZ_EINVAL. */
+int blz_set_block_device(blz_ctx *ctx, int block, const uint64_t *dev, int64_t ld, void *stream, int64_t *bad);
+int blz_get_block_device(blz_ctx *ctx, int block, uint64_t *dev, int64_t ld, void *stream);
+
+/* y = M * x (transpose = 0) or M^T * x on caller-owned device blocks, bit-identical to blz_set_block(src, x);
+ * blz_spmv(transpose, src, dst); blz_get_block(dst) on every kind of context -- plain, signed, wide, and bordered (then the
+ * bordered operator, as blz_spmv) -- but without touching the state of a solve: V, TMP, AV, P, the small operands, the
+ * iteration count and the implicit-p state stay exactly as they were, and a context whose solve has stopped still applies.
+ * blz_apply_rows gives the row counts of x and y (either pointer may be NULL).  x and y (pointers, strides, stream: as above)
+ * must not overlap.  The product runs in two scratch slabs of the context's own, one per side, allocated on first use:
+ * (rows of V + rows of TMP) x the width in HBM x blz_word_bytes bytes.  blz_apply_release frees them (after waiting for
+ * the context's stream); so do the next matrix-setting call and blz_destroy.  One rank only, as above. */
+int blz_apply_rows(const blz_ctx *ctx, int transpose, int64_t *x_rows, int64_t *y_rows);
+int blz_apply_device(blz_ctx *ctx, int transpose, const uint64_t *x, int64_t ldx, uint64_t *y, int64_t ldy, void *stream);
+int blz_apply_release(blz_ctx *ctx);
+
 /* sparse_matrix_vector_product(y, M, x, transpose), sequential/lanczos_modp.c:266-287:
  * dst = M*src (transpose=0) or M^T*src (transpose=1), all n columns, canonical residues. */
 int blz_spmv(blz_ctx *ctx, int transpose, int src_block, int dst_block);
