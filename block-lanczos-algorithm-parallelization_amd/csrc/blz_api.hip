@@ -12,6 +12,7 @@
  *   csr[0][k] / csr[1][k] = this rank's rows of M / M^T restricted to the columns of piece k.
  *   small  = [vtAv | vtAAv | winv | d | c | vtAvd], 6*n*n words;  ctl = DevCtl.
  *   slab[4 + side] (one rank, allocated on first use): the scratch slabs blz_apply_device multiplies in, never a caller's block.
+ *   devalg_partial (allocated on first use): the partial rows of blz_dot_device, never the `partial` of an iteration in flight.
  */
 #include <dlfcn.h>
 #include <unistd.h>
@@ -31,6 +32,7 @@
 #include "blz_kernels.h"
 #include "blz_border.h"
 #include "blz_devio.h"
+#include "blz_devalg.h"
 
 #define HIPCHK(expr)                                                                                     \
 	do {                                                                                             \
@@ -260,6 +262,8 @@ struct blz_ctx {
 	hipEvent_t ev_caller = nullptr, ev_ours = nullptr;	/* the caller's stream has reached the call / our work is enqueued */
 	unsigned long long *bad_dev = nullptr;		/* words not below p seen by a validating import */
 	DevCtl *apply_ctl = nullptr;			/* control words of blz_apply_device's products: the stop flag never up */
+	/* device block algebra (blz_dot_device): dev_dot_max_blocks() partial rows of un * un words, allocated on first use */
+	u64 *devalg_partial = nullptr;
 };
 
 enum { APPLY_SLAB = 4 };
@@ -499,6 +503,7 @@ extern "C" void blz_destroy(blz_ctx *c)
 	if (c->ev_caller) hipEventDestroy(c->ev_caller);
 	if (c->ev_ours) hipEventDestroy(c->ev_ours);
 	if (c->bad_dev) hipFree(c->bad_dev);
+	if (c->devalg_partial) hipFree(c->devalg_partial);
 	for (void *&b : c->slab)
 		if (b) hipFree(b);
 	for (void *&b : c->gath)
@@ -3076,19 +3081,26 @@ static int devio_refuse_ranks(const blz_ctx *c, const char *who)
 
 /* No kernel is launched on memory the library has not checked: the words [ptr, ptr + ((rows - 1) * ld + n) * 8) must lie
  * inside ONE allocation of the context's device.  A host pointer, another device's memory, managed or pinned host memory,
- * a range that runs past its allocation and ld < n are all BLZ_EINVAL, named by argument.  *bytes_out = the size checked. */
+ * a range that runs past its allocation and ld < n are all BLZ_EINVAL, named by argument.  *bytes_out = the size checked.
+ * `rows` is the block's own: a side of the matrix for set / get / apply, the caller's for the block algebra (an n x n operand
+ * is n rows of stride n).  A block of no rows has no words: any pointer will do, nothing is looked up and *bytes_out = 0. */
 static int devio_check_range(const blz_ctx *c, const char *who, const char *arg, const void *ptr, int64_t rows, int64_t ld,
 			     size_t *bytes_out)
 {
 	const int n = c->un;
-	if (!ptr)
+	if (!ptr && rows != 0)
 		return blz_fail(BLZ_EINVAL, "%s: %s is NULL", who, arg);
 	if (ld < n)
 		return blz_fail(BLZ_EINVAL, "%s: the row stride of %s is %lld words, less than n = %d", who, arg, (long long)ld, n);
 	if (((uintptr_t)ptr & 7) != 0)
 		return blz_fail(BLZ_EINVAL, "%s: %s is not aligned to 8 bytes", who, arg);
-	if (rows < 1 || ld > ((int64_t)1 << 40))
+	if (rows < 0 || rows > ((int64_t)1 << 40) || ld > ((int64_t)1 << 40))
 		return blz_fail(BLZ_EINVAL, "%s: %s: %lld rows with a row stride of %lld words", who, arg, (long long)rows, (long long)ld);
+	if (rows == 0) {
+		if (bytes_out)
+			*bytes_out = 0;
+		return BLZ_OK;
+	}
 	const size_t bytes = ((size_t)(rows - 1) * (size_t)ld + (size_t)n) * 8;
 	hipPointerAttribute_t at;
 	memset(&at, 0, sizeof at);
@@ -3127,12 +3139,20 @@ static int devio_refuse_capture(const char *who, hipStream_t caller)
 	return BLZ_OK;
 }
 
-static int devio_enter(blz_ctx *c, hipStream_t caller)
+/* the first of the two events: our stream waits for the caller's (no matrix is needed for this much) */
+static int devio_wait_caller(blz_ctx *c, hipStream_t caller)
 {
 	if (!c->ev_caller) {
 		HIPCHK(hipEventCreateWithFlags(&c->ev_caller, hipEventDisableTiming));
 		HIPCHK(hipEventCreateWithFlags(&c->ev_ours, hipEventDisableTiming));
 	}
+	HIPCHK(hipEventRecord(c->ev_caller, caller));
+	HIPCHK(hipStreamWaitEvent(c->stream, c->ev_caller, 0));
+	return BLZ_OK;
+}
+
+static int devio_enter(blz_ctx *c, hipStream_t caller)
+{
 	if (!c->inv_ready) {	/* once per matrix */
 		for (int sd = 0; sd < 2; sd++) {
 			if (c->inv[sd].empty())
@@ -3142,9 +3162,7 @@ static int devio_enter(blz_ctx *c, hipStream_t caller)
 		}
 		c->inv_ready = true;
 	}
-	HIPCHK(hipEventRecord(c->ev_caller, caller));
-	HIPCHK(hipStreamWaitEvent(c->stream, c->ev_caller, 0));
-	return BLZ_OK;
+	return devio_wait_caller(c, caller);
 }
 
 static int devio_leave(blz_ctx *c, hipStream_t caller)
@@ -3285,4 +3303,90 @@ extern "C" int blz_apply_release(blz_ctx *c)
 		HIPCHK(hipFree(c->apply_ctl));
 	c->apply_ctl = nullptr;
 	return BLZ_OK;
+}
+
+/* ---- device block algebra: X^T * Y and sum_t X_t * A_t on caller-owned device memory (kernels: blz_devalg.hip; DESIGN.md
+ * section 16).  No matrix is needed and nothing of a solve is read or written: the only state is the scratch of the dot. ---- */
+
+static bool devalg_overlap(const void *a, size_t ab, const void *b, size_t bb)
+{
+	return (const char *)a < (const char *)b + bb && (const char *)b < (const char *)a + ab;
+}
+
+extern "C" int blz_dot_device(blz_ctx *c, int64_t rows, const uint64_t *x, int64_t ldx, const uint64_t *y, int64_t ldy,
+			      uint64_t *out, void *stream)
+{
+	static const char who[] = "blz_dot_device";
+	int rc = devio_refuse_ranks(c, who);
+	if (rc != BLZ_OK)
+		return rc;
+	HIPCHK(hipSetDevice(c->device));
+	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
+		return rc;
+	if (rows < 0)
+		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
+	const int n = c->un;
+	size_t xb = 0, yb = 0, cb = 0;
+	if ((rc = devio_check_range(c, who, "x", x, rows, ldx, &xb)) != BLZ_OK ||
+	    (rc = devio_check_range(c, who, "y", y, rows, ldy, &yb)) != BLZ_OK ||
+	    (rc = devio_check_range(c, who, "c", out, n, n, &cb)) != BLZ_OK)
+		return rc;
+	if (devalg_overlap(out, cb, x, xb))
+		return blz_fail(BLZ_EINVAL, "%s: c overlaps x", who);
+	if (devalg_overlap(out, cb, y, yb))
+		return blz_fail(BLZ_EINVAL, "%s: c overlaps y", who);
+	if (!c->devalg_partial)
+		HIPCHK(hipMalloc((void **)&c->devalg_partial, (size_t)dev_dot_max_blocks(c->cfg, n) * n * n * sizeof(u64)));
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_dev_dot(c->cfg, n, rows, x, ldx, y, ldy, c->devalg_partial, out, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_combine_device(blz_ctx *c, int64_t rows, int nterms, const uint64_t *const *x, const int64_t *ldx,
+				  const uint64_t *const *a, uint64_t *z, int64_t ldz, void *stream)
+{
+	static const char who[] = "blz_combine_device";
+	int rc = devio_refuse_ranks(c, who);
+	if (rc != BLZ_OK)
+		return rc;
+	HIPCHK(hipSetDevice(c->device));
+	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
+		return rc;
+	if (nterms < 1 || nterms > BLZ_MAX_TERMS)
+		return blz_fail(BLZ_EINVAL, "%s: nterms = %d is outside 1..%d", who, nterms, BLZ_MAX_TERMS);
+	if (rows < 0)
+		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
+	if (!x || !ldx || !a)
+		return blz_fail(BLZ_EINVAL, "%s: the array of %s is NULL", who, !x ? "x" : !ldx ? "ldx" : "a");
+	const int n = c->un;
+	size_t xb[BLZ_MAX_TERMS] = { 0 }, ab[BLZ_MAX_TERMS] = { 0 }, zb = 0;
+	long long ldl[BLZ_MAX_TERMS] = { 0 };
+	char xn[8], an[8];
+	for (int t = 0; t < nterms; t++) {
+		snprintf(xn, sizeof xn, "x[%d]", t);
+		snprintf(an, sizeof an, "a[%d]", t);
+		if ((rc = devio_check_range(c, who, xn, x[t], rows, ldx[t], &xb[t])) != BLZ_OK ||
+		    (rc = devio_check_range(c, who, an, a[t], n, n, &ab[t])) != BLZ_OK)
+			return rc;
+		ldl[t] = ldx[t];
+	}
+	if ((rc = devio_check_range(c, who, "z", z, rows, ldz, &zb)) != BLZ_OK)
+		return rc;
+	for (int t = 0; t < nterms; t++) {
+		const bool in_place = x[t] == z && ldx[t] == ldz;
+		if (!in_place && devalg_overlap(z, zb, x[t], xb[t]))
+			return blz_fail(BLZ_EINVAL, "%s: z overlaps x[%d] without being it (the in-place form is the same pointer and "
+					"the same stride)", who, t);
+		if (devalg_overlap(z, zb, a[t], ab[t]))
+			return blz_fail(BLZ_EINVAL, "%s: z overlaps a[%d]", who, t);
+	}
+	if (rows == 0)
+		return BLZ_OK;	/* z has no words */
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_dev_combine(c->cfg, n, rows, nterms, x, ldl, a, z, ldz, c->stream));
+	return devio_leave(c, caller);
 }

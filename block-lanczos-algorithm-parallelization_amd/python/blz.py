@@ -123,7 +123,7 @@ def device_block(t, n, rows=None, device=None):
     if len(shape) == 2:
         if shape[1] != n:
             raise ValueError(f"device block: {shape[1]} columns, the block width is {n}")
-        if n > 1 and stride[1] != 1:
+        if n > 1 and stride[1] != 1 and shape[0] > 0:   # (a block of no rows has no words: torch may say any stride)
             raise ValueError(f"device block: inner stride {stride[1]}, rows must be contiguous")
         got, ld = shape[0], (stride[0] if shape[0] > 1 else max(stride[0], n))
         if ld < n:
@@ -139,6 +139,47 @@ def device_block(t, n, rows=None, device=None):
     if rows is not None and got != rows:
         raise ValueError(f"device block: {got} rows, the block has {rows}")
     return int(t.data_ptr()), int(got), int(ld), int(index)
+
+
+MAX_TERMS = 4       # BLZ_MAX_TERMS of include/blz.h
+
+
+def device_square(t, n, device=None):
+    """pointer of an n x n operand of the block algebra (a coefficient matrix, the result of dot) held by a tensor -- or by
+    anything with data_ptr(), shape, stride(), dtype and device: (n, n), contiguous, uint64 or int64, on the context's device.
+    Anything else is a ValueError that names the fault.  torch is not imported here."""
+    if str(t.dtype) not in DEVICE_DTYPES:
+        raise ValueError(f"n x n operand: dtype {t.dtype} is not one of {', '.join(DEVICE_DTYPES)}")
+    if getattr(t.device, "type", None) != "cuda":
+        raise ValueError(f"n x n operand: the tensor lives on {t.device}, not on a GPU")
+    index = t.device.index if t.device.index is not None else 0
+    if device is not None and index != device:
+        raise ValueError(f"n x n operand: the tensor lives on device {index}, the context on device {device}")
+    shape, stride = tuple(t.shape), tuple(t.stride())
+    if shape != (n, n):
+        raise ValueError(f"n x n operand: shape {shape}, not ({n}, {n})")
+    if n > 1 and stride != (n, 1):
+        raise ValueError(f"n x n operand: strides {stride}, the operand must be contiguous")
+    return int(t.data_ptr())
+
+
+def device_terms(terms, n, device=None):
+    """(rows, [(pointer of X, ld of X, pointer of A), ...]) of the 1..MAX_TERMS pairs (X, A) of Context.combine: every X goes
+    through device_block, every A through device_square; the rows are the first block's and all blocks must agree."""
+    terms = list(terms)
+    if not 1 <= len(terms) <= MAX_TERMS:
+        raise ValueError(f"combine: {len(terms)} terms, not 1..{MAX_TERMS}")
+    rows, out = None, []
+    for k, pair in enumerate(terms):
+        if len(pair) != 2:
+            raise ValueError(f"combine: term {k} is not a pair (X, A)")
+        try:
+            px, rows, ldx, _ = device_block(pair[0], n, rows, device)
+            pa = device_square(pair[1], n, device)
+        except ValueError as e:
+            raise ValueError(f"combine: term {k}: {e}") from None
+        out.append((px, ldx, pa))
+    return rows, out
 
 
 class Matrix:
@@ -806,6 +847,55 @@ class Context:
     def apply_release(self):
         """blz_apply_release(): free the two scratch slabs apply() works in (they come back on the next call)."""
         check(lib().blz_apply_release(self.h))
+
+    # ---- device block algebra: X^T Y and sum X_t A_t on tensors of the context's device; no matrix needed, no solve touched
+
+    def _coefficient(self, a, stream):
+        """an n x n coefficient as a tensor on the device: a tensor is taken as it is (device_square judges it), a numpy array
+        or a nested list of residues is moved there on `stream`"""
+        import torch
+        if isinstance(a, torch.Tensor):
+            return a
+        host = np.ascontiguousarray(np.array(a, dtype=np.uint64))
+        if host.size != self.n * self.n:
+            raise ValueError(f"n x n operand: {host.size} words, not {self.n} x {self.n}")
+        s = stream if isinstance(stream, torch.cuda.Stream) else \
+            torch.cuda.ExternalStream(self._stream(stream), device=f"cuda:{self.device}")
+        with torch.cuda.stream(s):
+            return torch.from_numpy(host.reshape(self.n, self.n).view(np.int64)).to(f"cuda:{self.device}")
+
+    def dot(self, x, y, out=None, stream=None):
+        """blz_dot_device(): out = x^T y mod p, an (n, n) torch.uint64 tensor on the device (out, or a new one); x and y are
+        blocks of the same number of rows (any, 0 included), `x is y` gives the Gram matrix.  Ordered on `stream`."""
+        px, rows, ldx, _ = device_block(x, self.n, None, self.device)
+        py, _, ldy, _ = device_block(y, self.n, rows, self.device)
+        if out is None:
+            import torch
+            out = torch.empty((self.n, self.n), dtype=torch.uint64, device=f"cuda:{self.device}")
+        pc = device_square(out, self.n, self.device)
+        check(lib().blz_dot_device(self.h, C.c_int64(rows), C.c_void_p(px), C.c_int64(ldx), C.c_void_p(py), C.c_int64(ldy),
+                                   C.c_void_p(pc), C.c_void_p(self._stream(stream))))
+        return out
+
+    def combine(self, terms, out=None, stream=None):
+        """blz_combine_device(): out = sum of X @ A mod p over the 1..4 pairs (X, A) of `terms`, row by row.  X: blocks of the
+        same number of rows; A: (n, n) tensors on the device, or numpy arrays / nested lists of residues, which are moved
+        there on `stream`.  out: a new (rows, n) torch.uint64 tensor, the caller's, or one of the X (the in-place form)."""
+        terms = list(terms)
+        if not 1 <= len(terms) <= MAX_TERMS:
+            raise ValueError(f"combine: {len(terms)} terms, not 1..{MAX_TERMS}")
+        terms = [(pair[0], self._coefficient(pair[1], stream)) for pair in terms]
+        rows, args = device_terms(terms, self.n, self.device)
+        if out is None:
+            out = self._new_block(rows)
+        pz, _, ldz, _ = device_block(out, self.n, rows, self.device)
+        k = len(args)
+        xs = (C.c_void_p * k)(*[a[0] for a in args])
+        lds = (C.c_int64 * k)(*[a[1] for a in args])
+        cs = (C.c_void_p * k)(*[a[2] for a in args])
+        check(lib().blz_combine_device(self.h, C.c_int64(rows), C.c_int(k), xs, lds, cs, C.c_void_p(pz), C.c_int64(ldz),
+                                       C.c_void_p(self._stream(stream))))
+        return out
 
     def set_small(self, which, host):
         check(lib().blz_set_small(self.h, C.c_int(which), ptr(u64(host))))

@@ -538,6 +538,39 @@ int blz_apply_rows(const blz_ctx *ctx, int transpose, int64_t *x_rows, int64_t *
 int blz_apply_device(blz_ctx *ctx, int transpose, const uint64_t *x, int64_t ldx, uint64_t *y, int64_t ldy, void *stream);
 int blz_apply_release(blz_ctx *ctx);
 
+/* Device block algebra: the other two parts of a Krylov step -- an n x n block inner product and a row-local recombination --
+ * on caller-owned device blocks, exact mod p (64 x 64 -> 128-bit products, which no torch dtype does).  n and p are the
+ * context's; `rows` is the CALLER's, any rows >= 0, not tied to a matrix: both calls work on a context with no matrix set and
+ * on one whose solve is running or has stopped, and touch nothing of a solve (V, TMP, AV, P, the small operands, the control
+ * words, the iteration count, the implicit-p state and the scratch slabs of blz_apply_device stay as they are).  Both
+ * operations are invariant under a permutation of the rows, so they run on the caller's rows, in the caller's numbering, at
+ * the caller's stride: no import, no export, no scratch slab.
+ *   blocks        rows x n words of uint64_t, row stride ld >= n words whatever blz_word_bytes is; words n .. ld-1 of a row
+ *                 are never read and never written.
+ *   c, a[t]       n x n words of uint64_t, row-major, contiguous, in device memory.  Results land in device memory: nothing is
+ *                 copied to the host and the host does not synchronise.
+ *   every word read (blocks and coefficients) is a residue below p -- blz_set_block's contract, NOT validated; every word
+ *   written is the canonical residue of the exact integer sum.
+ *   stream        as for blz_set_block_device: the two-event ordering on the context's stream; a capturing stream is BLZ_EINVAL.
+ * Checked on the host before the first enqueue, BLZ_EINVAL with a message that names the argument: rows < 0, nterms outside
+ * 1..BLZ_MAX_TERMS, ld < n, a NULL entry, a host pointer, a block, c or a[t] that does not lie inside one allocation of the
+ * context's device, and the overlaps below.  One rank only, as the other device-block calls.
+ *
+ * blz_dot_device      C = X^T * Y mod p:  c[i*n + j] = sum_r x[r*ldx + i] * y[r*ldy + j],  0 <= i, j < n.  dot(v, Av) is the
+ *                     reference's vtAv.  x == y is allowed (a Gram matrix); c must overlap neither.  rows == 0: c = 0.  The
+ *                     partial sums go through a scratch buffer of the context's own (at most 8 MB, allocated on first use,
+ *                     freed by blz_destroy), not the one of an iteration in flight.
+ * blz_combine_device  Z = sum_{t < nterms} X_t * A_t mod p, row by row:
+ *                     z[r*ldz + j] = sum_t sum_i x[t][r*ldx[t] + i] * a[t][i*n + j].  z may BE one or more of the x[t] -- the
+ *                     same pointer and the same stride: the in-place form, exact; otherwise z must overlap no x[t].  z must
+ *                     overlap no a[t].  rows == 0: z is not touched.
+ * Limits: one rank; vector-ALU kernels only (no matrix-core form at p = 2^61 - 1 yet); residues are not validated. */
+#define BLZ_MAX_TERMS 4
+int blz_dot_device(blz_ctx *ctx, int64_t rows, const uint64_t *x, int64_t ldx, const uint64_t *y, int64_t ldy, uint64_t *c,
+		   void *stream);
+int blz_combine_device(blz_ctx *ctx, int64_t rows, int nterms, const uint64_t *const *x, const int64_t *ldx,
+		       const uint64_t *const *a, uint64_t *z, int64_t ldz, void *stream);
+
 /* sparse_matrix_vector_product(y, M, x, transpose), sequential/lanczos_modp.c:266-287:
  * dst = M*src (transpose=0) or M^T*src (transpose=1), all n columns, canonical residues. */
 int blz_spmv(blz_ctx *ctx, int transpose, int src_block, int dst_block);
