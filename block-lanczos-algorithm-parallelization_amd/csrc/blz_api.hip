@@ -13,6 +13,8 @@
  *   small  = [vtAv | vtAAv | winv | d | c | vtAvd], 6*n*n words;  ctl = DevCtl.
  *   slab[4 + side] (one rank, allocated on first use): the scratch slabs blz_apply_device multiplies in, never a caller's block.
  *   devalg_partial (allocated on first use): the partial rows of blz_dot_device, never the `partial` of an iteration in flight.
+ *   devsmall_stack / devsmall_ctl (allocated on first use): the partial echelons and control words of blz_rref_device, never
+ *   the rref_* buffers of blz_block_rref / blz_kernel_basis.
  */
 #include <dlfcn.h>
 #include <unistd.h>
@@ -33,6 +35,7 @@
 #include "blz_border.h"
 #include "blz_devio.h"
 #include "blz_devalg.h"
+#include "blz_devsmall.h"
 
 #define HIPCHK(expr)                                                                                     \
 	do {                                                                                             \
@@ -264,6 +267,10 @@ struct blz_ctx {
 	DevCtl *apply_ctl = nullptr;			/* control words of blz_apply_device's products: the stop flag never up */
 	/* device block algebra (blz_dot_device): dev_dot_max_blocks() partial rows of un * un words, allocated on first use */
 	u64 *devalg_partial = nullptr;
+	/* device small algebra (blz_rref_device): dev_rref_stack_rows() partial echelon rows of un words and [rank-n flag, rows
+	 * stacked], allocated on first use */
+	u64 *devsmall_stack = nullptr;
+	int *devsmall_ctl = nullptr;
 };
 
 enum { APPLY_SLAB = 4 };
@@ -504,6 +511,8 @@ extern "C" void blz_destroy(blz_ctx *c)
 	if (c->ev_ours) hipEventDestroy(c->ev_ours);
 	if (c->bad_dev) hipFree(c->bad_dev);
 	if (c->devalg_partial) hipFree(c->devalg_partial);
+	if (c->devsmall_stack) hipFree(c->devsmall_stack);
+	if (c->devsmall_ctl) hipFree(c->devsmall_ctl);
 	for (void *&b : c->slab)
 		if (b) hipFree(b);
 	for (void *&b : c->gath)
@@ -3079,6 +3088,33 @@ static int devio_refuse_ranks(const blz_ctx *c, const char *who)
 	return BLZ_OK;
 }
 
+/* the look-up the two checks below share: `bytes` from ptr on lie inside ONE allocation of the context's device */
+static int devio_check_alloc(const blz_ctx *c, const char *who, const char *arg, const void *ptr, size_t bytes, int64_t rows,
+			     int64_t ld)
+{
+	hipPointerAttribute_t at;
+	memset(&at, 0, sizeof at);
+	if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
+		(void)hipGetLastError();	/* (a plain host pointer is an error of the query on some runtimes, an unregistered type on others) */
+		return blz_fail(BLZ_EINVAL, "%s: %s = %p is not device memory (a host pointer?)", who, arg, ptr);
+	}
+	if (at.type != hipMemoryTypeDevice)
+		return blz_fail(BLZ_EINVAL, "%s: %s = %p is not device memory (memory type %d; a host pointer?)", who, arg, ptr, (int)at.type);
+	if (at.device != c->device)
+		return blz_fail(BLZ_EINVAL, "%s: %s lives on device %d, the context on device %d", who, arg, at.device, c->device);
+	hipDeviceptr_t base = nullptr;
+	size_t size = 0;
+	if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) != hipSuccess || !base) {
+		(void)hipGetLastError();
+		return blz_fail(BLZ_EINVAL, "%s: the allocation of %s = %p cannot be found", who, arg, ptr);
+	}
+	const size_t off = (size_t)((const char *)ptr - (const char *)base);
+	if (off > size || bytes > size - off)
+		return blz_fail(BLZ_EINVAL, "%s: %s needs %zu bytes (%lld rows, row stride %lld, n = %d) but its allocation ends after %zu",
+				who, arg, bytes, (long long)rows, (long long)ld, c->un, off > size ? (size_t)0 : size - off);
+	return BLZ_OK;
+}
+
 /* No kernel is launched on memory the library has not checked: the words [ptr, ptr + ((rows - 1) * ld + n) * 8) must lie
  * inside ONE allocation of the context's device.  A host pointer, another device's memory, managed or pinned host memory,
  * a range that runs past its allocation and ld < n are all BLZ_EINVAL, named by argument.  *bytes_out = the size checked.
@@ -3102,28 +3138,26 @@ static int devio_check_range(const blz_ctx *c, const char *who, const char *arg,
 		return BLZ_OK;
 	}
 	const size_t bytes = ((size_t)(rows - 1) * (size_t)ld + (size_t)n) * 8;
-	hipPointerAttribute_t at;
-	memset(&at, 0, sizeof at);
-	if (hipPointerGetAttributes(&at, ptr) != hipSuccess) {
-		(void)hipGetLastError();	/* (a plain host pointer is an error of the query on some runtimes, an unregistered type on others) */
-		return blz_fail(BLZ_EINVAL, "%s: %s = %p is not device memory (a host pointer?)", who, arg, ptr);
-	}
-	if (at.type != hipMemoryTypeDevice)
-		return blz_fail(BLZ_EINVAL, "%s: %s = %p is not device memory (memory type %d; a host pointer?)", who, arg, ptr, (int)at.type);
-	if (at.device != c->device)
-		return blz_fail(BLZ_EINVAL, "%s: %s lives on device %d, the context on device %d", who, arg, at.device, c->device);
-	hipDeviceptr_t base = nullptr;
-	size_t size = 0;
-	if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)ptr) != hipSuccess || !base) {
-		(void)hipGetLastError();
-		return blz_fail(BLZ_EINVAL, "%s: the allocation of %s = %p cannot be found", who, arg, ptr);
-	}
-	const size_t off = (size_t)((const char *)ptr - (const char *)base);
-	if (off > size || bytes > size - off)
-		return blz_fail(BLZ_EINVAL, "%s: %s needs %zu bytes (%lld rows, row stride %lld, n = %d) but its allocation ends after %zu",
-				who, arg, bytes, (long long)rows, (long long)ld, n, off > size ? (size_t)0 : size - off);
+	const int rc = devio_check_alloc(c, who, arg, ptr, bytes, rows, ld);
+	if (rc != BLZ_OK)
+		return rc;
 	if (bytes_out)
 		*bytes_out = bytes;
+	return BLZ_OK;
+}
+
+/* the same for an operand that is `words` 8-byte words in a row and not a block: d, npiv, info */
+static int devio_check_words(const blz_ctx *c, const char *who, const char *arg, const void *ptr, int64_t words, size_t *bytes_out)
+{
+	if (!ptr)
+		return blz_fail(BLZ_EINVAL, "%s: %s is NULL", who, arg);
+	if (((uintptr_t)ptr & 7) != 0)
+		return blz_fail(BLZ_EINVAL, "%s: %s is not aligned to 8 bytes", who, arg);
+	const int rc = devio_check_alloc(c, who, arg, ptr, (size_t)words * 8, 1, words);
+	if (rc != BLZ_OK)
+		return rc;
+	if (bytes_out)
+		*bytes_out = (size_t)words * 8;
 	return BLZ_OK;
 }
 
@@ -3388,5 +3422,119 @@ extern "C" int blz_combine_device(blz_ctx *c, int64_t rows, int nterms, const ui
 	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
 		return rc;
 	HIPCHK(launch_dev_combine(c->cfg, n, rows, nterms, x, ldl, a, z, ldz, c->stream));
+	return devio_leave(c, caller);
+}
+
+/* ---- device small algebra: the n x n chain of a Krylov step and the echelon form of a caller's block (kernels:
+ * blz_devsmall.hip).  No matrix is needed and nothing of a solve is read or written: the only state is
+ * the stack and the control words of blz_rref_device, which are this call's own. ---- */
+
+struct DevRange {
+	const char *name;
+	const void *ptr;
+	size_t bytes;
+};
+
+/* no output may overlap an input or another output: outs[0 .. nout) against each other and against ins[0 .. nin) */
+static int devsmall_refuse_overlap(const char *who, const DevRange *outs, int nout, const DevRange *ins, int nin)
+{
+	for (int a = 0; a < nout; a++) {
+		if (!outs[a].ptr)
+			continue;
+		for (int b = 0; b < nin; b++)
+			if (ins[b].bytes && devalg_overlap(outs[a].ptr, outs[a].bytes, ins[b].ptr, ins[b].bytes))
+				return blz_fail(BLZ_EINVAL, "%s: %s overlaps %s", who, outs[a].name, ins[b].name);
+		for (int b = a + 1; b < nout; b++)
+			if (outs[b].ptr && devalg_overlap(outs[a].ptr, outs[a].bytes, outs[b].ptr, outs[b].bytes))
+				return blz_fail(BLZ_EINVAL, "%s: %s overlaps %s", who, outs[a].name, outs[b].name);
+	}
+	return BLZ_OK;
+}
+
+static int devsmall_begin(blz_ctx *c, const char *who, void *stream)
+{
+	int rc = devio_refuse_ranks(c, who);
+	if (rc != BLZ_OK)
+		return rc;
+	HIPCHK(hipSetDevice(c->device));
+	return devio_refuse_capture(who, (hipStream_t)stream);
+}
+
+extern "C" int blz_semi_inverse_device(blz_ctx *c, const uint64_t *vtav, uint64_t *winv, uint64_t *d, uint64_t *npiv, void *stream)
+{
+	static const char who[] = "blz_semi_inverse_device";
+	int rc = devsmall_begin(c, who, stream);
+	if (rc != BLZ_OK)
+		return rc;
+	const int n = c->un;
+	DevRange in = { "vtav", vtav, 0 }, out[3] = { { "winv", winv, 0 }, { "d", d, 0 }, { "npiv", npiv, 0 } };
+	if ((rc = devio_check_range(c, who, "vtav", vtav, n, n, &in.bytes)) != BLZ_OK ||
+	    (rc = devio_check_range(c, who, "winv", winv, n, n, &out[0].bytes)) != BLZ_OK ||
+	    (rc = devio_check_words(c, who, "d", d, n, &out[1].bytes)) != BLZ_OK ||
+	    (npiv && (rc = devio_check_words(c, who, "npiv", npiv, 1, &out[2].bytes)) != BLZ_OK))
+		return rc;
+	if ((rc = devsmall_refuse_overlap(who, out, 3, &in, 1)) != BLZ_OK)
+		return rc;
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_dev_chain(c->cfg, n, vtav, nullptr, winv, d, nullptr, npiv, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_ortho_coeffs_device(blz_ctx *c, const uint64_t *vtav, const uint64_t *vtaav, uint64_t *coef, uint64_t *npiv,
+				       void *stream)
+{
+	static const char who[] = "blz_ortho_coeffs_device";
+	int rc = devsmall_begin(c, who, stream);
+	if (rc != BLZ_OK)
+		return rc;
+	const int n = c->un;
+	DevRange in[2] = { { "vtav", vtav, 0 }, { "vtaav", vtaav, 0 } }, out[2] = { { "coef", coef, 0 }, { "npiv", npiv, 0 } };
+	if ((rc = devio_check_range(c, who, "vtav", vtav, n, n, &in[0].bytes)) != BLZ_OK ||
+	    (rc = devio_check_range(c, who, "vtaav", vtaav, n, n, &in[1].bytes)) != BLZ_OK ||
+	    (rc = devio_check_words(c, who, "coef", coef, (int64_t)BLZ_COEF_PANELS * n * n, &out[0].bytes)) != BLZ_OK ||
+	    (npiv && (rc = devio_check_words(c, who, "npiv", npiv, 1, &out[1].bytes)) != BLZ_OK))
+		return rc;
+	if ((rc = devsmall_refuse_overlap(who, out, 2, in, 2)) != BLZ_OK)
+		return rc;
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_dev_chain(c->cfg, n, vtav, vtaav, nullptr, nullptr, coef, npiv, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_rref_device(blz_ctx *c, int64_t rows, const uint64_t *x, int64_t ldx, uint64_t *e, uint64_t *z, int64_t *info,
+			       void *stream)
+{
+	static const char who[] = "blz_rref_device";
+	int rc = devsmall_begin(c, who, stream);
+	if (rc != BLZ_OK)
+		return rc;
+	if (rows < 0)
+		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
+	const int n = c->un;
+	DevRange in = { "x", x, 0 }, out[3] = { { "e", e, 0 }, { "z", z, 0 }, { "info", info, 0 } };
+	/* the kernel indexes a row as row * ldx in 64 signed bits (devio_check_range admits 2^40 of either) */
+	if (rows > 0 && ldx >= n && ldx > (INT64_MAX / 8) / rows)
+		return blz_fail(BLZ_EINVAL, "%s: %lld rows at a row stride of ldx = %lld words are beyond 64-bit byte offsets", who,
+				(long long)rows, (long long)ldx);
+	if ((rc = devio_check_range(c, who, "x", x, rows, ldx, &in.bytes)) != BLZ_OK)
+		return rc;
+	if ((rc = devio_check_range(c, who, "e", e, n, n, &out[0].bytes)) != BLZ_OK ||
+	    (z && (rc = devio_check_range(c, who, "z", z, n, n, &out[1].bytes)) != BLZ_OK) ||
+	    (rc = devio_check_words(c, who, "info", info, (int64_t)n + 1, &out[2].bytes)) != BLZ_OK)
+		return rc;
+	if ((rc = devsmall_refuse_overlap(who, out, 3, &in, 1)) != BLZ_OK)
+		return rc;
+	if (!c->devsmall_stack)
+		HIPCHK(hipMalloc((void **)&c->devsmall_stack, (size_t)dev_rref_stack_rows(c->cfg, n) * n * sizeof(u64)));
+	if (!c->devsmall_ctl)
+		HIPCHK(hipMalloc((void **)&c->devsmall_ctl, 2 * sizeof(int)));
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_dev_rref(c->cfg, n, rows, x, ldx, c->devsmall_stack, c->devsmall_ctl, e, z, (long long *)info, c->stream));
 	return devio_leave(c, caller);
 }

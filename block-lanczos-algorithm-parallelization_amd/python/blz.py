@@ -163,6 +163,43 @@ def device_square(t, n, device=None):
     return int(t.data_ptr())
 
 
+COEF_PANELS = 5     # BLZ_COEF_PANELS of include/blz.h, and the panel indices of its enum
+COEF_V_AV, COEF_V_V, COEF_V_P, COEF_P_P, COEF_P_V = 0, 1, 2, 3, 4
+
+
+def device_words(t, shape, dtypes=DEVICE_DTYPES, device=None, what="operand"):
+    """pointer of a contiguous operand of the small algebra that is not a block: `shape` words of one of `dtypes` on the
+    context's device -- the (5, n, n) coefficient panels, d (n,), npiv (1,), info (n + 1,) of int64.  Looks at data_ptr(),
+    shape, stride(), dtype and device only; anything else is a ValueError that names the fault.  torch is not imported here."""
+    shape = tuple(shape)
+    if str(t.dtype) not in dtypes:
+        raise ValueError(f"{what}: dtype {t.dtype} is not one of {', '.join(dtypes)}")
+    if getattr(t.device, "type", None) != "cuda":
+        raise ValueError(f"{what}: the tensor lives on {t.device}, not on a GPU")
+    index = t.device.index if t.device.index is not None else 0
+    if device is not None and index != device:
+        raise ValueError(f"{what}: the tensor lives on device {index}, the context on device {device}")
+    if tuple(t.shape) != shape:
+        raise ValueError(f"{what}: shape {tuple(t.shape)}, not {shape}")
+    want, run = [], 1
+    for extent in reversed(shape):
+        want.insert(0, run)
+        run *= extent
+    if any(s != w for s, w, extent in zip(tuple(t.stride()), want, shape) if extent > 1):
+        raise ValueError(f"{what}: strides {tuple(t.stride())}, the operand must be contiguous")
+    return int(t.data_ptr())
+
+
+def device_coef(t, n, device=None):
+    """pointer of the (COEF_PANELS, n, n) contiguous coefficient panels of Context.ortho_coeffs"""
+    return device_words(t, (COEF_PANELS, n, n), DEVICE_DTYPES, device, "coefficient panels")
+
+
+def device_info(t, n, device=None):
+    """pointer of the (n + 1,) int64 words [rank, pivots] of Context.rref"""
+    return device_words(t, (n + 1,), ("torch.int64",), device, "info")
+
+
 def device_terms(terms, n, device=None):
     """(rows, [(pointer of X, ld of X, pointer of A), ...]) of the 1..MAX_TERMS pairs (X, A) of Context.combine: every X goes
     through device_block, every A through device_square; the rows are the first block's and all blocks must agree."""
@@ -896,6 +933,48 @@ class Context:
         check(lib().blz_combine_device(self.h, C.c_int64(rows), C.c_int(k), xs, lds, cs, C.c_void_p(pz), C.c_int64(ldz),
                                        C.c_void_p(self._stream(stream))))
         return out
+
+    # ---- device small algebra: the n x n chain of a Krylov step and the echelon form of a block, results on the device
+
+    def _empty(self, shape, dtype=None):
+        import torch
+        return torch.empty(shape, dtype=dtype or torch.uint64, device=f"cuda:{self.device}")
+
+    def semi_inverse_device(self, vtav, stream=None):
+        """blz_semi_inverse_device(): (winv (n, n), d (n,), npiv (1,)) as torch.uint64 tensors on the device, the reference's
+        semi_inverse() of the (n, n) tensor vtav.  Ordered on `stream`; nothing is read on the host."""
+        n = self.n
+        pa = device_square(vtav, n, self.device)
+        winv, d, npiv = self._empty((n, n)), self._empty((n,)), self._empty((1,))
+        check(lib().blz_semi_inverse_device(self.h, C.c_void_p(pa), C.c_void_p(winv.data_ptr()), C.c_void_p(d.data_ptr()),
+                                            C.c_void_p(npiv.data_ptr()), C.c_void_p(self._stream(stream))))
+        return winv, d, npiv
+
+    def ortho_coeffs(self, vtav, vtaav, out=None, stream=None):
+        """blz_ortho_coeffs_device(): (coef, npiv) -- coef (5, n, n) contiguous torch.uint64 (out, or a new one), so that
+        coef[COEF_V_AV] ... coef[COEF_P_V] go straight into combine(); npiv (1,) on the device.  One launch."""
+        n = self.n
+        pa, pb = device_square(vtav, n, self.device), device_square(vtaav, n, self.device)
+        if out is None:
+            out = self._empty((COEF_PANELS, n, n))
+        pc = device_coef(out, n, self.device)
+        npiv = self._empty((1,))
+        check(lib().blz_ortho_coeffs_device(self.h, C.c_void_p(pa), C.c_void_p(pb), C.c_void_p(pc), C.c_void_p(npiv.data_ptr()),
+                                            C.c_void_p(self._stream(stream))))
+        return out, npiv
+
+    def rref(self, x, null=True, stream=None):
+        """blz_rref_device(): (e, z or None, info) of the block x -- e (n, n) the canonical RREF of its row space, z (n, n)
+        the canonical null basis of e (null=True), info (n + 1,) torch.int64 = [rank, pivot columns, -1 from the rank on]."""
+        import torch
+        n = self.n
+        px, rows, ldx, _ = device_block(x, n, None, self.device)
+        e, z, info = self._empty((n, n)), (self._empty((n, n)) if null else None), self._empty((n + 1,), torch.int64)
+        pe, pi = device_square(e, n, self.device), device_info(info, n, self.device)
+        pz = device_square(z, n, self.device) if null else None
+        check(lib().blz_rref_device(self.h, C.c_int64(rows), C.c_void_p(px), C.c_int64(ldx), C.c_void_p(pe), C.c_void_p(pz),
+                                    C.c_void_p(pi), C.c_void_p(self._stream(stream))))
+        return e, z, info
 
     def set_small(self, which, host):
         check(lib().blz_set_small(self.h, C.c_int(which), ptr(u64(host))))

@@ -571,6 +571,60 @@ int blz_dot_device(blz_ctx *ctx, int64_t rows, const uint64_t *x, int64_t ldx, c
 int blz_combine_device(blz_ctx *ctx, int64_t rows, int nterms, const uint64_t *const *x, const int64_t *ldx,
 		       const uint64_t *const *a, uint64_t *z, int64_t ldz, void *stream);
 
+/* Device small algebra: the FOURTH part of a Krylov step -- the n x n algebra between the inner product and the recombination
+ * -- and the echelon form of a caller's block, with the conventions of the device block algebra above: n and p are the
+ * context's (n the caller's width), every operand is uint64_t words in device memory whatever blz_word_bytes is, n x n
+ * operands are row-major and contiguous, results stay in device memory, the two-event ordering on `stream` with no host
+ * synchronisation, a capturing stream is BLZ_EINVAL, one rank only, residues are NOT validated (blz_set_block's contract).
+ * Each call works on a context with no matrix set, while a solve runs and after it has stopped, and touches nothing of a
+ * solve: V, TMP, AV, P, the small operands, the control words (stop flag, npiv), the iteration count, the implicit-p state,
+ * the scratch of blz_apply_device and blz_dot_device and the buffers of blz_block_rref / blz_kernel_basis stay as they are --
+ * which is why blz_semi_inverse, which works on the context's own small operands and control words, cannot stand in.
+ * Checked on the host before the first enqueue, BLZ_EINVAL with a message that names the argument: a NULL or host pointer, an
+ * operand that does not lie inside one allocation of the context's device, rows < 0, ldx < n, and ANY overlap of an output
+ * with an input or with another output (inputs may overlap each other).  Nothing is launched then.  DESIGN.md section 17.
+ *
+ * blz_semi_inverse_device   semi_inverse(), sequential/lanczos_modp.c:342-438, on the caller's n x n matrix vtav: writes winv
+ *                           (n x n), d (n words, 0 or 1) and, unless it is NULL, npiv (ONE word: the pivot count).  Word for
+ *                           word what blz_semi_inverse gives: the same pivot order, hence the same d and winv.  npiv = 0
+ *                           comes with winv = 0 and d = 0, which is what the reference's two sweeps leave.  One launch.
+ * blz_ortho_coeffs_device   the same semi-inverse AND the coefficients of orthogonalize(), :456-475, in ONE launch.  coef
+ *                           receives BLZ_COEF_PANELS contiguous n x n panels of canonical residues; with D = diag(d),
+ *                           W = winv and S = vtaav's column j where d[j] = 1, vtav's where d[j] = 0 (`spliced`, :462-466):
+ *                               BLZ_COEF_V_AV  D                    BLZ_COEF_P_P  I - D
+ *                               BLZ_COEF_V_V   (I - D) - W * S      BLZ_COEF_P_V  W
+ *                               BLZ_COEF_V_P   -vtav * D
+ *                           so that the row update of :478-491 is exactly
+ *                               v' = combine(Av * coef[V_AV] + v * coef[V_V] + p * coef[V_P])
+ *                               p' = combine(p * coef[P_P] + v * coef[P_V])
+ *                           With npiv = 0 the panels are 0, I, 0, I, 0: the step is the identity on v and p, so a loop that
+ *                           runs past the stop of :644-650 changes nothing and needs no look from the host to be safe.
+ *                           npiv as above (may be NULL).
+ * blz_rref_device           the canonical reduced row echelon form of the row space of the caller's block x: rows x n words,
+ *                           row stride ldx >= n (the words past n of a row are never read), any rows >= 0.  No reference
+ *                           counterpart; it is blz_block_rref and step 2 of blz_kernel_basis below on a caller's block.
+ *                             e     n x n: rows sorted by pivot column, zero from the rank on -- the words blz_block_rref
+ *                                   returns for the same rows
+ *                             info  n + 1 int64_t words in DEVICE memory: info[0] = the rank, info[1 + i] = the pivot column
+ *                                   of row i, -1 from the rank on
+ *                             z     n x n, may be NULL: the canonical null basis of e -- one column per free column f,
+ *                                   ascending, with 1 at f, -e[i][f] at pivot info[1 + i], 0 elsewhere; the columns from
+ *                                   n - rank on are zero; z = I when the rank is 0
+ *                           rows == 0: e = 0, rank 0, every pivot -1, z = I.  A block of full rank is decided after one tile
+ *                           per workgroup and is NOT read whole; a deficient one is read once.  The partial echelons go
+ *                           through a stack of the call's own (at most 2 x CUs x n x n words, 16 MB at n = 64) and two
+ *                           control words, allocated on first use and freed by blz_destroy.  A stride so large that
+ *                           rows * ldx leaves 64-bit byte offsets is BLZ_EINVAL.  With blz_apply_device and
+ *                           blz_combine_device the four steps of blz_kernel_basis can be done on caller-owned candidates.
+ * Limits: one rank; no capturing stream; residues are not validated; vector-ALU kernels only. */
+#define BLZ_COEF_PANELS 5
+enum { BLZ_COEF_V_AV = 0, BLZ_COEF_V_V = 1, BLZ_COEF_V_P = 2, BLZ_COEF_P_P = 3, BLZ_COEF_P_V = 4 };
+int blz_semi_inverse_device(blz_ctx *ctx, const uint64_t *vtav, uint64_t *winv, uint64_t *d, uint64_t *npiv, void *stream);
+int blz_ortho_coeffs_device(blz_ctx *ctx, const uint64_t *vtav, const uint64_t *vtaav, uint64_t *coef, uint64_t *npiv,
+			    void *stream);
+int blz_rref_device(blz_ctx *ctx, int64_t rows, const uint64_t *x, int64_t ldx, uint64_t *e, uint64_t *z, int64_t *info,
+		    void *stream);
+
 /* sparse_matrix_vector_product(y, M, x, transpose), sequential/lanczos_modp.c:266-287:
  * dst = M*src (transpose=0) or M^T*src (transpose=1), all n columns, canonical residues. */
 int blz_spmv(blz_ctx *ctx, int transpose, int src_block, int dst_block);
