@@ -13,6 +13,7 @@
  *   small  = [vtAv | vtAAv | winv | d | c | vtAvd], 6*n*n words;  ctl = DevCtl.
  *   slab[4 + side] (one rank, allocated on first use): the scratch slabs blz_apply_device multiplies in, never a caller's block.
  *   devalg_partial (allocated on first use): the partial rows of blz_dot_device, never the `partial` of an iteration in flight.
+ *   devfuse_partial (allocated on first use): the partial rows of blz_dot_pair_device, twice devalg_partial's size.
  *   devsmall_stack / devsmall_ctl (allocated on first use): the partial echelons and control words of blz_rref_device, never
  *   the rref_* buffers of blz_block_rref / blz_kernel_basis.
  */
@@ -36,6 +37,7 @@
 #include "blz_devio.h"
 #include "blz_devalg.h"
 #include "blz_devsmall.h"
+#include "blz_devfuse.h"
 
 #define HIPCHK(expr)                                                                                     \
 	do {                                                                                             \
@@ -267,6 +269,8 @@ struct blz_ctx {
 	DevCtl *apply_ctl = nullptr;			/* control words of blz_apply_device's products: the stop flag never up */
 	/* device block algebra (blz_dot_device): dev_dot_max_blocks() partial rows of un * un words, allocated on first use */
 	u64 *devalg_partial = nullptr;
+	/* fused device calls (blz_dot_pair_device): dev_dot2_max_blocks() partial rows of 2 * un * un words, allocated on first use */
+	u64 *devfuse_partial = nullptr;
 	/* device small algebra (blz_rref_device): dev_rref_stack_rows() partial echelon rows of un words and [rank-n flag, rows
 	 * stacked], allocated on first use */
 	u64 *devsmall_stack = nullptr;
@@ -511,6 +515,7 @@ extern "C" void blz_destroy(blz_ctx *c)
 	if (c->ev_ours) hipEventDestroy(c->ev_ours);
 	if (c->bad_dev) hipFree(c->bad_dev);
 	if (c->devalg_partial) hipFree(c->devalg_partial);
+	if (c->devfuse_partial) hipFree(c->devfuse_partial);
 	if (c->devsmall_stack) hipFree(c->devsmall_stack);
 	if (c->devsmall_ctl) hipFree(c->devsmall_ctl);
 	for (void *&b : c->slab)
@@ -3422,6 +3427,164 @@ extern "C" int blz_combine_device(blz_ctx *c, int64_t rows, int nterms, const ui
 	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
 		return rc;
 	HIPCHK(launch_dev_combine(c->cfg, n, rows, nterms, x, ldl, a, z, ldz, c->stream));
+	return devio_leave(c, caller);
+}
+
+/* ---- fused device calls: z = op2 (op1 x), two inner products against one block, two recombinations of shared inputs, each in
+ * one call and one pass (kernels: blz_devfuse.hip).  Nothing of a solve is read or written: the state is
+ * the scratch slabs and control words of blz_apply_device and a scratch of blz_dot_pair_device's own. ---- */
+
+extern "C" int blz_apply_pair_device(blz_ctx *c, int transpose_first, const uint64_t *x, int64_t ldx, uint64_t *y, int64_t ldy,
+				     uint64_t *z, int64_t ldz, void *stream)
+{
+	static const char who[] = "blz_apply_pair_device";
+	int rc = devio_refuse_ranks(c, who);
+	if (rc != BLZ_OK)
+		return rc;
+	NEED_MATRIX(c);
+	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
+		return rc;
+	const int t = transpose_first ? 1 : 0, ys = c->row_side[t], xs = 1 - ys;
+	size_t xb = 0, yb = 0, zb = 0;
+	if ((rc = devio_check_range(c, who, "x", x, c->glob_rows[xs], ldx, &xb)) != BLZ_OK ||
+	    (y && (rc = devio_check_range(c, who, "y", y, c->glob_rows[ys], ldy, &yb)) != BLZ_OK) ||
+	    (rc = devio_check_range(c, who, "z", z, c->glob_rows[xs], ldz, &zb)) != BLZ_OK)
+		return rc;
+	const bool in_place = (const uint64_t *)z == x && ldz == ldx;
+	if (!in_place && devalg_overlap(z, zb, x, xb))
+		return blz_fail(BLZ_EINVAL, "%s: z overlaps x without being it (the in-place form is the same pointer and the same "
+				"stride)", who);
+	if (y && devalg_overlap(y, yb, x, xb))
+		return blz_fail(BLZ_EINVAL, "%s: y overlaps x", who);
+	if (y && devalg_overlap(y, yb, z, zb))
+		return blz_fail(BLZ_EINVAL, "%s: y overlaps z", who);
+	/* the two scratch slabs and the control words of blz_apply_device */
+	for (int sd = 0; sd < 2; sd++)
+		if (!c->slab[APPLY_SLAB + sd]) {
+			const size_t bytes = (size_t)std::max<int64_t>(c->stride[sd], 1) * c->cfg.n * c->cfg.word;
+			HIPCHK(hipMalloc(&c->slab[APPLY_SLAB + sd], bytes));
+			HIPCHK(hipMemset(c->slab[APPLY_SLAB + sd], 0, bytes));
+			c->slab_bytes[APPLY_SLAB + sd] = bytes;
+		}
+	if (!c->apply_ctl) {
+		HIPCHK(hipMalloc((void **)&c->apply_ctl, sizeof(DevCtl)));
+		HIPCHK(hipMemset(c->apply_ctl, 0, sizeof(DevCtl)));
+	}
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_enter(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_block_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, c->inv_dev[xs], c->count[xs], c->un, nullptr, c->stream));
+	if ((rc = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
+		return rc;
+	if (y)	/* the intermediate is wanted: one pass more; otherwise it lives in its slab only */
+		HIPCHK(launch_block_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], c->inv_dev[ys], c->count[ys], c->un, c->stream));
+	/* back into the slab x was imported to: the first product has consumed it */
+	if ((rc = enqueue_product(c, 1 - t, APPLY_SLAB + ys, APPLY_SLAB + xs, false, nullptr, c->apply_ctl)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_block_export(c->cfg, z, ldz, c->slab[APPLY_SLAB + xs], c->inv_dev[xs], c->count[xs], c->un, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_dot_pair_device(blz_ctx *c, int64_t rows, const uint64_t *x0, int64_t ldx0, const uint64_t *x1, int64_t ldx1,
+				   const uint64_t *y, int64_t ldy, uint64_t *out, void *stream)
+{
+	static const char who[] = "blz_dot_pair_device";
+	int rc = devio_refuse_ranks(c, who);
+	if (rc != BLZ_OK)
+		return rc;
+	HIPCHK(hipSetDevice(c->device));
+	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
+		return rc;
+	if (rows < 0)
+		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
+	const int n = c->un;
+	size_t x0b = 0, x1b = 0, yb = 0, cb = 0;
+	if ((rc = devio_check_range(c, who, "x0", x0, rows, ldx0, &x0b)) != BLZ_OK ||
+	    (rc = devio_check_range(c, who, "x1", x1, rows, ldx1, &x1b)) != BLZ_OK ||
+	    (rc = devio_check_range(c, who, "y", y, rows, ldy, &yb)) != BLZ_OK ||
+	    (rc = devio_check_words(c, who, "c", out, (int64_t)2 * n * n, &cb)) != BLZ_OK)
+		return rc;
+	if (devalg_overlap(out, cb, x0, x0b))
+		return blz_fail(BLZ_EINVAL, "%s: c overlaps x0", who);
+	if (devalg_overlap(out, cb, x1, x1b))
+		return blz_fail(BLZ_EINVAL, "%s: c overlaps x1", who);
+	if (devalg_overlap(out, cb, y, yb))
+		return blz_fail(BLZ_EINVAL, "%s: c overlaps y", who);
+	if (!c->devfuse_partial)
+		HIPCHK(hipMalloc((void **)&c->devfuse_partial, (size_t)dev_dot2_max_blocks(c->cfg, n) * 2 * n * n * sizeof(u64)));
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_dev_dot2(c->cfg, n, rows, x0, ldx0, x1, ldx1, y, ldy, c->devfuse_partial, out, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_combine_pair_device(blz_ctx *c, int64_t rows, int nterms, const uint64_t *const *x, const int64_t *ldx,
+				       const uint64_t *const *a0, const uint64_t *const *a1, uint64_t *z0, int64_t ldz0, uint64_t *z1,
+				       int64_t ldz1, void *stream)
+{
+	static const char who[] = "blz_combine_pair_device";
+	int rc = devio_refuse_ranks(c, who);
+	if (rc != BLZ_OK)
+		return rc;
+	HIPCHK(hipSetDevice(c->device));
+	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
+		return rc;
+	if (nterms < 1 || nterms > BLZ_MAX_TERMS)
+		return blz_fail(BLZ_EINVAL, "%s: nterms = %d is outside 1..%d", who, nterms, BLZ_MAX_TERMS);
+	if (rows < 0)
+		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
+	if (!x || !ldx || !a0 || !a1)
+		return blz_fail(BLZ_EINVAL, "%s: the array of %s is NULL", who, !x ? "x" : !ldx ? "ldx" : !a0 ? "a0" : "a1");
+	int in[2] = { 0, 0 };
+	for (int t = 0; t < nterms; t++) {
+		if (!a0[t] && !a1[t])
+			return blz_fail(BLZ_EINVAL, "%s: term %d enters neither output (a0[%d] and a1[%d] are both NULL)", who, t, t, t);
+		in[0] += a0[t] != nullptr;
+		in[1] += a1[t] != nullptr;
+	}
+	for (int o = 0; o < 2; o++)
+		if (!in[o])
+			return blz_fail(BLZ_EINVAL, "%s: output z%d has no term (every a%d[t] is NULL)", who, o, o);
+	const int n = c->un;
+	const uint64_t *const *a[2] = { a0, a1 };
+	uint64_t *z[2] = { z0, z1 };
+	const int64_t ldz[2] = { ldz0, ldz1 };
+	size_t xb[BLZ_MAX_TERMS] = { 0 }, ab[2][BLZ_MAX_TERMS] = { { 0 } }, zb[2] = { 0, 0 };
+	long long ldl[BLZ_MAX_TERMS] = { 0 };
+	char nm[12];
+	for (int t = 0; t < nterms; t++) {
+		snprintf(nm, sizeof nm, "x[%d]", t);
+		if ((rc = devio_check_range(c, who, nm, x[t], rows, ldx[t], &xb[t])) != BLZ_OK)
+			return rc;
+		for (int o = 0; o < 2; o++) {
+			snprintf(nm, sizeof nm, "a%d[%d]", o, t);
+			if (a[o][t] && (rc = devio_check_range(c, who, nm, a[o][t], n, n, &ab[o][t])) != BLZ_OK)
+				return rc;
+		}
+		ldl[t] = ldx[t];
+	}
+	if ((rc = devio_check_range(c, who, "z0", z0, rows, ldz0, &zb[0])) != BLZ_OK ||
+	    (rc = devio_check_range(c, who, "z1", z1, rows, ldz1, &zb[1])) != BLZ_OK)
+		return rc;
+	if (rows > 0 && devalg_overlap(z0, zb[0], z1, zb[1]))
+		return blz_fail(BLZ_EINVAL, "%s: z0 overlaps z1", who);
+	for (int o = 0; o < 2; o++)
+		for (int t = 0; t < nterms; t++) {
+			const bool in_place = x[t] == z[o] && ldx[t] == ldz[o];
+			if (!in_place && devalg_overlap(z[o], zb[o], x[t], xb[t]))
+				return blz_fail(BLZ_EINVAL, "%s: z%d overlaps x[%d] without being it (the in-place form is the same pointer "
+						"and the same stride)", who, o, t);
+			for (int q = 0; q < 2; q++)
+				if (a[q][t] && devalg_overlap(z[o], zb[o], a[q][t], ab[q][t]))
+					return blz_fail(BLZ_EINVAL, "%s: z%d overlaps a%d[%d]", who, o, q, t);
+		}
+	if (rows == 0)
+		return BLZ_OK;	/* the outputs have no words */
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_dev_combine2(c->cfg, n, rows, nterms, x, ldl, a0, a1, z0, ldz0, z1, ldz1, c->stream));
 	return devio_leave(c, caller);
 }
 

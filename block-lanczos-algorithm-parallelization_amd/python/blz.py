@@ -219,6 +219,50 @@ def device_terms(terms, n, device=None):
     return rows, out
 
 
+def device_pair(t, n, device=None):
+    """pointer of the (2, n, n) contiguous panels of Context.dot_pair: [0] = x0^T y, [1] = x1^T y"""
+    return device_words(t, (2, n, n), DEVICE_DTYPES, device, "inner product pair")
+
+
+def device_pair_terms(terms, n, device=None):
+    """(rows, [(pointer of X, ld of X, pointer of A0 or None, pointer of A1 or None), ...]) of the 1..MAX_TERMS triples
+    (X, A0, A1) of Context.combine_pair: every X goes through device_block, every coefficient that is not None through
+    device_square; all blocks agree in their rows, every term enters an output and every output has a term."""
+    terms = list(terms)
+    if not 1 <= len(terms) <= MAX_TERMS:
+        raise ValueError(f"combine_pair: {len(terms)} terms, not 1..{MAX_TERMS}")
+    rows, out = None, []
+    for k, triple in enumerate(terms):
+        if len(triple) != 3:
+            raise ValueError(f"combine_pair: term {k} is not a triple (X, A0, A1)")
+        if triple[1] is None and triple[2] is None:
+            raise ValueError(f"combine_pair: term {k} enters neither output (A0 and A1 are both None)")
+        try:
+            px, rows, ldx, _ = device_block(triple[0], n, rows, device)
+            pa = [None if a is None else device_square(a, n, device) for a in triple[1:]]
+        except ValueError as e:
+            raise ValueError(f"combine_pair: term {k}: {e}") from None
+        out.append((px, ldx, pa[0], pa[1]))
+    for o in (0, 1):
+        if all(term[2 + o] is None for term in out):
+            raise ValueError(f"combine_pair: output z{o} has no term (every A{o} is None)")
+    return rows, out
+
+
+def device_pair_out(out, n, rows, device=None):
+    """[(pointer, ld), (pointer, ld)] of the two outputs (z0, z1) of Context.combine_pair: blocks of `rows` rows each"""
+    if not isinstance(out, (tuple, list)) or len(out) != 2:
+        raise ValueError("combine_pair: out is not a pair (z0, z1)")
+    res = []
+    for o, z in enumerate(out):
+        try:
+            pz, _, ldz, _ = device_block(z, n, rows, device)
+        except ValueError as e:
+            raise ValueError(f"combine_pair: output z{o}: {e}") from None
+        res.append((pz, ldz))
+    return res
+
+
 class Matrix:
     """struct sparsematrix_t of the reference (sequential/lanczos_modp.c:55-62) as numpy arrays."""
 
@@ -933,6 +977,64 @@ class Context:
         check(lib().blz_combine_device(self.h, C.c_int64(rows), C.c_int(k), xs, lds, cs, C.c_void_p(pz), C.c_int64(ldz),
                                        C.c_void_p(self._stream(stream))))
         return out
+
+    # ---- fused device calls: op2 (op1 x), two inner products against one block, two recombinations of shared inputs
+
+    def apply_pair(self, transpose_first, x, out=None, mid=None, stream=None):
+        """blz_apply_pair_device(): z = M^T (M x) (transpose_first False) / M (M^T x) in one call.  Returns z (out, or a new
+        torch.uint64 tensor; out=x is the in-place form).  mid=True allocates the intermediate, a tensor for mid receives
+        it; either way the return is (z, mid).  mid=None: the intermediate never leaves the library's scratch."""
+        xr, yr = self.apply_rows(transpose_first)
+        px, _, ldx, _ = device_block(x, self.n, xr, self.device)
+        if out is None:
+            out = self._new_block(xr)
+        pz, _, ldz, _ = device_block(out, self.n, xr, self.device)
+        if mid is True:
+            mid = self._new_block(yr)
+        py, ldy = None, 0
+        if mid is not None:
+            py, _, ldy, _ = device_block(mid, self.n, yr, self.device)
+        check(lib().blz_apply_pair_device(self.h, C.c_int(int(bool(transpose_first))), C.c_void_p(px), C.c_int64(ldx),
+                                          C.c_void_p(py), C.c_int64(ldy), C.c_void_p(pz), C.c_int64(ldz),
+                                          C.c_void_p(self._stream(stream))))
+        return out if mid is None else (out, mid)
+
+    def dot_pair(self, x0, x1, y, out=None, stream=None):
+        """blz_dot_pair_device(): out[0] = x0^T y and out[1] = x1^T y mod p in one pass, a contiguous (2, n, n) torch.uint64
+        tensor on the device (out, or a new one) whose two views go straight into ortho_coeffs.  Blocks that are the same
+        tensor are read once."""
+        px0, rows, ldx0, _ = device_block(x0, self.n, None, self.device)
+        px1, _, ldx1, _ = device_block(x1, self.n, rows, self.device)
+        py, _, ldy, _ = device_block(y, self.n, rows, self.device)
+        if out is None:
+            out = self._empty((2, self.n, self.n))
+        pc = device_pair(out, self.n, self.device)
+        check(lib().blz_dot_pair_device(self.h, C.c_int64(rows), C.c_void_p(px0), C.c_int64(ldx0), C.c_void_p(px1),
+                                        C.c_int64(ldx1), C.c_void_p(py), C.c_int64(ldy), C.c_void_p(pc),
+                                        C.c_void_p(self._stream(stream))))
+        return out
+
+    def combine_pair(self, terms, out=None, stream=None):
+        """blz_combine_pair_device(): (z0, z1) with z0 = sum of X @ A0 and z1 = sum of X @ A1 mod p over the 1..4 triples
+        (X, A0, A1) of `terms`, every X read once; A0 or A1 may be None (the term does not enter that output).  Coefficients
+        as in combine().  out: (z0, z1), each a new block, the caller's, or one of the X (the in-place form), or None."""
+        terms = [tuple(t) for t in terms]
+        if not 1 <= len(terms) <= MAX_TERMS:
+            raise ValueError(f"combine_pair: {len(terms)} terms, not 1..{MAX_TERMS}")
+        terms = [t if len(t) != 3 else (t[0],) + tuple(None if a is None else self._coefficient(a, stream) for a in t[1:])
+                 for t in terms]
+        rows, args = device_pair_terms(terms, self.n, self.device)
+        if out is None:
+            out = (self._new_block(rows), self._new_block(rows))
+        (pz0, ldz0), (pz1, ldz1) = device_pair_out(out, self.n, rows, self.device)
+        k = len(args)
+        xs = (C.c_void_p * k)(*[a[0] for a in args])
+        lds = (C.c_int64 * k)(*[a[1] for a in args])
+        c0 = (C.c_void_p * k)(*[a[2] for a in args])
+        c1 = (C.c_void_p * k)(*[a[3] for a in args])
+        check(lib().blz_combine_pair_device(self.h, C.c_int64(rows), C.c_int(k), xs, lds, c0, c1, C.c_void_p(pz0),
+                                            C.c_int64(ldz0), C.c_void_p(pz1), C.c_int64(ldz1), C.c_void_p(self._stream(stream))))
+        return out[0], out[1]
 
     # ---- device small algebra: the n x n chain of a Krylov step and the echelon form of a block, results on the device
 

@@ -625,6 +625,45 @@ int blz_ortho_coeffs_device(blz_ctx *ctx, const uint64_t *vtav, const uint64_t *
 int blz_rref_device(blz_ctx *ctx, int64_t rows, const uint64_t *x, int64_t ldx, uint64_t *e, uint64_t *z, int64_t *info,
 		    void *stream);
 
+/* Fused device calls: the same parts of a Krylov step in fewer calls and fewer passes over the tall blocks -- z = op2 (op1 x),
+ * two inner products against one block, two recombinations of shared inputs.  Every convention is that of the calls above:
+ * uint64_t words in device memory, the context's n and p, row stride ld >= n with the words past n never read or written, the
+ * two-event ordering on `stream` with no host synchronisation, a capturing stream and anything but one rank are BLZ_EINVAL,
+ * every pointer is checked on the host before the first enqueue and the message names the argument, residues are NOT
+ * validated, nothing of a solve is read or written.  With them a host-free step of the iteration is FOUR calls --
+ * apply_pair, dot_pair, ortho_coeffs, combine_pair -- where it was seven.
+ *
+ * blz_apply_pair_device    transpose_first = 0: y = M * x, z = M^T * y;  transpose_first = 1: y = M^T * x, z = M * y.  x and z
+ *                          have the x_rows of blz_apply_rows(ctx, transpose_first), y its y_rows.  y == NULL: the intermediate
+ *                          is not wanted, ldy is ignored, and it lives only in the scratch slab of its side, neither exported
+ *                          nor imported; y != NULL: it is exported as well (one pass more).  z may BE x -- the same pointer and
+ *                          the same stride: the in-place form; otherwise x, y and z overlap one another nowhere.  Needs a
+ *                          matrix; on a bordered context both products are the bordered operator, signed and wide slabs run
+ *                          as in blz_apply_device, whose two scratch slabs and control words it shares.  Word for word what two
+ *                          blz_apply_device calls give.
+ * blz_dot_pair_device      c[0] = X0^T * Y and c[1] = X1^T * Y mod p, two contiguous n x n panels (2 * n * n words) in ONE pass:
+ *                          dot_pair(v, Av, Av) gives vtAv and vtAAv where blz_ortho_coeffs_device takes them, c and c + n*n.
+ *                          Any of x0, x1 and y may be the same block (the same pointer and the same stride), which is then
+ *                          read once; c must overlap none of them.  rows == 0: both panels are zero.  Both triangles of a Gram
+ *                          panel are written.  The partial sums go through a scratch buffer of this call's own (twice that of
+ *                          blz_dot_device at the most, allocated on first use, freed by blz_destroy).  At n > 32 and
+ *                          p >= 2^32 other than 2^61 - 1 the call runs the kernel of blz_dot_device twice.
+ * blz_combine_pair_device  Z0 = sum_t X_t * A0_t and Z1 = sum_t X_t * A1_t mod p, 1 <= nterms <= BLZ_MAX_TERMS, every row of
+ *                          every X_t read ONCE.  a0[t] or a1[t] may be NULL: term t does not enter that output.  A term that
+ *                          enters neither output and an output with no term are BLZ_EINVAL, named.  Each of z0 and z1 may BE
+ *                          one of the x[t] (the same pointer and the same stride); otherwise an output overlaps no x[t].  z0 and
+ *                          z1 overlap each other nowhere and neither overlaps a coefficient matrix.  rows == 0: nothing is
+ *                          touched.  One launch at every width and panel count.  The update of :478-491 is one call: terms
+ *                          (Av, coef[V_AV], NULL), (v, coef[V_V], coef[P_V]), (p, coef[V_P], coef[P_P]), z0 = v, z1 = p.
+ * Limits: one rank; no capturing stream; residues are not validated; vector-ALU kernels only. */
+int blz_apply_pair_device(blz_ctx *ctx, int transpose_first, const uint64_t *x, int64_t ldx, uint64_t *y, int64_t ldy,
+			  uint64_t *z, int64_t ldz, void *stream);
+int blz_dot_pair_device(blz_ctx *ctx, int64_t rows, const uint64_t *x0, int64_t ldx0, const uint64_t *x1, int64_t ldx1,
+			const uint64_t *y, int64_t ldy, uint64_t *c, void *stream);
+int blz_combine_pair_device(blz_ctx *ctx, int64_t rows, int nterms, const uint64_t *const *x, const int64_t *ldx,
+			    const uint64_t *const *a0, const uint64_t *const *a1, uint64_t *z0, int64_t ldz0, uint64_t *z1,
+			    int64_t ldz1, void *stream);
+
 /* sparse_matrix_vector_product(y, M, x, transpose), sequential/lanczos_modp.c:266-287:
  * dst = M*src (transpose=0) or M^T*src (transpose=1), all n columns, canonical residues. */
 int blz_spmv(blz_ctx *ctx, int transpose, int src_block, int dst_block);
