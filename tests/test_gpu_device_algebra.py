@@ -8,6 +8,9 @@ Context.combine) mod p on caller-owned torch tensors, against
 
 Every comparison is equality of u64 words.  Tensors are int64 views of the u64 words where torch has to compute on them (same
 bits), torch.uint64 where the library allocates.
+
+The reducer ladder -- the Barrett primes of 33 ... 60 bits, the two primes either side of 2^32, the widths 2 ... 63 this file
+leaves out, and blocks long enough that an accumulator passes ModP::chunk -- is tests/test_gpu_device_exact.py.
 """
 import ctypes as C
 import os

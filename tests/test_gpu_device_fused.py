@@ -7,7 +7,9 @@ blz_combine_pair_device (Context.combine_pair) on caller-owned torch tensors, ag
     past the stop;
   - an undisturbed twin for "the solve is left alone".
 
-Every comparison is equality of u64 words.
+Every comparison is equality of u64 words.  The reducer ladder -- every reducer class of csrc/modp.h, the widths between
+those of WIDTHS, sums past ModP::chunk in k_dev_dot2 and k_dev_combine2 -- is tests/test_gpu_device_exact.py, which imports the
+helpers, MASKS and four_calls_against_twin from here.
 """
 import ctypes as C
 import os

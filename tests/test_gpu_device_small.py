@@ -8,7 +8,9 @@
     host inside the loop, from the usual and from a rank-deficient start, and on past the stop;
   - an undisturbed twin for "the solve is left alone".
 
-Every comparison is equality of u64 words.
+Every comparison is equality of u64 words.  The reducer ladder -- every reducer class of csrc/modp.h, k_dev_chain at 1024
+threads with lg = 5, k_dev_rref with lane groups of 2 and 32 and a reduction past ModP::chunk -- is
+tests/test_gpu_device_exact.py.
 """
 import ctypes as C
 import os
