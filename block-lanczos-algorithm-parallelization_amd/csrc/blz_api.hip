@@ -38,6 +38,7 @@
 #include "blz_devalg.h"
 #include "blz_devsmall.h"
 #include "blz_devfuse.h"
+#include "blz_devrank.h"
 
 #define HIPCHK(expr)                                                                                     \
 	do {                                                                                             \
@@ -275,6 +276,11 @@ struct blz_ctx {
 	 * stacked], allocated on first use */
 	u64 *devsmall_stack = nullptr;
 	int *devsmall_ctl = nullptr;
+	/* device blocks on ranks (blz_set_device_ranks): the blocks of the device-block family are this
+	 * rank's own rows in slab order.  devrank_send = the rank's residues of a dot (2 un * un words), devrank_recv = where
+	 * their all-reduce lands; both this family's own (never dot_send / dot_recv), allocated on first use */
+	bool device_ranks = false;
+	u64 *devrank_send = nullptr, *devrank_recv = nullptr;
 };
 
 enum { APPLY_SLAB = 4 };
@@ -309,7 +315,8 @@ struct Span {
 	}
 };
 
-static inline int side_of(int block) { return block == BLZ_TMP ? 1 : 0; }
+/* (the scratch slab of side 1 counts: on ranks enqueue_product gathers by the side of its source) */
+static inline int side_of(int block) { return block == BLZ_TMP || block == APPLY_SLAB + 1 ? 1 : 0; }
 
 static inline char *slab_ptr(const blz_ctx *c, int block) { return (char *)c->slab[block]; }
 
@@ -518,6 +525,8 @@ extern "C" void blz_destroy(blz_ctx *c)
 	if (c->devfuse_partial) hipFree(c->devfuse_partial);
 	if (c->devsmall_stack) hipFree(c->devsmall_stack);
 	if (c->devsmall_ctl) hipFree(c->devsmall_ctl);
+	if (c->devrank_send) hipFree(c->devrank_send);
+	if (c->devrank_recv) hipFree(c->devrank_recv);
 	for (void *&b : c->slab)
 		if (b) hipFree(b);
 	for (void *&b : c->gath)
@@ -2938,6 +2947,9 @@ extern "C" int blz_set_exchange_mode(blz_ctx *c, int external)
 	if (external && c->have_matrix && c->rhs && c->rhs_ranks)
 		return blz_fail(BLZ_EINVAL, "blz_set_exchange_mode: the context carries a right-hand side on several ranks (the all-reduce "
 				"of its border words is the library's own)");
+	if (external && c->device_ranks)
+		return blz_fail(BLZ_EINVAL, "blz_set_exchange_mode: the context has device blocks on ranks switched on "
+				"(blz_set_device_ranks), whose exchange is the library's own");
 	c->external_exchange = external != 0;
 	return BLZ_OK;
 }
@@ -3087,9 +3099,135 @@ static int devio_refuse_ranks(const blz_ctx *c, const char *who)
 {
 	if (!c)
 		return blz_fail(BLZ_EINVAL, "%s: NULL context", who);
+	if (c->device_ranks) {	/* blocks are rank-local: ranks are welcome, the caller's own exchange is not */
+		if (c->external_exchange)
+			return blz_fail(BLZ_EINVAL, "%s: device blocks on ranks need the library's own exchange, and the context is in "
+					"external-exchange mode (blz_set_exchange_mode)", who);
+		return BLZ_OK;
+	}
 	if (c->nranks > 1 || c->comm || c->loop || c->force_comm)
 		return blz_fail(BLZ_EINVAL, "%s: device blocks need a single rank without a communicator, a loopback group or "
 				"BLZ_FORCE_COMM (see DESIGN.md section 15)", who);
+	return BLZ_OK;
+}
+
+/* ---- device blocks on ranks (kernels: blz_devrank.hip).  With blz_set_device_ranks a block of the
+ * device-block family is the rank's own rows, count[side] of them, in slab order: import and export are the identity, the
+ * products are enqueue_product with its exchange, an inner product ends in an all-reduce.  Every refusal below is a function
+ * of what all ranks share (the mode, the matrix' shape and partition, the communicator's size, p), so either every rank
+ * passes or every rank refuses, before the first enqueue and before any rendezvous. ---- */
+
+extern "C" int blz_set_device_ranks(blz_ctx *c, int on)
+{
+	if (!c)
+		return blz_fail(BLZ_EINVAL, "blz_set_device_ranks: NULL context");
+	c->device_ranks = on != 0;
+	return BLZ_OK;
+}
+
+extern "C" int blz_device_ranks(const blz_ctx *c) { return c && c->device_ranks ? 1 : 0; }
+
+extern "C" int blz_local_row_ids(const blz_ctx *c, int block, int64_t *ids)
+{
+	if (!c || !c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "no matrix loaded (blz_set_matrix)");
+	if (block < 0 || block > 3)
+		return blz_fail(BLZ_EINVAL, "blz_local_row_ids: block %d is not one of V, TMP, AV, P", block);
+	const int sd = side_of(block);
+	if (!ids && c->count[sd] > 0)
+		return blz_fail(BLZ_EINVAL, "blz_local_row_ids: ids is NULL");
+	for (int64_t q = 0; q < c->count[sd]; q++)
+		ids[q] = c->inv[sd].empty() ? c->first[sd] + q : (int64_t)c->inv[sd][(size_t)(c->first[sd] + q)];
+	return BLZ_OK;
+}
+
+/* rows of a block of side sd as the device-block family sees it: the rank's own with the mode on, all of them otherwise
+ * (the same number on one rank) */
+static inline int64_t devio_rows(const blz_ctx *c, int sd) { return c->device_ranks ? c->count[sd] : c->glob_rows[sd]; }
+
+/* the numbering an import / export goes through: none with the mode on (slab order) */
+static inline const int32_t *devio_inv(const blz_ctx *c, int sd) { return c->device_ranks ? nullptr : c->inv_dev[sd]; }
+
+/* a product of a mode-on context, before anything is enqueued: its short-side form has no scratch slab to run in, and an
+ * exchange needs its communicator */
+static int devrank_refuse_product(const blz_ctx *c, const char *who, int t)
+{
+	if (!c->device_ranks)
+		return BLZ_OK;
+	if (c->short_side[t])
+		return blz_fail(BLZ_EINVAL, "%s: product %d of this matrix runs in the short-side form (blz_short_side), which device "
+				"blocks on ranks do not have", who, t);
+	if (c->nranks > 1 && !c->comm && !c->loop)
+		return blz_fail(BLZ_ECOMM, "%s: nranks > 1 but blz_comm_init was not called", who);
+	return BLZ_OK;
+}
+
+/* An error inside a collective device call, after the checks: the peers are at, or on their way to, a rendezvous this rank
+ * will not reach.  Mark the loopback group broken so that they return BLZ_ECOMM at once, not after BLZ_LOOP_TIMEOUT_S.
+ * (Mode-on calls only: nothing else changes what it does on an error.) */
+static int devrank_collective_exit(blz_ctx *c, int rc)
+{
+	if (rc != BLZ_OK && c->device_ranks && c->loop) {
+		std::lock_guard<std::mutex> lk(c->loop->mu);
+		c->loop->broken = true;
+		c->loop->cv.notify_all();
+	}
+	return rc;
+}
+
+/* ranks of the context's communicator (1 without one): the ranks of a collective dot, which needs no matrix */
+static int devrank_comm_ranks(const blz_ctx *c, int *out)
+{
+	int cnt = 1;
+	if (c->loop)
+		cnt = c->loop->nranks;
+	else if (c->comm)
+		NCCLCHK(g_rccl.CommCount(c->comm, &cnt));
+	*out = cnt;
+	return BLZ_OK;
+}
+
+/* Is this dot collective, and may it be?  *N = the ranks its sum runs over (1: today's path, straight into c).  Checked
+ * before anything is enqueued: nranks * p <= 2^64 (blz_set_matrix's rule: the u64 sum of the ranks' residues must not wrap). */
+static int devrank_dot_ranks(const blz_ctx *c, const char *who, int *N, bool *collective)
+{
+	*N = 1;
+	*collective = false;
+	if (!c->device_ranks)
+		return BLZ_OK;
+	int rc = devrank_comm_ranks(c, N);
+	if (rc != BLZ_OK)
+		return rc;
+	if (c->have_matrix && c->nranks > 1 && !c->comm && !c->loop)
+		return blz_fail(BLZ_ECOMM, "%s: nranks > 1 but blz_comm_init was not called", who);
+	*collective = (c->comm || c->loop) && (*N > 1 || c->force_comm);
+	if (*collective && (unsigned __int128)*N * c->prime > ((unsigned __int128)1 << 64))
+		return blz_fail(BLZ_EINVAL, "%s: nranks * p must not exceed 2**64 (u64 all-reduce of residues): %d ranks", who, *N);
+	return BLZ_OK;
+}
+
+/* the tail of a collective dot on the context's stream: `words` residues of this rank in devrank_send -> all-reduce ->
+ * their sums' residues in out */
+static int devrank_dot_finish(blz_ctx *c, uint64_t *out, int words)
+{
+	int rc;
+	{
+		Span sp(c, PK_AR);
+		rc = coll_allreduce_u64(c, c->devrank_send, c->devrank_recv, (size_t)words, c->stream);
+	}
+	if (rc != BLZ_OK)
+		return rc;
+	HIPCHK(launch_residue_sums(c->cfg, out, c->devrank_recv, words, c->stream));
+	return BLZ_OK;
+}
+
+static int devrank_dot_buffers(blz_ctx *c)
+{
+	const size_t bytes = (size_t)2 * c->un * c->un * sizeof(u64);
+	if (!c->devrank_send)
+		HIPCHK(hipMalloc((void **)&c->devrank_send, bytes));
+	if (!c->devrank_recv)
+		HIPCHK(hipMalloc((void **)&c->devrank_recv, bytes));
 	return BLZ_OK;
 }
 
@@ -3222,7 +3360,7 @@ extern "C" int blz_set_block_device(blz_ctx *c, int block, const uint64_t *dev, 
 	if (block < 0 || block > 3)
 		return blz_fail(BLZ_EINVAL, "blz_set_block_device: block %d is not one of V, TMP, AV, P", block);
 	const int sd = side_of(block);
-	if ((rc = devio_check_range(c, "blz_set_block_device", "dev", dev, c->glob_rows[sd], ld, nullptr)) != BLZ_OK)
+	if ((rc = devio_check_range(c, "blz_set_block_device", "dev", dev, devio_rows(c, sd), ld, nullptr)) != BLZ_OK)
 		return rc;
 	if (bad && !c->bad_dev)
 		HIPCHK(hipMalloc((void **)&c->bad_dev, sizeof(unsigned long long)));
@@ -3235,8 +3373,10 @@ extern "C" int blz_set_block_device(blz_ctx *c, int block, const uint64_t *dev, 
 	}
 	if (bad)
 		HIPCHK(hipMemsetAsync(c->bad_dev, 0, sizeof(unsigned long long), c->stream));
-	HIPCHK(launch_block_import(c->cfg, c->slab[block], dev, ld, c->inv_dev[sd], c->count[sd], c->un, bad ? c->bad_dev : nullptr,
+	HIPCHK(launch_block_import(c->cfg, c->slab[block], dev, ld, devio_inv(c, sd), c->count[sd], c->un, bad ? c->bad_dev : nullptr,
 				   c->stream));
+	if (c->gath_holds[sd] == block)
+		c->gath_holds[sd] = -1;		/* on ranks: the gathered copy is of the rows the block had before */
 	if ((rc = devio_leave(c, caller)) != BLZ_OK)
 		return rc;
 	if (bad) {
@@ -3261,7 +3401,7 @@ extern "C" int blz_get_block_device(blz_ctx *c, int block, uint64_t *dev, int64_
 	if (block < 0 || block > 3)
 		return blz_fail(BLZ_EINVAL, "blz_get_block_device: block %d is not one of V, TMP, AV, P", block);
 	const int sd = side_of(block);
-	if ((rc = devio_check_range(c, "blz_get_block_device", "dev", dev, c->glob_rows[sd], ld, nullptr)) != BLZ_OK)
+	if ((rc = devio_check_range(c, "blz_get_block_device", "dev", dev, devio_rows(c, sd), ld, nullptr)) != BLZ_OK)
 		return rc;
 	hipStream_t caller = (hipStream_t)stream;
 	if ((rc = devio_enter(c, caller)) != BLZ_OK)
@@ -3272,7 +3412,7 @@ extern "C" int blz_get_block_device(blz_ctx *c, int block, uint64_t *dev, int64_
 		HIPCHK(launch_identity_tail(c->small, np, c->stream));
 		c->p_implicit = false;
 	}
-	HIPCHK(launch_block_export(c->cfg, dev, ld, c->slab[block], c->inv_dev[sd], c->count[sd], c->un, c->stream));
+	HIPCHK(launch_block_export(c->cfg, dev, ld, c->slab[block], devio_inv(c, sd), c->count[sd], c->un, c->stream));
 	return devio_leave(c, caller);
 }
 
@@ -3282,9 +3422,9 @@ extern "C" int blz_apply_rows(const blz_ctx *c, int transpose, int64_t *x_rows, 
 		return blz_fail(BLZ_EINVAL, "no matrix loaded (blz_set_matrix)");
 	const int ys = c->row_side[transpose ? 1 : 0];
 	if (x_rows)
-		*x_rows = c->glob_rows[1 - ys];
+		*x_rows = devio_rows(c, 1 - ys);
 	if (y_rows)
-		*y_rows = c->glob_rows[ys];
+		*y_rows = devio_rows(c, ys);
 	return BLZ_OK;
 }
 
@@ -3298,31 +3438,40 @@ extern "C" int blz_apply_device(blz_ctx *c, int transpose, const uint64_t *x, in
 		return rc;
 	const int t = transpose ? 1 : 0, ys = c->row_side[t], xs = 1 - ys;
 	size_t xb = 0, yb = 0;
-	if ((rc = devio_check_range(c, "blz_apply_device", "x", x, c->glob_rows[xs], ldx, &xb)) != BLZ_OK ||
-	    (rc = devio_check_range(c, "blz_apply_device", "y", y, c->glob_rows[ys], ldy, &yb)) != BLZ_OK)
+	if ((rc = devio_check_range(c, "blz_apply_device", "x", x, devio_rows(c, xs), ldx, &xb)) != BLZ_OK ||
+	    (rc = devio_check_range(c, "blz_apply_device", "y", y, devio_rows(c, ys), ldy, &yb)) != BLZ_OK)
 		return rc;
 	if ((const char *)x < (const char *)y + yb && (const char *)y < (const char *)x + xb)
 		return blz_fail(BLZ_EINVAL, "blz_apply_device: x and y overlap");
-	/* two scratch slabs of the context's own, one per side, and control words whose stop flag is never up */
-	for (int sd = 0; sd < 2; sd++)
-		if (!c->slab[APPLY_SLAB + sd]) {
-			const size_t bytes = (size_t)std::max<int64_t>(c->stride[sd], 1) * c->cfg.n * c->cfg.word;
-			HIPCHK(hipMalloc(&c->slab[APPLY_SLAB + sd], bytes));
-			HIPCHK(hipMemset(c->slab[APPLY_SLAB + sd], 0, bytes));
-			c->slab_bytes[APPLY_SLAB + sd] = bytes;
+	if ((rc = devrank_refuse_product(c, "blz_apply_device", t)) != BLZ_OK)
+		return rc;
+	/* (on ranks the product is collective from here on: an error exit tells the loopback peers) */
+	auto enqueue = [&]() -> int {
+		/* two scratch slabs of the context's own, one per side, and control words whose stop flag is never up.  On ranks the
+		 * rows past count[side] of a slab are never written and stay zero, which the all-gather relies on */
+		for (int sd = 0; sd < 2; sd++)
+			if (!c->slab[APPLY_SLAB + sd]) {
+				const size_t bytes = (size_t)std::max<int64_t>(c->stride[sd], 1) * c->cfg.n * c->cfg.word;
+				HIPCHK(hipMalloc(&c->slab[APPLY_SLAB + sd], bytes));
+				HIPCHK(hipMemset(c->slab[APPLY_SLAB + sd], 0, bytes));
+				c->slab_bytes[APPLY_SLAB + sd] = bytes;
+			}
+		if (!c->apply_ctl) {
+			HIPCHK(hipMalloc((void **)&c->apply_ctl, sizeof(DevCtl)));
+			HIPCHK(hipMemset(c->apply_ctl, 0, sizeof(DevCtl)));
 		}
-	if (!c->apply_ctl) {
-		HIPCHK(hipMalloc((void **)&c->apply_ctl, sizeof(DevCtl)));
-		HIPCHK(hipMemset(c->apply_ctl, 0, sizeof(DevCtl)));
-	}
-	hipStream_t caller = (hipStream_t)stream;
-	if ((rc = devio_enter(c, caller)) != BLZ_OK)
-		return rc;
-	HIPCHK(launch_block_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, c->inv_dev[xs], c->count[xs], c->un, nullptr, c->stream));
-	if ((rc = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
-		return rc;
-	HIPCHK(launch_block_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], c->inv_dev[ys], c->count[ys], c->un, c->stream));
-	return devio_leave(c, caller);
+		hipStream_t caller = (hipStream_t)stream;
+		int rc_ = devio_enter(c, caller);
+		if (rc_ != BLZ_OK)
+			return rc_;
+		HIPCHK(launch_block_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, devio_inv(c, xs), c->count[xs], c->un, nullptr,
+					   c->stream));
+		if ((rc_ = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
+			return rc_;
+		HIPCHK(launch_block_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], devio_inv(c, ys), c->count[ys], c->un, c->stream));
+		return devio_leave(c, caller);
+	};
+	return devrank_collective_exit(c, enqueue());
 }
 
 extern "C" int blz_apply_release(blz_ctx *c)
@@ -3374,13 +3523,26 @@ extern "C" int blz_dot_device(blz_ctx *c, int64_t rows, const uint64_t *x, int64
 		return blz_fail(BLZ_EINVAL, "%s: c overlaps x", who);
 	if (devalg_overlap(out, cb, y, yb))
 		return blz_fail(BLZ_EINVAL, "%s: c overlaps y", who);
-	if (!c->devalg_partial)
-		HIPCHK(hipMalloc((void **)&c->devalg_partial, (size_t)dev_dot_max_blocks(c->cfg, n) * n * n * sizeof(u64)));
-	hipStream_t caller = (hipStream_t)stream;
-	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
+	int N = 1;
+	bool collective = false;
+	if ((rc = devrank_dot_ranks(c, who, &N, &collective)) != BLZ_OK)
 		return rc;
-	HIPCHK(launch_dev_dot(c->cfg, n, rows, x, ldx, y, ldy, c->devalg_partial, out, c->stream));
-	return devio_leave(c, caller);
+	auto enqueue = [&]() -> int {
+		if (!c->devalg_partial)
+			HIPCHK(hipMalloc((void **)&c->devalg_partial, (size_t)dev_dot_max_blocks(c->cfg, n) * n * n * sizeof(u64)));
+		int rc_ = collective ? devrank_dot_buffers(c) : BLZ_OK;
+		if (rc_ != BLZ_OK)
+			return rc_;
+		hipStream_t caller = (hipStream_t)stream;
+		if ((rc_ = devio_wait_caller(c, caller)) != BLZ_OK)
+			return rc_;
+		/* on ranks: this rank's residues into the send buffer, their sums over the ranks, the sums' residues into c */
+		HIPCHK(launch_dev_dot(c->cfg, n, rows, x, ldx, y, ldy, c->devalg_partial, collective ? c->devrank_send : out, c->stream));
+		if (collective && (rc_ = devrank_dot_finish(c, out, n * n)) != BLZ_OK)
+			return rc_;
+		return devio_leave(c, caller);
+	};
+	return collective ? devrank_collective_exit(c, enqueue()) : enqueue();
 }
 
 extern "C" int blz_combine_device(blz_ctx *c, int64_t rows, int nterms, const uint64_t *const *x, const int64_t *ldx,
@@ -3446,9 +3608,9 @@ extern "C" int blz_apply_pair_device(blz_ctx *c, int transpose_first, const uint
 		return rc;
 	const int t = transpose_first ? 1 : 0, ys = c->row_side[t], xs = 1 - ys;
 	size_t xb = 0, yb = 0, zb = 0;
-	if ((rc = devio_check_range(c, who, "x", x, c->glob_rows[xs], ldx, &xb)) != BLZ_OK ||
-	    (y && (rc = devio_check_range(c, who, "y", y, c->glob_rows[ys], ldy, &yb)) != BLZ_OK) ||
-	    (rc = devio_check_range(c, who, "z", z, c->glob_rows[xs], ldz, &zb)) != BLZ_OK)
+	if ((rc = devio_check_range(c, who, "x", x, devio_rows(c, xs), ldx, &xb)) != BLZ_OK ||
+	    (y && (rc = devio_check_range(c, who, "y", y, devio_rows(c, ys), ldy, &yb)) != BLZ_OK) ||
+	    (rc = devio_check_range(c, who, "z", z, devio_rows(c, xs), ldz, &zb)) != BLZ_OK)
 		return rc;
 	const bool in_place = (const uint64_t *)z == x && ldz == ldx;
 	if (!in_place && devalg_overlap(z, zb, x, xb))
@@ -3458,31 +3620,39 @@ extern "C" int blz_apply_pair_device(blz_ctx *c, int transpose_first, const uint
 		return blz_fail(BLZ_EINVAL, "%s: y overlaps x", who);
 	if (y && devalg_overlap(y, yb, z, zb))
 		return blz_fail(BLZ_EINVAL, "%s: y overlaps z", who);
-	/* the two scratch slabs and the control words of blz_apply_device */
-	for (int sd = 0; sd < 2; sd++)
-		if (!c->slab[APPLY_SLAB + sd]) {
-			const size_t bytes = (size_t)std::max<int64_t>(c->stride[sd], 1) * c->cfg.n * c->cfg.word;
-			HIPCHK(hipMalloc(&c->slab[APPLY_SLAB + sd], bytes));
-			HIPCHK(hipMemset(c->slab[APPLY_SLAB + sd], 0, bytes));
-			c->slab_bytes[APPLY_SLAB + sd] = bytes;
+	if ((rc = devrank_refuse_product(c, who, t)) != BLZ_OK || (rc = devrank_refuse_product(c, who, 1 - t)) != BLZ_OK)
+		return rc;
+	auto enqueue = [&]() -> int {	/* (collective on ranks, as blz_apply_device) */
+		/* the two scratch slabs and the control words of blz_apply_device */
+		for (int sd = 0; sd < 2; sd++)
+			if (!c->slab[APPLY_SLAB + sd]) {
+				const size_t bytes = (size_t)std::max<int64_t>(c->stride[sd], 1) * c->cfg.n * c->cfg.word;
+				HIPCHK(hipMalloc(&c->slab[APPLY_SLAB + sd], bytes));
+				HIPCHK(hipMemset(c->slab[APPLY_SLAB + sd], 0, bytes));
+				c->slab_bytes[APPLY_SLAB + sd] = bytes;
+			}
+		if (!c->apply_ctl) {
+			HIPCHK(hipMalloc((void **)&c->apply_ctl, sizeof(DevCtl)));
+			HIPCHK(hipMemset(c->apply_ctl, 0, sizeof(DevCtl)));
 		}
-	if (!c->apply_ctl) {
-		HIPCHK(hipMalloc((void **)&c->apply_ctl, sizeof(DevCtl)));
-		HIPCHK(hipMemset(c->apply_ctl, 0, sizeof(DevCtl)));
-	}
-	hipStream_t caller = (hipStream_t)stream;
-	if ((rc = devio_enter(c, caller)) != BLZ_OK)
-		return rc;
-	HIPCHK(launch_block_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, c->inv_dev[xs], c->count[xs], c->un, nullptr, c->stream));
-	if ((rc = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
-		return rc;
-	if (y)	/* the intermediate is wanted: one pass more; otherwise it lives in its slab only */
-		HIPCHK(launch_block_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], c->inv_dev[ys], c->count[ys], c->un, c->stream));
-	/* back into the slab x was imported to: the first product has consumed it */
-	if ((rc = enqueue_product(c, 1 - t, APPLY_SLAB + ys, APPLY_SLAB + xs, false, nullptr, c->apply_ctl)) != BLZ_OK)
-		return rc;
-	HIPCHK(launch_block_export(c->cfg, z, ldz, c->slab[APPLY_SLAB + xs], c->inv_dev[xs], c->count[xs], c->un, c->stream));
-	return devio_leave(c, caller);
+		hipStream_t caller = (hipStream_t)stream;
+		int rc_ = devio_enter(c, caller);
+		if (rc_ != BLZ_OK)
+			return rc_;
+		HIPCHK(launch_block_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, devio_inv(c, xs), c->count[xs], c->un, nullptr,
+					   c->stream));
+		if ((rc_ = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
+			return rc_;
+		if (y)	/* the intermediate is wanted: one pass more; otherwise it lives in its slab only */
+			HIPCHK(launch_block_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], devio_inv(c, ys), c->count[ys], c->un,
+						   c->stream));
+		/* back into the slab x was imported to: the first product has consumed it */
+		if ((rc_ = enqueue_product(c, 1 - t, APPLY_SLAB + ys, APPLY_SLAB + xs, false, nullptr, c->apply_ctl)) != BLZ_OK)
+			return rc_;
+		HIPCHK(launch_block_export(c->cfg, z, ldz, c->slab[APPLY_SLAB + xs], devio_inv(c, xs), c->count[xs], c->un, c->stream));
+		return devio_leave(c, caller);
+	};
+	return devrank_collective_exit(c, enqueue());
 }
 
 extern "C" int blz_dot_pair_device(blz_ctx *c, int64_t rows, const uint64_t *x0, int64_t ldx0, const uint64_t *x1, int64_t ldx1,
@@ -3510,13 +3680,27 @@ extern "C" int blz_dot_pair_device(blz_ctx *c, int64_t rows, const uint64_t *x0,
 		return blz_fail(BLZ_EINVAL, "%s: c overlaps x1", who);
 	if (devalg_overlap(out, cb, y, yb))
 		return blz_fail(BLZ_EINVAL, "%s: c overlaps y", who);
-	if (!c->devfuse_partial)
-		HIPCHK(hipMalloc((void **)&c->devfuse_partial, (size_t)dev_dot2_max_blocks(c->cfg, n) * 2 * n * n * sizeof(u64)));
-	hipStream_t caller = (hipStream_t)stream;
-	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
+	int N = 1;
+	bool collective = false;
+	if ((rc = devrank_dot_ranks(c, who, &N, &collective)) != BLZ_OK)
 		return rc;
-	HIPCHK(launch_dev_dot2(c->cfg, n, rows, x0, ldx0, x1, ldx1, y, ldy, c->devfuse_partial, out, c->stream));
-	return devio_leave(c, caller);
+	auto enqueue = [&]() -> int {
+		if (!c->devfuse_partial)
+			HIPCHK(hipMalloc((void **)&c->devfuse_partial, (size_t)dev_dot2_max_blocks(c->cfg, n) * 2 * n * n * sizeof(u64)));
+		int rc_ = collective ? devrank_dot_buffers(c) : BLZ_OK;
+		if (rc_ != BLZ_OK)
+			return rc_;
+		hipStream_t caller = (hipStream_t)stream;
+		if ((rc_ = devio_wait_caller(c, caller)) != BLZ_OK)
+			return rc_;
+		/* on ranks: both panels through one all-reduce of 2 n^2 words (blz_dot_device) */
+		HIPCHK(launch_dev_dot2(c->cfg, n, rows, x0, ldx0, x1, ldx1, y, ldy, c->devfuse_partial, collective ? c->devrank_send : out,
+				       c->stream));
+		if (collective && (rc_ = devrank_dot_finish(c, out, 2 * n * n)) != BLZ_OK)
+			return rc_;
+		return devio_leave(c, caller);
+	};
+	return collective ? devrank_collective_exit(c, enqueue()) : enqueue();
 }
 
 extern "C" int blz_combine_pair_device(blz_ctx *c, int64_t rows, int nterms, const uint64_t *const *x, const int64_t *ldx,
@@ -3675,6 +3859,9 @@ extern "C" int blz_rref_device(blz_ctx *c, int64_t rows, const uint64_t *x, int6
 	int rc = devsmall_begin(c, who, stream);
 	if (rc != BLZ_OK)
 		return rc;
+	if (c->device_ranks && (c->nranks > 1 || c->comm || c->loop || c->force_comm))
+		return blz_fail(BLZ_EINVAL, "%s: the echelon on ranks is not built (the row space of a block spread over ranks needs a "
+				"merge of the ranks' echelons); the call needs a plain single rank (DESIGN.md section 20)", who);
 	if (rows < 0)
 		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
 	const int n = c->un;
@@ -3700,4 +3887,53 @@ extern "C" int blz_rref_device(blz_ctx *c, int64_t rows, const uint64_t *x, int6
 		return rc;
 	HIPCHK(launch_dev_rref(c->cfg, n, rows, x, ldx, c->devsmall_stack, c->devsmall_ctl, e, z, (long long *)info, c->stream));
 	return devio_leave(c, caller);
+}
+
+/* ---- the bridges of device blocks on ranks: a whole block (blz_rows x n, the file's numbering) and the rank's own rows of it
+ * (blz_local_rows x n, slab order).  Row-local copies on the context's stream; nothing of a solve is read or written. ---- */
+
+static int devrank_bridge(blz_ctx *c, const char *who, int block, const uint64_t *whole, int64_t ldw, const uint64_t *local,
+			  int64_t ldl, void *stream, bool take)
+{
+	if (!c)
+		return blz_fail(BLZ_EINVAL, "%s: NULL context", who);
+	if (!c->device_ranks)
+		return blz_fail(BLZ_EINVAL, "%s: device blocks on ranks are not switched on (blz_set_device_ranks)", who);
+	int rc = devio_refuse_ranks(c, who);
+	if (rc != BLZ_OK)
+		return rc;
+	NEED_MATRIX(c);
+	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
+		return rc;
+	if (block < 0 || block > 3)
+		return blz_fail(BLZ_EINVAL, "%s: block %d is not one of V, TMP, AV, P", who, block);
+	const int sd = side_of(block);
+	size_t wb = 0, lb = 0;
+	if ((rc = devio_check_range(c, who, "global", whole, c->glob_rows[sd], ldw, &wb)) != BLZ_OK ||
+	    (rc = devio_check_range(c, who, "local", local, c->count[sd], ldl, &lb)) != BLZ_OK)
+		return rc;
+	if (wb && lb && devalg_overlap(whole, wb, local, lb))
+		return blz_fail(BLZ_EINVAL, "%s: local overlaps global", who);
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_enter(c, caller)) != BLZ_OK)
+		return rc;
+	if (take)
+		HIPCHK(launch_rows_take(c->cfg, const_cast<uint64_t *>(local), ldl, whole, ldw, c->inv_dev[sd], c->first[sd], c->count[sd],
+					c->un, c->stream));
+	else
+		HIPCHK(launch_rows_put(c->cfg, const_cast<uint64_t *>(whole), ldw, local, ldl, c->inv_dev[sd], c->first[sd], c->count[sd],
+				       c->un, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_take_local_device(blz_ctx *c, int block, const uint64_t *global, int64_t ldg, uint64_t *local, int64_t ldl,
+				     void *stream)
+{
+	return devrank_bridge(c, "blz_take_local_device", block, global, ldg, local, ldl, stream, true);
+}
+
+extern "C" int blz_put_local_device(blz_ctx *c, int block, const uint64_t *local, int64_t ldl, uint64_t *global, int64_t ldg,
+				    void *stream)
+{
+	return devrank_bridge(c, "blz_put_local_device", block, global, ldg, local, ldl, stream, false);
 }

@@ -887,11 +887,56 @@ class Context:
         import torch
         return torch.empty((rows, self.n), dtype=torch.uint64, device=f"cuda:{self.device}")
 
+    # ---- device blocks on ranks: with device_ranks() the blocks of every method below are the rank's own rows, in slab order
+
+    def device_ranks(self, on=True):
+        """blz_set_device_ranks(): device blocks are rank-local from here on (every rank of a job alike); returns self."""
+        check(lib().blz_set_device_ranks(self.h, C.c_int(1 if on else 0)))
+        return self
+
+    @property
+    def device_ranks_on(self):
+        return bool(lib().blz_device_ranks(self.h))
+
+    def _block_rows(self, block):
+        """rows of a device block of `block`: the rank's own with the mode on, all of them otherwise"""
+        return self.local_rows(block)[1] if self.device_ranks_on else self.rows(block)
+
+    def local_row_ids(self, block):
+        """blz_local_row_ids(): the original row number of every local row of `block`, int64 numpy (a host call)."""
+        ids = np.zeros(max(self.local_rows(block)[1], 0), dtype=np.int64)
+        check(lib().blz_local_row_ids(self.h, C.c_int(block), ids.ctypes.data_as(C.POINTER(C.c_int64))))
+        return ids
+
+    def take_local(self, block, whole, out=None, stream=None):
+        """blz_take_local_device(): out <- this rank's rows of `whole`, a (rows(block), n) tensor in the original numbering;
+        out is (local rows, n), a new torch.uint64 tensor when not given.  Not collective."""
+        rows = self.rows(block) if 0 <= block <= 3 else None
+        local = self.local_rows(block)[1] if 0 <= block <= 3 else None
+        pw, _, ldw, _ = device_block(whole, self.n, rows, self.device)
+        if out is None:
+            out = self._new_block(local if local is not None else 1)
+        pl, _, ldl, _ = device_block(out, self.n, local, self.device)
+        check(lib().blz_take_local_device(self.h, C.c_int(block), C.c_void_p(pw), C.c_int64(ldw), C.c_void_p(pl), C.c_int64(ldl),
+                                          C.c_void_p(self._stream(stream))))
+        return out
+
+    def put_local(self, block, local, whole, stream=None):
+        """blz_put_local_device(): this rank's rows of `whole` <- local; no other row of `whole` is touched.  Returns whole."""
+        rows = self.rows(block) if 0 <= block <= 3 else None
+        count = self.local_rows(block)[1] if 0 <= block <= 3 else None
+        pl, _, ldl, _ = device_block(local, self.n, count, self.device)
+        pw, _, ldw, _ = device_block(whole, self.n, rows, self.device)
+        check(lib().blz_put_local_device(self.h, C.c_int(block), C.c_void_p(pl), C.c_int64(ldl), C.c_void_p(pw), C.c_int64(ldw),
+                                         C.c_void_p(self._stream(stream))))
+        return whole
+
     def set_block_device(self, block, t, validate=False, stream=None):
         """blz_set_block_device(): block <- the tensor t, (rows(block), n) with strides (ld, 1) or flat, ordered on `stream`
         (default: torch's current stream) without a host synchronisation.  validate=True counts the words that are not
-        below p (synchronises) and returns the count, 0; a count that is not 0 raises BlzError(EINVAL) with it."""
-        rows = self.rows(block) if 0 <= block <= 3 else None
+        below p (synchronises) and returns the count, 0; a count that is not 0 raises BlzError(EINVAL) with it.
+        (With device_ranks() the tensor is the rank's own rows, here and in get_block_device.)"""
+        rows = self._block_rows(block) if 0 <= block <= 3 else None
         p, _, ld, _ = device_block(t, self.n, rows, self.device)
         bad = C.c_int64(-1)
         check(lib().blz_set_block_device(self.h, C.c_int(block), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream)),
@@ -900,7 +945,7 @@ class Context:
 
     def get_block_device(self, block, out=None, stream=None):
         """blz_get_block_device(): the block as a tensor on the device (out, or a new (rows, n) torch.uint64 one)."""
-        rows = self.rows(block) if 0 <= block <= 3 else None
+        rows = self._block_rows(block) if 0 <= block <= 3 else None
         if out is None:
             out = self._new_block(rows if rows is not None else 1)
         p, _, ld, _ = device_block(out, self.n, rows, self.device)

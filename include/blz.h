@@ -664,6 +664,55 @@ int blz_combine_pair_device(blz_ctx *ctx, int64_t rows, int nterms, const uint64
 			    const uint64_t *const *a0, const uint64_t *const *a1, uint64_t *z0, int64_t ldz0, uint64_t *z1,
 			    int64_t ldz1, void *stream);
 
+/* Device blocks on several ranks.  Everything above from blz_set_block_device on says "one rank only",
+ * and that stays the default.  blz_set_device_ranks(ctx, 1) opens the family to a context that holds one rank's share of the
+ * matrix: a block of the family is then RANK-LOCAL -- blz_local_rows(ctx, block, NULL) rows x n words of uint64_t, row stride
+ * ld >= n, local row q being row first + q of the solver's numbering, the order the rank's slab already has (on one rank: all
+ * rows, in the solver's numbering).  No rank needs memory for a whole block, and no call permutes a row.
+ *   blz_set_device_ranks  sticky; before or after the matrix and the communicator; accepted on any context, a plain single
+ *                         rank included; launches nothing.  Every rank of a job must set it alike: the caller's duty.  With the
+ *                         mode off every call is byte for byte what it was.  blz_device_ranks reads it back.
+ *   blz_local_row_ids     ids[q] = the ORIGINAL row number of local row q, blz_local_rows of them.  A host call, no GPU.  Over the
+ *                         ranks of a job the ids partition 0 .. blz_rows - 1, and blz_owner_of_row(ctx, block, ids[q]) is this
+ *                         rank.  (Needs a matrix, not the mode.)
+ *   blz_take_local_device local <- the rank's rows of `global`, a whole block: blz_rows x n words in the ORIGINAL numbering.
+ *   blz_put_local_device  the rank's rows of `global` <- local; no other row of `global` is touched.  Neither touches a word
+ *                         past n of any row, neither is collective; both need the mode on and a matrix; pointer checks, the
+ *                         two-event ordering on `stream` and the refusal of a capturing stream are those of
+ *                         blz_set_block_device; local and global must not overlap.  For tests, start vectors, assembling results.
+ * What the calls above mean with the mode on:
+ *   blz_set_block_device, blz_get_block_device   the rank's rows to and from its slab, identity order; `bad` counts this rank's
+ *                         words and is not collective.
+ *   blz_apply_rows        the LOCAL row counts of x and y.
+ *   blz_apply_device, blz_apply_pair_device      COLLECTIVE: every rank calls, with its own rows of x, y (and the intermediate).
+ *                         Import into the scratch slab, the product with the solver's own exchange in all its pieces, export of
+ *                         the rank's rows.  The bordered operator on a context set with blz_set_rhs_ranks; signed slabs as on
+ *                         one rank.
+ *   blz_dot_device, blz_dot_pair_device          COLLECTIVE: c = the sum over all ranks of X^T Y mod p, the same canonical words
+ *                         on every rank.  `rows` is each rank's own, may differ between ranks and may be 0.  No matrix is
+ *                         needed: the ranks are the communicator's.  The rank's residues go into a send buffer of the call's own,
+ *                         one all-reduce of n * n (2 * n * n) words, one kernel reduces the sums mod p into c.  nranks * p > 2^64
+ *                         is BLZ_EINVAL before anything is enqueued (blz_set_matrix's rule: the sum must not wrap).  On a
+ *                         context that is not exchanging -- a plain single rank -- there is no collective.
+ *   blz_combine_device, blz_combine_pair_device, blz_semi_inverse_device, blz_ortho_coeffs_device   allowed, unchanged, NOT
+ *                         collective: row-local or n x n; the coefficients agree across ranks because the dots do.
+ *   blz_rref_device       BLZ_EINVAL on anything but a plain single rank: the echelon on ranks is not built.
+ * Refused with the mode on, by name, before the first enqueue and before any rendezvous: external-exchange mode (and
+ * blz_set_exchange_mode(ctx, 1) afterwards), a product whose short-side form is active (blz_short_side), a capturing stream,
+ * and the strides, pointers and overlaps refused above.  Every one of these checks is a function of things all ranks share
+ * (the mode, the matrix' shape and partition, the communicator's size, p, the caller's strides being alike), so either all
+ * ranks pass or all refuse and nobody waits at a rendezvous alone.  An error past the checks inside a collective call marks a
+ * loopback group broken: its peers return BLZ_ECOMM at once.
+ * As before no call reads or writes V, TMP, AV, P, the small operands, the control words, the iteration count or the
+ * implicit-p state; the gathered operands are scratch that every product of an exchanging context refills.  A solve that runs
+ * between the calls is unaffected.  No run on more than one GPU exists for this (or any) part of the library: the ranks of
+ * its tests are loopback ranks on one device. */
+int blz_set_device_ranks(blz_ctx *ctx, int on);
+int blz_device_ranks(const blz_ctx *ctx);
+int blz_local_row_ids(const blz_ctx *ctx, int block, int64_t *ids);
+int blz_take_local_device(blz_ctx *ctx, int block, const uint64_t *global, int64_t ldg, uint64_t *local, int64_t ldl, void *stream);
+int blz_put_local_device(blz_ctx *ctx, int block, const uint64_t *local, int64_t ldl, uint64_t *global, int64_t ldg, void *stream);
+
 /* sparse_matrix_vector_product(y, M, x, transpose), sequential/lanczos_modp.c:266-287:
  * dst = M*src (transpose=0) or M^T*src (transpose=1), all n columns, canonical residues. */
 int blz_spmv(blz_ctx *ctx, int transpose, int src_block, int dst_block);
