@@ -39,6 +39,7 @@
 #include "blz_devsmall.h"
 #include "blz_devfuse.h"
 #include "blz_devrank.h"
+#include "blz_devw32.h"
 
 #define HIPCHK(expr)                                                                                     \
 	do {                                                                                             \
@@ -3936,4 +3937,344 @@ extern "C" int blz_put_local_device(blz_ctx *c, int block, const uint64_t *local
 				    void *stream)
 {
 	return devrank_bridge(c, "blz_put_local_device", block, global, ldg, local, ldl, stream, false);
+}
+
+/* ---- 32-bit device blocks: the family above on a caller's blocks of uint32_t words, for contexts of 4-byte words (p < 2^32;
+ * kernels: blz_devw32.hip).  Each call writes the words its 64-bit namesake writes, truncated; the n x n
+ * operands stay u64, the scratch is the namesake's (the apply slabs, devalg_partial, devfuse_partial), and the two families
+ * interleave freely on one context.  A plain single rank only: no device blocks on ranks, no echelon. ---- */
+
+static int w32_begin(blz_ctx *c, const char *who, void *stream, bool need_matrix)
+{
+	if (!c)
+		return blz_fail(BLZ_EINVAL, "%s: NULL context", who);
+	if (c->device_ranks)
+		return blz_fail(BLZ_EINVAL, "%s: 32-bit device blocks need a plain single rank, and device blocks on ranks are "
+				"switched on (blz_set_device_ranks)", who);
+	if (c->nranks > 1 || c->comm || c->loop || c->force_comm)
+		return blz_fail(BLZ_EINVAL, "%s: 32-bit device blocks need a single rank without a communicator, a loopback group or "
+				"BLZ_FORCE_COMM", who);
+	if (c->prime >= ((uint64_t)1 << 32) || c->cfg.word != 4)
+		return blz_fail(BLZ_EINVAL, "%s: p = %llu: residues do not fit 32-bit words (blz_word_bytes is %d)", who,
+				(unsigned long long)c->prime, c->cfg.word);
+	if (need_matrix && !c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "no matrix loaded (blz_set_matrix)");
+	HIPCHK(hipSetDevice(c->device));
+	return devio_refuse_capture(who, (hipStream_t)stream);
+}
+
+/* devio_check_range for a block of 4-byte words: [ptr, ptr + ((rows - 1) * ld + n) * 4) inside ONE allocation of the
+ * context's device, ptr aligned to 4 bytes, ld >= n, the byte offsets within 64 bits. */
+static int w32_check_range(const blz_ctx *c, const char *who, const char *arg, const void *ptr, int64_t rows, int64_t ld,
+			   size_t *bytes_out)
+{
+	const int n = c->un;
+	if (!ptr && rows != 0)
+		return blz_fail(BLZ_EINVAL, "%s: %s is NULL", who, arg);
+	if (ld < n)
+		return blz_fail(BLZ_EINVAL, "%s: the row stride of %s is %lld words, less than n = %d", who, arg, (long long)ld, n);
+	if (((uintptr_t)ptr & 3) != 0)
+		return blz_fail(BLZ_EINVAL, "%s: %s is not aligned to 4 bytes", who, arg);
+	if (rows < 0)
+		return blz_fail(BLZ_EINVAL, "%s: %s: %lld rows", who, arg, (long long)rows);
+	if (rows == 0) {
+		if (bytes_out)
+			*bytes_out = 0;
+		return BLZ_OK;
+	}
+	const unsigned __int128 wide = ((unsigned __int128)(rows - 1) * (unsigned __int128)ld + (unsigned __int128)n) * 4;
+	if (wide > ((unsigned __int128)1 << 62))
+		return blz_fail(BLZ_EINVAL, "%s: %s of %lld rows with a row stride of %lld words leaves 64-bit byte offsets", who, arg,
+				(long long)rows, (long long)ld);
+	const size_t bytes = (size_t)wide;
+	const int rc = devio_check_alloc(c, who, arg, ptr, bytes, rows, ld);
+	if (rc != BLZ_OK)
+		return rc;
+	if (bytes_out)
+		*bytes_out = bytes;
+	return BLZ_OK;
+}
+
+/* the two scratch slabs and the control words of blz_apply_device, shared with it */
+static int w32_apply_scratch(blz_ctx *c)
+{
+	for (int sd = 0; sd < 2; sd++)
+		if (!c->slab[APPLY_SLAB + sd]) {
+			const size_t bytes = (size_t)std::max<int64_t>(c->stride[sd], 1) * c->cfg.n * c->cfg.word;
+			HIPCHK(hipMalloc(&c->slab[APPLY_SLAB + sd], bytes));
+			HIPCHK(hipMemset(c->slab[APPLY_SLAB + sd], 0, bytes));
+			c->slab_bytes[APPLY_SLAB + sd] = bytes;
+		}
+	if (!c->apply_ctl) {
+		HIPCHK(hipMalloc((void **)&c->apply_ctl, sizeof(DevCtl)));
+		HIPCHK(hipMemset(c->apply_ctl, 0, sizeof(DevCtl)));
+	}
+	return BLZ_OK;
+}
+
+extern "C" int blz_set_block_device32(blz_ctx *c, int block, const uint32_t *dev, int64_t ld, void *stream, int64_t *bad)
+{
+	static const char who[] = "blz_set_block_device32";
+	int rc = w32_begin(c, who, stream, true);
+	if (rc != BLZ_OK)
+		return rc;
+	if (block < 0 || block > 3)
+		return blz_fail(BLZ_EINVAL, "%s: block %d is not one of V, TMP, AV, P", who, block);
+	const int sd = side_of(block);
+	if ((rc = w32_check_range(c, who, "dev", dev, c->glob_rows[sd], ld, nullptr)) != BLZ_OK)
+		return rc;
+	if (bad && !c->bad_dev)
+		HIPCHK(hipMalloc((void **)&c->bad_dev, sizeof(unsigned long long)));
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_enter(c, caller)) != BLZ_OK)
+		return rc;
+	if (block == BLZ_P) {	/* p is what the caller says from here on (as blz_set_block_device) */
+		HIPCHK(launch_identity_tail(c->small, c->cfg.n, c->stream));
+		c->p_implicit = false;
+	}
+	if (bad)
+		HIPCHK(hipMemsetAsync(c->bad_dev, 0, sizeof(unsigned long long), c->stream));
+	HIPCHK(launch_w32_import(c->cfg, c->slab[block], dev, ld, c->inv_dev[sd], c->count[sd], c->un, bad ? c->bad_dev : nullptr,
+				 c->stream));
+	if (c->gath_holds[sd] == block)
+		c->gath_holds[sd] = -1;
+	if ((rc = devio_leave(c, caller)) != BLZ_OK)
+		return rc;
+	if (bad) {
+		unsigned long long cnt = 0;
+		HIPCHK(hipStreamSynchronize(c->stream));
+		HIPCHK(hipMemcpy(&cnt, c->bad_dev, sizeof cnt, hipMemcpyDeviceToHost));
+		*bad = (int64_t)cnt;
+		if (cnt)
+			return blz_fail(BLZ_EINVAL, "%s: %llu words of the block are not residues below p", who, cnt);
+	}
+	return BLZ_OK;
+}
+
+extern "C" int blz_get_block_device32(blz_ctx *c, int block, uint32_t *dev, int64_t ld, void *stream)
+{
+	static const char who[] = "blz_get_block_device32";
+	int rc = w32_begin(c, who, stream, true);
+	if (rc != BLZ_OK)
+		return rc;
+	if (block < 0 || block > 3)
+		return blz_fail(BLZ_EINVAL, "%s: block %d is not one of V, TMP, AV, P", who, block);
+	const int sd = side_of(block);
+	if ((rc = w32_check_range(c, who, "dev", dev, c->glob_rows[sd], ld, nullptr)) != BLZ_OK)
+		return rc;
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_enter(c, caller)) != BLZ_OK)
+		return rc;
+	if (block == BLZ_P && c->p_implicit) {	/* materialize_p, on the stream (as blz_get_block_device) */
+		const int np = c->cfg.n;
+		HIPCHK(launch_block_mul(c->cfg, c->slab[BLZ_P], c->count[0], np, np, c->small + small_E(np), c->stream));
+		HIPCHK(launch_identity_tail(c->small, np, c->stream));
+		c->p_implicit = false;
+	}
+	HIPCHK(launch_w32_export(c->cfg, dev, ld, c->slab[block], c->inv_dev[sd], c->count[sd], c->un, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_apply_device32(blz_ctx *c, int transpose, const uint32_t *x, int64_t ldx, uint32_t *y, int64_t ldy, void *stream)
+{
+	static const char who[] = "blz_apply_device32";
+	int rc = w32_begin(c, who, stream, true);
+	if (rc != BLZ_OK)
+		return rc;
+	const int t = transpose ? 1 : 0, ys = c->row_side[t], xs = 1 - ys;
+	size_t xb = 0, yb = 0;
+	if ((rc = w32_check_range(c, who, "x", x, c->glob_rows[xs], ldx, &xb)) != BLZ_OK ||
+	    (rc = w32_check_range(c, who, "y", y, c->glob_rows[ys], ldy, &yb)) != BLZ_OK)
+		return rc;
+	if (devalg_overlap(x, xb, y, yb))
+		return blz_fail(BLZ_EINVAL, "%s: x and y overlap", who);
+	if ((rc = w32_apply_scratch(c)) != BLZ_OK)
+		return rc;
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_enter(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_w32_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, c->inv_dev[xs], c->count[xs], c->un, nullptr, c->stream));
+	if ((rc = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_w32_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], c->inv_dev[ys], c->count[ys], c->un, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_apply_pair_device32(blz_ctx *c, int transpose_first, const uint32_t *x, int64_t ldx, uint32_t *y, int64_t ldy,
+				       uint32_t *z, int64_t ldz, void *stream)
+{
+	static const char who[] = "blz_apply_pair_device32";
+	int rc = w32_begin(c, who, stream, true);
+	if (rc != BLZ_OK)
+		return rc;
+	const int t = transpose_first ? 1 : 0, ys = c->row_side[t], xs = 1 - ys;
+	size_t xb = 0, yb = 0, zb = 0;
+	if ((rc = w32_check_range(c, who, "x", x, c->glob_rows[xs], ldx, &xb)) != BLZ_OK ||
+	    (y && (rc = w32_check_range(c, who, "y", y, c->glob_rows[ys], ldy, &yb)) != BLZ_OK) ||
+	    (rc = w32_check_range(c, who, "z", z, c->glob_rows[xs], ldz, &zb)) != BLZ_OK)
+		return rc;
+	const bool in_place = (const uint32_t *)z == x && ldz == ldx;
+	if (!in_place && devalg_overlap(z, zb, x, xb))
+		return blz_fail(BLZ_EINVAL, "%s: z overlaps x without being it (the in-place form is the same pointer and the same "
+				"stride)", who);
+	if (y && devalg_overlap(y, yb, x, xb))
+		return blz_fail(BLZ_EINVAL, "%s: y overlaps x", who);
+	if (y && devalg_overlap(y, yb, z, zb))
+		return blz_fail(BLZ_EINVAL, "%s: y overlaps z", who);
+	if ((rc = w32_apply_scratch(c)) != BLZ_OK)
+		return rc;
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_enter(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_w32_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, c->inv_dev[xs], c->count[xs], c->un, nullptr, c->stream));
+	if ((rc = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
+		return rc;
+	if (y)	/* the intermediate is wanted: one pass more; otherwise it lives in its slab only */
+		HIPCHK(launch_w32_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], c->inv_dev[ys], c->count[ys], c->un, c->stream));
+	/* back into the slab x was imported to: the first product has consumed it (so z may be x) */
+	if ((rc = enqueue_product(c, 1 - t, APPLY_SLAB + ys, APPLY_SLAB + xs, false, nullptr, c->apply_ctl)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_w32_export(c->cfg, z, ldz, c->slab[APPLY_SLAB + xs], c->inv_dev[xs], c->count[xs], c->un, c->stream));
+	return devio_leave(c, caller);
+}
+
+/* the inner products of both arities: nx = 1 writes n * n words, nx = 2 two contiguous panels */
+static int w32_dot(blz_ctx *c, const char *who, int64_t rows, int nx, const uint32_t *const *x, const int64_t *ldx,
+		   const uint32_t *y, int64_t ldy, uint64_t *out, void *stream)
+{
+	int rc = w32_begin(c, who, stream, false);
+	if (rc != BLZ_OK)
+		return rc;
+	if (rows < 0)
+		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
+	const int n = c->un;
+	static const char *const xname[2][2] = { { "x", "" }, { "x0", "x1" } };
+	size_t xb[2] = { 0, 0 }, yb = 0, cb = 0;
+	long long ldl[2] = { 0, 0 };
+	for (int k = 0; k < nx; k++) {
+		if ((rc = w32_check_range(c, who, xname[nx - 1][k], x[k], rows, ldx[k], &xb[k])) != BLZ_OK)
+			return rc;
+		ldl[k] = ldx[k];
+	}
+	if ((rc = w32_check_range(c, who, "y", y, rows, ldy, &yb)) != BLZ_OK ||
+	    (rc = devio_check_words(c, who, "c", out, (int64_t)nx * n * n, &cb)) != BLZ_OK)
+		return rc;
+	for (int k = 0; k < nx; k++)
+		if (devalg_overlap(out, cb, x[k], xb[k]))
+			return blz_fail(BLZ_EINVAL, "%s: c overlaps %s", who, xname[nx - 1][k]);
+	if (devalg_overlap(out, cb, y, yb))
+		return blz_fail(BLZ_EINVAL, "%s: c overlaps y", who);
+	u64 **partial = nx == 1 ? &c->devalg_partial : &c->devfuse_partial;
+	if (!*partial)	/* the namesake's scratch, of the namesake's size */
+		HIPCHK(hipMalloc((void **)partial, nx == 1 ? (size_t)dev_dot_max_blocks(c->cfg, n) * n * n * sizeof(u64)
+							   : (size_t)dev_dot2_max_blocks(c->cfg, n) * 2 * n * n * sizeof(u64)));
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_w32_dot(c->cfg, n, rows, nx, x, ldl, y, ldy, *partial, out, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_dot_device32(blz_ctx *c, int64_t rows, const uint32_t *x, int64_t ldx, const uint32_t *y, int64_t ldy,
+				uint64_t *out, void *stream)
+{
+	return w32_dot(c, "blz_dot_device32", rows, 1, &x, &ldx, y, ldy, out, stream);
+}
+
+extern "C" int blz_dot_pair_device32(blz_ctx *c, int64_t rows, const uint32_t *x0, int64_t ldx0, const uint32_t *x1, int64_t ldx1,
+				     const uint32_t *y, int64_t ldy, uint64_t *out, void *stream)
+{
+	const uint32_t *x[2] = { x0, x1 };
+	const int64_t ldx[2] = { ldx0, ldx1 };
+	return w32_dot(c, "blz_dot_pair_device32", rows, 2, x, ldx, y, ldy, out, stream);
+}
+
+/* the recombinations of both arities: nz = 1 has a0 and z0 only */
+static int w32_combine(blz_ctx *c, const char *who, int64_t rows, int nterms, const uint32_t *const *x, const int64_t *ldx, int nz,
+		       const uint64_t *const *a0, const uint64_t *const *a1, uint32_t *z0, int64_t ldz0, uint32_t *z1, int64_t ldz1,
+		       void *stream)
+{
+	int rc = w32_begin(c, who, stream, false);
+	if (rc != BLZ_OK)
+		return rc;
+	if (nterms < 1 || nterms > BLZ_MAX_TERMS)
+		return blz_fail(BLZ_EINVAL, "%s: nterms = %d is outside 1..%d", who, nterms, BLZ_MAX_TERMS);
+	if (rows < 0)
+		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
+	if (!x || !ldx || !a0 || (nz == 2 && !a1))
+		return blz_fail(BLZ_EINVAL, "%s: the array of %s is NULL", who, !x ? "x" : !ldx ? "ldx" : !a0 ? (nz == 2 ? "a0" : "a") : "a1");
+	const uint64_t *const *a[2] = { a0, a1 };
+	uint32_t *z[2] = { z0, z1 };
+	const int64_t ldz[2] = { ldz0, ldz1 };
+	if (nz == 2) {
+		int in[2] = { 0, 0 };
+		for (int t = 0; t < nterms; t++) {
+			if (!a0[t] && !a1[t])
+				return blz_fail(BLZ_EINVAL, "%s: term %d enters neither output (a0[%d] and a1[%d] are both NULL)", who, t, t, t);
+			in[0] += a0[t] != nullptr;
+			in[1] += a1[t] != nullptr;
+		}
+		for (int o = 0; o < 2; o++)
+			if (!in[o])
+				return blz_fail(BLZ_EINVAL, "%s: output z%d has no term (every a%d[t] is NULL)", who, o, o);
+	}
+	const int n = c->un;
+	size_t xb[BLZ_MAX_TERMS] = { 0 }, ab[2][BLZ_MAX_TERMS] = { { 0 } }, zb[2] = { 0, 0 };
+	long long ldl[BLZ_MAX_TERMS] = { 0 };
+	char nm[12], zn[4];
+	for (int t = 0; t < nterms; t++) {
+		snprintf(nm, sizeof nm, "x[%d]", t);
+		if ((rc = w32_check_range(c, who, nm, x[t], rows, ldx[t], &xb[t])) != BLZ_OK)
+			return rc;
+		for (int o = 0; o < nz; o++) {
+			if (nz == 2)
+				snprintf(nm, sizeof nm, "a%d[%d]", o, t);
+			else
+				snprintf(nm, sizeof nm, "a[%d]", t);
+			if (nz == 1 && !a[o][t])
+				return blz_fail(BLZ_EINVAL, "%s: %s is NULL", who, nm);
+			if (a[o][t] && (rc = devio_check_range(c, who, nm, a[o][t], n, n, &ab[o][t])) != BLZ_OK)
+				return rc;
+		}
+		ldl[t] = ldx[t];
+	}
+	for (int o = 0; o < nz; o++) {
+		snprintf(zn, sizeof zn, nz == 2 ? "z%d" : "z", o);
+		if ((rc = w32_check_range(c, who, zn, z[o], rows, ldz[o], &zb[o])) != BLZ_OK)
+			return rc;
+	}
+	if (nz == 2 && rows > 0 && devalg_overlap(z0, zb[0], z1, zb[1]))
+		return blz_fail(BLZ_EINVAL, "%s: z0 overlaps z1", who);
+	for (int o = 0; o < nz; o++) {
+		snprintf(zn, sizeof zn, nz == 2 ? "z%d" : "z", o);
+		for (int t = 0; t < nterms; t++) {
+			const bool in_place = x[t] == z[o] && ldx[t] == ldz[o];
+			if (!in_place && devalg_overlap(z[o], zb[o], x[t], xb[t]))
+				return blz_fail(BLZ_EINVAL, "%s: %s overlaps x[%d] without being it (the in-place form is the same pointer "
+						"and the same stride)", who, zn, t);
+			for (int q = 0; q < nz; q++)
+				if (a[q][t] && devalg_overlap(z[o], zb[o], a[q][t], ab[q][t]))
+					return blz_fail(BLZ_EINVAL, "%s: %s overlaps a coefficient of term %d", who, zn, t);
+		}
+	}
+	if (rows == 0)
+		return BLZ_OK;	/* the outputs have no words */
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
+		return rc;
+	HIPCHK(launch_w32_combine(c->cfg, n, rows, nterms, x, ldl, nz, a0, a1, z0, ldz0, z1, ldz1, c->stream));
+	return devio_leave(c, caller);
+}
+
+extern "C" int blz_combine_device32(blz_ctx *c, int64_t rows, int nterms, const uint32_t *const *x, const int64_t *ldx,
+				    const uint64_t *const *a, uint32_t *z, int64_t ldz, void *stream)
+{
+	return w32_combine(c, "blz_combine_device32", rows, nterms, x, ldx, 1, a, nullptr, z, ldz, nullptr, 0, stream);
+}
+
+extern "C" int blz_combine_pair_device32(blz_ctx *c, int64_t rows, int nterms, const uint32_t *const *x, const int64_t *ldx,
+					 const uint64_t *const *a0, const uint64_t *const *a1, uint32_t *z0, int64_t ldz0, uint32_t *z1,
+					 int64_t ldz1, void *stream)
+{
+	return w32_combine(c, "blz_combine_pair_device32", rows, nterms, x, ldx, 2, a0, a1, z0, ldz0, z1, ldz1, stream);
 }

@@ -112,8 +112,22 @@ def device_block(t, n, rows=None, device=None):
     stride(), dtype and device, which is all this looks at: torch is not imported here.  Two layouts: 2-D (rows, n) with
     strides (ld, 1), ld >= n, or 1-D contiguous with rows * n elements.  rows / device, when given, are what the caller
     expects (the block's row count, the context's device index).  Anything else is a ValueError that names the fault."""
-    if str(t.dtype) not in DEVICE_DTYPES:
-        raise ValueError(f"device block: dtype {t.dtype} is not one of {', '.join(DEVICE_DTYPES)}")
+    return _device_block(t, n, rows, device, DEVICE_DTYPES)
+
+
+DEVICE_DTYPES32 = ("torch.uint32", "torch.int32")   # the same 32 bits either way: a residue >= 2**31 is not negative
+
+
+def device_block32(t, n, rows=None, device=None):
+    """device_block() for a block of 32-bit words (the ...32 methods of Context, p < 2**32): the same two layouts and the same
+    faults, the dtype one of DEVICE_DTYPES32 and ld counted in 32-bit words."""
+    return _device_block(t, n, rows, device, DEVICE_DTYPES32)
+
+
+def _device_block(t, n, rows, device, dtypes):
+    """what device_block() and device_block32() share: everything but the dtypes they accept"""
+    if str(t.dtype) not in dtypes:
+        raise ValueError(f"device block: dtype {t.dtype} is not one of {', '.join(dtypes)}")
     if getattr(t.device, "type", None) != "cuda":
         raise ValueError(f"device block: the tensor lives on {t.device}, not on a GPU")
     index = t.device.index if t.device.index is not None else 0
@@ -200,7 +214,7 @@ def device_info(t, n, device=None):
     return device_words(t, (n + 1,), ("torch.int64",), device, "info")
 
 
-def device_terms(terms, n, device=None):
+def device_terms(terms, n, device=None, block=None):
     """(rows, [(pointer of X, ld of X, pointer of A), ...]) of the 1..MAX_TERMS pairs (X, A) of Context.combine: every X goes
     through device_block, every A through device_square; the rows are the first block's and all blocks must agree."""
     terms = list(terms)
@@ -211,7 +225,7 @@ def device_terms(terms, n, device=None):
         if len(pair) != 2:
             raise ValueError(f"combine: term {k} is not a pair (X, A)")
         try:
-            px, rows, ldx, _ = device_block(pair[0], n, rows, device)
+            px, rows, ldx, _ = (block or device_block)(pair[0], n, rows, device)
             pa = device_square(pair[1], n, device)
         except ValueError as e:
             raise ValueError(f"combine: term {k}: {e}") from None
@@ -224,7 +238,7 @@ def device_pair(t, n, device=None):
     return device_words(t, (2, n, n), DEVICE_DTYPES, device, "inner product pair")
 
 
-def device_pair_terms(terms, n, device=None):
+def device_pair_terms(terms, n, device=None, block=None):
     """(rows, [(pointer of X, ld of X, pointer of A0 or None, pointer of A1 or None), ...]) of the 1..MAX_TERMS triples
     (X, A0, A1) of Context.combine_pair: every X goes through device_block, every coefficient that is not None through
     device_square; all blocks agree in their rows, every term enters an output and every output has a term."""
@@ -238,7 +252,7 @@ def device_pair_terms(terms, n, device=None):
         if triple[1] is None and triple[2] is None:
             raise ValueError(f"combine_pair: term {k} enters neither output (A0 and A1 are both None)")
         try:
-            px, rows, ldx, _ = device_block(triple[0], n, rows, device)
+            px, rows, ldx, _ = (block or device_block)(triple[0], n, rows, device)
             pa = [None if a is None else device_square(a, n, device) for a in triple[1:]]
         except ValueError as e:
             raise ValueError(f"combine_pair: term {k}: {e}") from None
@@ -249,14 +263,14 @@ def device_pair_terms(terms, n, device=None):
     return rows, out
 
 
-def device_pair_out(out, n, rows, device=None):
+def device_pair_out(out, n, rows, device=None, block=None):
     """[(pointer, ld), (pointer, ld)] of the two outputs (z0, z1) of Context.combine_pair: blocks of `rows` rows each"""
     if not isinstance(out, (tuple, list)) or len(out) != 2:
         raise ValueError("combine_pair: out is not a pair (z0, z1)")
     res = []
     for o, z in enumerate(out):
         try:
-            pz, _, ldz, _ = device_block(z, n, rows, device)
+            pz, _, ldz, _ = (block or device_block)(z, n, rows, device)
         except ValueError as e:
             raise ValueError(f"combine_pair: output z{o}: {e}") from None
         res.append((pz, ldz))
@@ -1079,6 +1093,125 @@ class Context:
         c1 = (C.c_void_p * k)(*[a[3] for a in args])
         check(lib().blz_combine_pair_device(self.h, C.c_int64(rows), C.c_int(k), xs, lds, c0, c1, C.c_void_p(pz0),
                                             C.c_int64(ldz0), C.c_void_p(pz1), C.c_int64(ldz1), C.c_void_p(self._stream(stream))))
+        return out[0], out[1]
+
+    # ---- 32-bit device blocks: the methods above on torch.uint32 / torch.int32 tensors, for contexts with word_bytes == 4
+    # (p < 2**32).  A block the wrapper allocates takes the dtype of the first block passed in (torch.uint32 where there is
+    # none); the n x n results are torch.uint64 and the coefficients are what combine() takes, so ortho_coeffs() and
+    # semi_inverse_device() serve both families.
+
+    def _new_block32(self, rows, like=None):
+        import torch
+        return torch.empty((rows, self.n), dtype=like.dtype if like is not None else torch.uint32, device=f"cuda:{self.device}")
+
+    def set_block_device32(self, block, t, validate=False, stream=None):
+        """blz_set_block_device32(): set_block_device() from a tensor of 32-bit words."""
+        rows = self.rows(block) if 0 <= block <= 3 else None
+        p, _, ld, _ = device_block32(t, self.n, rows, self.device)
+        bad = C.c_int64(-1)
+        check(lib().blz_set_block_device32(self.h, C.c_int(block), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream)),
+                                           C.byref(bad) if validate else None))
+        return int(bad.value) if validate else None
+
+    def get_block_device32(self, block, out=None, stream=None):
+        """blz_get_block_device32(): the block as a tensor of 32-bit words (out, or a new (rows, n) torch.uint32 one)."""
+        rows = self.rows(block) if 0 <= block <= 3 else None
+        if out is None:
+            out = self._new_block32(rows if rows is not None else 1)
+        p, _, ld, _ = device_block32(out, self.n, rows, self.device)
+        check(lib().blz_get_block_device32(self.h, C.c_int(block), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream))))
+        return out
+
+    def apply32(self, transpose, x, out=None, stream=None):
+        """blz_apply_device32(): apply() on tensors of 32-bit words.  Returns out (a new tensor of x's dtype when not given)."""
+        xr, yr = self.apply_rows(transpose)
+        px, _, ldx, _ = device_block32(x, self.n, xr, self.device)
+        if out is None:
+            out = self._new_block32(yr, x)
+        py, _, ldy, _ = device_block32(out, self.n, yr, self.device)
+        check(lib().blz_apply_device32(self.h, C.c_int(int(bool(transpose))), C.c_void_p(px), C.c_int64(ldx), C.c_void_p(py),
+                                       C.c_int64(ldy), C.c_void_p(self._stream(stream))))
+        return out
+
+    def apply_pair32(self, transpose_first, x, out=None, mid=None, stream=None):
+        """blz_apply_pair_device32(): apply_pair() on tensors of 32-bit words; out, mid and the return as there."""
+        xr, yr = self.apply_rows(transpose_first)
+        px, _, ldx, _ = device_block32(x, self.n, xr, self.device)
+        if out is None:
+            out = self._new_block32(xr, x)
+        pz, _, ldz, _ = device_block32(out, self.n, xr, self.device)
+        if mid is True:
+            mid = self._new_block32(yr, x)
+        py, ldy = None, 0
+        if mid is not None:
+            py, _, ldy, _ = device_block32(mid, self.n, yr, self.device)
+        check(lib().blz_apply_pair_device32(self.h, C.c_int(int(bool(transpose_first))), C.c_void_p(px), C.c_int64(ldx),
+                                            C.c_void_p(py), C.c_int64(ldy), C.c_void_p(pz), C.c_int64(ldz),
+                                            C.c_void_p(self._stream(stream))))
+        return out if mid is None else (out, mid)
+
+    def dot32(self, x, y, out=None, stream=None):
+        """blz_dot_device32(): dot() of two blocks of 32-bit words; out is (n, n) torch.uint64, as there."""
+        px, rows, ldx, _ = device_block32(x, self.n, None, self.device)
+        py, _, ldy, _ = device_block32(y, self.n, rows, self.device)
+        if out is None:
+            out = self._empty((self.n, self.n))
+        pc = device_square(out, self.n, self.device)
+        check(lib().blz_dot_device32(self.h, C.c_int64(rows), C.c_void_p(px), C.c_int64(ldx), C.c_void_p(py), C.c_int64(ldy),
+                                     C.c_void_p(pc), C.c_void_p(self._stream(stream))))
+        return out
+
+    def dot_pair32(self, x0, x1, y, out=None, stream=None):
+        """blz_dot_pair_device32(): dot_pair() of blocks of 32-bit words; out is (2, n, n) torch.uint64, as there."""
+        px0, rows, ldx0, _ = device_block32(x0, self.n, None, self.device)
+        px1, _, ldx1, _ = device_block32(x1, self.n, rows, self.device)
+        py, _, ldy, _ = device_block32(y, self.n, rows, self.device)
+        if out is None:
+            out = self._empty((2, self.n, self.n))
+        pc = device_pair(out, self.n, self.device)
+        check(lib().blz_dot_pair_device32(self.h, C.c_int64(rows), C.c_void_p(px0), C.c_int64(ldx0), C.c_void_p(px1),
+                                          C.c_int64(ldx1), C.c_void_p(py), C.c_int64(ldy), C.c_void_p(pc),
+                                          C.c_void_p(self._stream(stream))))
+        return out
+
+    def combine32(self, terms, out=None, stream=None):
+        """blz_combine_device32(): combine() on blocks of 32-bit words.  The coefficients are what combine() takes ((n, n)
+        uint64 / int64 tensors, numpy arrays, nested lists); out: a new block of the first X's dtype, the caller's, or one
+        of the X (the in-place form)."""
+        terms = list(terms)
+        if not 1 <= len(terms) <= MAX_TERMS:
+            raise ValueError(f"combine: {len(terms)} terms, not 1..{MAX_TERMS}")
+        terms = [(pair[0], self._coefficient(pair[1], stream)) for pair in terms]
+        rows, args = device_terms(terms, self.n, self.device, device_block32)
+        if out is None:
+            out = self._new_block32(rows, terms[0][0])
+        pz, _, ldz, _ = device_block32(out, self.n, rows, self.device)
+        k = len(args)
+        xs = (C.c_void_p * k)(*[a[0] for a in args])
+        lds = (C.c_int64 * k)(*[a[1] for a in args])
+        cs = (C.c_void_p * k)(*[a[2] for a in args])
+        check(lib().blz_combine_device32(self.h, C.c_int64(rows), C.c_int(k), xs, lds, cs, C.c_void_p(pz), C.c_int64(ldz),
+                                         C.c_void_p(self._stream(stream))))
+        return out
+
+    def combine_pair32(self, terms, out=None, stream=None):
+        """blz_combine_pair_device32(): combine_pair() on blocks of 32-bit words; terms, out and the return as there."""
+        terms = [tuple(t) for t in terms]
+        if not 1 <= len(terms) <= MAX_TERMS:
+            raise ValueError(f"combine_pair: {len(terms)} terms, not 1..{MAX_TERMS}")
+        terms = [t if len(t) != 3 else (t[0],) + tuple(None if a is None else self._coefficient(a, stream) for a in t[1:])
+                 for t in terms]
+        rows, args = device_pair_terms(terms, self.n, self.device, device_block32)
+        if out is None:
+            out = (self._new_block32(rows, terms[0][0]), self._new_block32(rows, terms[0][0]))
+        (pz0, ldz0), (pz1, ldz1) = device_pair_out(out, self.n, rows, self.device, device_block32)
+        k = len(args)
+        xs = (C.c_void_p * k)(*[a[0] for a in args])
+        lds = (C.c_int64 * k)(*[a[1] for a in args])
+        c0 = (C.c_void_p * k)(*[a[2] for a in args])
+        c1 = (C.c_void_p * k)(*[a[3] for a in args])
+        check(lib().blz_combine_pair_device32(self.h, C.c_int64(rows), C.c_int(k), xs, lds, c0, c1, C.c_void_p(pz0),
+                                              C.c_int64(ldz0), C.c_void_p(pz1), C.c_int64(ldz1), C.c_void_p(self._stream(stream))))
         return out[0], out[1]
 
     # ---- device small algebra: the n x n chain of a Krylov step and the echelon form of a block, results on the device

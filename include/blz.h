@@ -713,6 +713,45 @@ int blz_local_row_ids(const blz_ctx *ctx, int block, int64_t *ids);
 int blz_take_local_device(blz_ctx *ctx, int block, const uint64_t *global, int64_t ldg, uint64_t *local, int64_t ldl, void *stream);
 int blz_put_local_device(blz_ctx *ctx, int block, const uint64_t *local, int64_t ldl, uint64_t *global, int64_t ldg, void *stream);
 
+/* 32-bit device blocks: the same family on a caller's blocks of uint32_t words, valid exactly on
+ * contexts with blz_word_bytes(ctx) == 4, i.e. p < 2^32 -- the reference's whole domain, and the width the solver's own slabs
+ * have there.  Nothing above changes; the calls of the two families interleave freely on one context.
+ *
+ *   blocks        rows x n words of uint32_t, every ld counted in 32-bit words, ld >= n; words n .. ld-1 of a row are never
+ *                 read or written.  A word is an UNSIGNED 32-bit residue: one that is >= 2^31 (common at p = 2^32 - 5) is not
+ *                 negative, whatever the dtype of the tensor that holds it.  Pointers are aligned to 4 bytes; 8- and 16-byte
+ *                 lane accesses are used where the pointer, the stride and n all allow them.
+ *   c, a[t]       the n x n operands stay contiguous uint64_t words in device memory -- the results of blz_dot_device32 /
+ *                 blz_dot_pair_device32, the coefficients of blz_combine_device32 / blz_combine_pair_device32 -- so
+ *                 blz_ortho_coeffs_device and blz_semi_inverse_device serve both families unchanged.
+ *   contract      each call writes exactly the words its 64-bit namesake writes when given the same residues zero-extended,
+ *                 truncated to 32 bits.  Ordering on `stream`, the in-place forms, the overlaps refused, a NULL y of the
+ *                 paired product, NULL coefficients of the paired recombination and rows == 0 are the namesake's.  `bad` of
+ *                 blz_set_block_device32 counts the words >= p.
+ *   scratch       the namesakes': the two slabs of blz_apply_device (blz_apply_release frees them) and the partial sums of
+ *                 blz_dot_device / blz_dot_pair_device.  No buffer is added to a context.
+ *   BLZ_EINVAL    on the host, before anything is enqueued, naming the argument: a context with p >= 2^32 ("residues do not fit
+ *                 32-bit words"); a block pointer that is not aligned to 4 bytes; ld < n; a host pointer, or a range
+ *                 ((rows - 1) * ld + n) * 4 bytes that does not lie inside one allocation of the context's device; a byte offset
+ *                 that leaves 64 bits; the overlaps the namesakes refuse; a capturing stream; anything but a plain single rank
+ *                 -- a communicator, a loopback group, BLZ_FORCE_COMM, or blz_set_device_ranks on.
+ *   not built     there is no blz_rref_device32 and no blz_take_local_device32 / blz_put_local_device32: the echelon form
+ *                 and device blocks on ranks take uint64_t blocks only. */
+int blz_set_block_device32(blz_ctx *ctx, int block, const uint32_t *dev, int64_t ld, void *stream, int64_t *bad);
+int blz_get_block_device32(blz_ctx *ctx, int block, uint32_t *dev, int64_t ld, void *stream);
+int blz_apply_device32(blz_ctx *ctx, int transpose, const uint32_t *x, int64_t ldx, uint32_t *y, int64_t ldy, void *stream);
+int blz_apply_pair_device32(blz_ctx *ctx, int transpose_first, const uint32_t *x, int64_t ldx, uint32_t *y, int64_t ldy,
+			    uint32_t *z, int64_t ldz, void *stream);
+int blz_dot_device32(blz_ctx *ctx, int64_t rows, const uint32_t *x, int64_t ldx, const uint32_t *y, int64_t ldy, uint64_t *c,
+		     void *stream);
+int blz_dot_pair_device32(blz_ctx *ctx, int64_t rows, const uint32_t *x0, int64_t ldx0, const uint32_t *x1, int64_t ldx1,
+			  const uint32_t *y, int64_t ldy, uint64_t *c, void *stream);
+int blz_combine_device32(blz_ctx *ctx, int64_t rows, int nterms, const uint32_t *const *x, const int64_t *ldx,
+			 const uint64_t *const *a, uint32_t *z, int64_t ldz, void *stream);
+int blz_combine_pair_device32(blz_ctx *ctx, int64_t rows, int nterms, const uint32_t *const *x, const int64_t *ldx,
+			      const uint64_t *const *a0, const uint64_t *const *a1, uint32_t *z0, int64_t ldz0, uint32_t *z1,
+			      int64_t ldz1, void *stream);
+
 /* sparse_matrix_vector_product(y, M, x, transpose), sequential/lanczos_modp.c:266-287:
  * dst = M*src (transpose=0) or M^T*src (transpose=1), all n columns, canonical residues. */
 int blz_spmv(blz_ctx *ctx, int transpose, int src_block, int dst_block);
