@@ -21,6 +21,7 @@
 #include <unistd.h>
 #include <rccl/rccl.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -40,6 +41,7 @@
 #include "blz_devfuse.h"
 #include "blz_devrank.h"
 #include "blz_devw32.h"
+#include "blz_devmat.h"
 
 #define HIPCHK(expr)                                                                                     \
 	do {                                                                                             \
@@ -282,6 +284,8 @@ struct blz_ctx {
 	 * their all-reduce lands; both this family's own (never dot_send / dot_recv), allocated on first use */
 	bool device_ranks = false;
 	u64 *devrank_send = nullptr, *devrank_recv = nullptr;
+	/* the resident matrix was built on the device (blz_set_matrix_device / blz_set_matrix_upload) */
+	bool device_built = false;
 };
 
 enum { APPLY_SLAB = 4 };
@@ -626,6 +630,8 @@ extern "C" int blz_values_wide(const blz_ctx *c) { return c && c->values_wide ? 
 
 extern "C" int blz_values_signed(const blz_ctx *c) { return c && c->values_signed ? 1 : 0; }
 
+static int plan_csr(blz_ctx *c, const u32 *row_ptr, DevCsr &D, int64_t hot_rows, bool dot_slab);
+
 /* hi0: wide value mode, the high limbs of H0.val (host) */
 static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows = 0, bool dot_slab = false, double locality = 1.0,
 		      const u32 *hi0 = nullptr)
@@ -725,6 +731,15 @@ static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows
 			}
 		}
 	}
+	return plan_csr(c, H.row_ptr, D, hot_rows, dot_slab);
+}
+
+/* The plan of a slab whose arrays are in place (rows, cols, nnz, val, palette, wide, locality set), from a host copy of its
+ * row pointers: the outlier lists, the spread of the rows the streaming kernel keeps, the staged and the panel plan.  Shared
+ * by the host upload above and the device build (devmat_build). */
+static int plan_csr(blz_ctx *c, const u32 *row_ptr, DevCsr &D, int64_t hot_rows, bool dot_slab)
+{
+	struct { int64_t rows, nnz; const u32 *row_ptr; } H = { D.rows, D.nnz, row_ptr };
 	D.heavy_thr = spmv_heavy_threshold(c->cfg, H.rows, H.nnz);
 	std::vector<HeavySeg> heavy;
 	std::vector<HeavyRow> multi;
@@ -855,6 +870,97 @@ extern "C" uint64_t blz_prepare_key(const blz_ctx *c, uint64_t content_hash, int
 	return h ? h : 1;
 }
 
+/* What every matrix-setting call drops of the matrix before it: the captured iteration, the scratch of the device blocks,
+ * the border.  (The host path and the device build share this and matrix_blocks below.) */
+static void matrix_reset(blz_ctx *c, int right, int rank, int nranks)
+{
+	if (c->iter_graph) {
+		hipGraphExecDestroy(c->iter_graph);
+		c->iter_graph = nullptr;
+	}
+	devio_release_matrix(c);	/* the scratch slabs and the device copy of the numbering belong to the matrix they were made for */
+	c->right = right;
+	c->rank = rank;
+	c->nranks = nranks;
+	c->fuse_local_off = false;
+	if (c->rhs) {		/* a border belongs to the matrix it was set for */
+		hipFree(c->rhs);
+		c->rhs = nullptr;
+	}
+	c->border = -1;
+	c->rhs_k = c->rhs_kp = 0;
+	c->border_rows.clear();
+	c->rhs_ranks = false;
+	c->border_own.clear();
+}
+
+/* The last step of every matrix-setting call, once csr[] and stride[] are what the new matrix wants: the four blocks
+ * (zeroed), the gathered operands, the piece events, the control words and the explicit-p state. */
+static int matrix_blocks(blz_ctx *c, int nranks, int K)
+{
+	/* One rank: every block can hold either side (the reference sizes all four for the larger one, :597-605, and
+	 * blz_spmv takes any pair of blocks).  Several ranks: a block lives on ONE side (side_of), and a rank's slab of the
+	 * long side of a tall matrix is many times its slab of the short one (relat9 shape at N = 8: 1.5 M rows against
+	 * 69 k) -- each block is sized by its own side (round 2 gave all four the larger: 23 x what V, AV and P need there). */
+	for (int b = 0; b < 4; b++) {
+		const int64_t rows = nranks == 1 ? std::max(c->stride[0], c->stride[1]) : c->stride[side_of(b)];
+		const size_t bytes = (size_t)std::max<int64_t>(rows, 1) * c->cfg.n * c->cfg.word;
+		if (c->slab[b])
+			hipFree(c->slab[b]);
+		c->slab[b] = nullptr;
+		HIPCHK(hipMalloc(&c->slab[b], bytes));
+		HIPCHK(hipMemset(c->slab[b], 0, bytes));		/* sequential/lanczos_modp.c:617-622 */
+		c->slab_bytes[b] = bytes;
+	}
+	for (int sd = 0; sd < 2; sd++) {
+		if (c->gath[sd])
+			hipFree(c->gath[sd]);
+		c->gath[sd] = nullptr;
+		c->gath_holds[sd] = -1;
+		/* side sd is gathered by the product whose rows live on the other side; in its short-side form nothing is */
+		const int t_gath = c->row_side[0] == 1 - sd ? 0 : 1;
+		if (nranks > 1 && !c->short_side[t_gath]) {
+			const size_t gb = (size_t)std::max<int64_t>(c->stride[sd], 1) * nranks * c->cfg.n * c->cfg.word;
+			HIPCHK(hipMalloc(&c->gath[sd], gb));
+			HIPCHK(hipMemset(c->gath[sd], 0, gb));
+		}
+	}
+	while ((int)c->ev_piece.size() < K) {
+		hipEvent_t e;
+		HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+		c->ev_piece.push_back(e);
+	}
+	HIPCHK(hipMemset(c->ctl, 0, sizeof(DevCtl)));
+	c->host_ctl = DevCtl{};
+	{
+		int rc_ = explicit_p_state(c);		/* p = 0 as it stands */
+		if (rc_ != BLZ_OK)
+			return rc_;
+	}
+	c->have_matrix = true;
+	return BLZ_OK;
+}
+
+/* One rank, the product in one piece: what follows the upload of slab t = csr[t][0] (row_ptr: its row pointers on the host) */
+static void slab_whole_choices(blz_ctx *c, int t, const u32 *row_ptr, int64_t cols, bool dot_slab, int nranks, bool uploaded)
+{
+	/* Gathers that mostly hit (a banded / well-ordered matrix: the locality rule of spmv_plan_staged): the product
+	 * is paced by the kernel, and there the staged form with 16-byte lanes plus the inner products as their own
+	 * matrix-core kernel beat the fused lane-per-column form -- band matrix, 2 M x 2 M, n = 8: 308 + 55 us against
+	 * 389 (profiles/r03_band_switches.txt).  Where the fabric paces the gathers the fused form stays (the inner
+	 * products ride along for 20 us). */
+	DevCsr &D = c->csr[t][0];
+	if (uploaded && dot_slab && nranks == 1 && !D.wide && block_dot_mfma_supported(c->cfg) && D.panel_rows == 0 &&
+	    D.locality < 0.3 && !D.uneven && D.outlier_share < 0.02) {
+		spmv_plan_staged(c->cfg, row_ptr, D, true);
+		c->fuse_local_off = D.st_ok;
+	}
+	const char *xe = getenv("BLZ_XCD_RANGES");	/* 0 / 1 force it off / on (A/B) */
+	/* (an operand of a few MB sits in every L2 anyway: nothing to separate) */
+	const bool big = (double)cols * c->cfg.n * c->cfg.word > 8e6;
+	c->csr[t][0].xcd_ranges = xe ? xe[0] == '1' : (c->locality[t] < 0.6 && big);
+}
+
 /* allow_short_side = false: plan no short-side product (a bordered context: the border rows of the operand are not
  * gathered in that form) */
 static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool allow_short_side)
@@ -879,24 +985,8 @@ static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool
 		return blz_fail(BLZ_EINVAL, "blz_set_matrix_prepared: rank %d of %d, but the context is rank %d of %d in its loopback communicator",
 				rank, nranks, c->loop_rank, c->loop->nranks);
 	HIPCHK(hipSetDevice(c->device));
-	if (c->iter_graph) {
-		hipGraphExecDestroy(c->iter_graph);
-		c->iter_graph = nullptr;
-	}
-	devio_release_matrix(c);	/* the scratch slabs and the device copy of the numbering belong to the matrix they were made for */
-	c->right = right;
-	c->rank = rank;
-	c->nranks = nranks;
-	c->fuse_local_off = false;
-	if (c->rhs) {		/* a border belongs to the matrix it was set for */
-		hipFree(c->rhs);
-		c->rhs = nullptr;
-	}
-	c->border = -1;
-	c->rhs_k = c->rhs_kp = 0;
-	c->border_rows.clear();
-	c->rhs_ranks = false;
-	c->border_own.clear();
+	matrix_reset(c, right, rank, nranks);
+	c->device_built = false;
 	/* side 0 = rows of v: rows of M for a left kernel, columns of M for a right kernel
 	 * (sequential/lanczos_modp.c:592-593). */
 	c->glob_rows[0] = right ? P->ncols : P->nrows;
@@ -973,23 +1063,7 @@ static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool
 			const int64_t hot_t = c->cfg.panel ? P->hot[t == 0 ? 1 : 0] : 0;
 			rc = upload_csr(c, slab, c->csr[t][0], hot_t, dot_slab, nranks == 1 ? c->locality[t] : 1.0,
 					whole ? P->val_hi[t] : nullptr);
-			{
-				/* Gathers that mostly hit (a banded / well-ordered matrix: the locality rule of spmv_plan_staged): the product
-				 * is paced by the kernel, and there the staged form with 16-byte lanes plus the inner products as their own
-				 * matrix-core kernel beat the fused lane-per-column form -- band matrix, 2 M x 2 M, n = 8: 308 + 55 us against
-				 * 389 (profiles/r03_band_switches.txt).  Where the fabric paces the gathers the fused form stays (the inner
-				 * products ride along for 20 us). */
-				DevCsr &D = c->csr[t][0];
-				if (rc == BLZ_OK && dot_slab && nranks == 1 && !D.wide && block_dot_mfma_supported(c->cfg) && D.panel_rows == 0 &&
-				    D.locality < 0.3 && !D.uneven && D.outlier_share < 0.02) {
-					spmv_plan_staged(c->cfg, slab.row_ptr, D, true);
-					c->fuse_local_off = D.st_ok;
-				}
-			}
-			const char *xe = getenv("BLZ_XCD_RANGES");	/* 0 / 1 force it off / on (A/B) */
-			/* (an operand of a few MB sits in every L2 anyway: nothing to separate) */
-			const bool big = (double)slab.cols * c->cfg.n * c->cfg.word > 8e6;
-			c->csr[t][0].xcd_ranges = xe ? xe[0] == '1' : (c->locality[t] < 0.6 && big);
+			slab_whole_choices(c, t, slab.row_ptr, slab.cols, dot_slab, nranks, rc == BLZ_OK);
 		} else {
 			/* columns are positions in the gathered operand of the opposite side: piece k = [k*w, (k+1)*w) */
 			const int csd = 1 - c->row_side[t];
@@ -1021,47 +1095,7 @@ static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool
 		HIPCHK(hipMalloc(&c->rs_recv, rs_need));
 		c->rs_bytes = rs_need;
 	}
-	/* One rank: every block can hold either side (the reference sizes all four for the larger one, :597-605, and
-	 * blz_spmv takes any pair of blocks).  Several ranks: a block lives on ONE side (side_of), and a rank's slab of the
-	 * long side of a tall matrix is many times its slab of the short one (relat9 shape at N = 8: 1.5 M rows against
-	 * 69 k) -- each block is sized by its own side (round 2 gave all four the larger: 23 x what V, AV and P need there). */
-	for (int b = 0; b < 4; b++) {
-		const int64_t rows = nranks == 1 ? std::max(c->stride[0], c->stride[1]) : c->stride[side_of(b)];
-		const size_t bytes = (size_t)std::max<int64_t>(rows, 1) * c->cfg.n * c->cfg.word;
-		if (c->slab[b])
-			hipFree(c->slab[b]);
-		c->slab[b] = nullptr;
-		HIPCHK(hipMalloc(&c->slab[b], bytes));
-		HIPCHK(hipMemset(c->slab[b], 0, bytes));		/* sequential/lanczos_modp.c:617-622 */
-		c->slab_bytes[b] = bytes;
-	}
-	for (int sd = 0; sd < 2; sd++) {
-		if (c->gath[sd])
-			hipFree(c->gath[sd]);
-		c->gath[sd] = nullptr;
-		c->gath_holds[sd] = -1;
-		/* side sd is gathered by the product whose rows live on the other side; in its short-side form nothing is */
-		const int t_gath = c->row_side[0] == 1 - sd ? 0 : 1;
-		if (nranks > 1 && !c->short_side[t_gath]) {
-			const size_t gb = (size_t)std::max<int64_t>(c->stride[sd], 1) * nranks * c->cfg.n * c->cfg.word;
-			HIPCHK(hipMalloc(&c->gath[sd], gb));
-			HIPCHK(hipMemset(c->gath[sd], 0, gb));
-		}
-	}
-	while ((int)c->ev_piece.size() < K) {
-		hipEvent_t e;
-		HIPCHK(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-		c->ev_piece.push_back(e);
-	}
-	HIPCHK(hipMemset(c->ctl, 0, sizeof(DevCtl)));
-	c->host_ctl = DevCtl{};
-	{
-		int rc_ = explicit_p_state(c);		/* p = 0 as it stands */
-		if (rc_ != BLZ_OK)
-			return rc_;
-	}
-	c->have_matrix = true;
-	return BLZ_OK;
+	return matrix_blocks(c, nranks, K);
 }
 
 extern "C" int blz_set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank)
@@ -3349,6 +3383,329 @@ static int devio_leave(blz_ctx *c, hipStream_t caller)
 	HIPCHK(hipStreamWaitEvent(caller, c->ev_ours, 0));
 	return BLZ_OK;
 }
+
+/* ---- device matrix: M from triplets on the GPU, both CSRs built there (kernels: blz_devmat.hip) ---- */
+
+/* device memory of one build: whatever is still listed when the build leaves, by whichever exit, is freed */
+struct DevmatTmp {
+	std::vector<void *> ptrs;
+	~DevmatTmp()
+	{
+		for (void *p : ptrs)
+			hipFree(p);
+	}
+	hipError_t alloc(void **p, size_t bytes)
+	{
+		const hipError_t e = hipMalloc(p, bytes ? bytes : 1);
+		if (e == hipSuccess)
+			ptrs.push_back(*p);
+		return e;
+	}
+	void keep(void *p)	/* it belongs to the context from here on */
+	{
+		for (auto &q : ptrs)
+			if (q == p) {
+				q = ptrs.back();
+				ptrs.pop_back();
+				return;
+			}
+	}
+};
+
+/* BLZ_DEVMAT_TRACE=1: HIP events around the kernels of a build, one line on stderr (tools/device_matrix_cost.py reads it) */
+struct DevmatTrace {
+	enum { COUNT0 = 0, COUNT1, SCAN1, SCATTER0, SCATTER1, PALETTE1, PACK1, MARKS };
+	bool on = false;
+	hipStream_t st = nullptr;
+	hipEvent_t ev[MARKS] = {};
+	bool set[MARKS] = {};
+	explicit DevmatTrace(hipStream_t s) : st(s)
+	{
+		const char *e = getenv("BLZ_DEVMAT_TRACE");
+		on = e && e[0] == '1';
+	}
+	void mark(int k)
+	{
+		if (on && !set[k] && hipEventCreate(&ev[k]) == hipSuccess) {
+			(void)hipEventRecord(ev[k], st);
+			set[k] = true;
+		}
+	}
+	float ms(int a, int b)
+	{
+		float t = 0.0f;
+		if (!set[a] || !set[b] || hipEventElapsedTime(&t, ev[a], ev[b]) != hipSuccess)
+			return 0.0f;
+		return t;
+	}
+	~DevmatTrace()
+	{
+		if (on && set[SCATTER1] && hipStreamSynchronize(st) == hipSuccess)
+			fprintf(stderr, "blz device build: check+count %.3f ms, scan %.3f ms, scatter %.3f ms, palette %.3f ms, pack %.3f ms\n",
+				ms(COUNT0, COUNT1), ms(COUNT1, SCAN1), ms(SCATTER0, SCATTER1), ms(SCATTER1, PALETTE1), ms(PALETTE1, PACK1));
+		for (int k = 0; k < MARKS; k++)
+			if (set[k])
+				hipEventDestroy(ev[k]);
+	}
+};
+
+/* everything that is refused before a byte moves: the arguments and the state of the context (pointers: devmat_refuse_ptr) */
+static int devmat_refuse(const blz_ctx *c, const char *who, int64_t nrows, int64_t ncols, int64_t nnz, int idx_bytes, const void *x,
+			 int val_bytes)
+{
+	if (!c)
+		return blz_fail(BLZ_EINVAL, "%s: NULL context", who);
+	if (idx_bytes != 4 && idx_bytes != 8)
+		return blz_fail(BLZ_EINVAL, "%s: idx_bytes = %d is neither 4 (int32) nor 8 (int64)", who, idx_bytes);
+	if (val_bytes != 0 && val_bytes != 4 && val_bytes != 8)
+		return blz_fail(BLZ_EINVAL, "%s: val_bytes = %d is not 0 (all ones), 4 (uint32) or 8 (uint64)", who, val_bytes);
+	if ((val_bytes == 0 && x) || (val_bytes != 0 && !x && nnz > 0))	/* (no entries: no element is read, any pointer will do) */
+		return blz_fail(BLZ_EINVAL, "%s: x and val_bytes disagree (val_bytes = %d with x %s NULL)", who, val_bytes, x ? "not" : "=");
+	if (nrows < 0 || ncols < 0 || nrows >= ((int64_t)1 << 31) || ncols >= ((int64_t)1 << 31))
+		return blz_fail(BLZ_EINVAL, "%s: nrows = %lld, ncols = %lld: both must lie in [0, 2^31)", who, (long long)nrows, (long long)ncols);
+	if (nnz < 0 || nnz >= (int64_t)UINT32_MAX)
+		return blz_fail(BLZ_EINVAL, "%s: nnz = %lld must lie in [0, 2^32 - 1)", who, (long long)nnz);
+	if (c->values_signed)
+		return blz_fail(BLZ_EINVAL, "%s: the context is in signed value mode; the device build takes residues below p", who);
+	if (c->wide_hi)
+		return blz_fail(BLZ_EINVAL, "%s: high limbs are pending (blz_set_values_wide); the device build takes wide entries as "
+				"8-byte values", who);
+	if ((c->have_matrix && c->nranks > 1) || c->comm || c->loop || c->force_comm)
+		return blz_fail(BLZ_EINVAL, "%s: the device build needs a single rank without a communicator, a loopback group or "
+				"BLZ_FORCE_COMM (see DESIGN.md section 22)", who);
+	return BLZ_OK;
+}
+
+static int devmat_refuse_ptr(const blz_ctx *c, const char *who, const char *arg, const void *ptr, int64_t count, int elem)
+{
+	if (count == 0)
+		return BLZ_OK;		/* no element is read: any pointer will do */
+	if (!ptr)
+		return blz_fail(BLZ_EINVAL, "%s: %s is NULL", who, arg);
+	if (((uintptr_t)ptr & (uintptr_t)(elem - 1)) != 0)
+		return blz_fail(BLZ_EINVAL, "%s: %s is not aligned to its %d-byte elements", who, arg, elem);
+	return devio_check_alloc(c, who, arg, ptr, (size_t)count * (size_t)elem, count, 1);
+}
+
+/* The build itself.  i, j, x have passed devmat_refuse_ptr (or are the library's own copies).  Until the counts of the check
+ * pass and the two row_ptr arrays have been read the context is untouched; from there on a failure leaves it without a matrix. */
+static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
+			int idx_bytes, const void *x, int val_bytes, int right)
+{
+	DevmatTmp tmp;
+	hipStream_t st = c->stream;
+	DevmatTrace trace(st);
+	const int64_t rows_t[2] = { nrows, ncols };	/* rows of CSR(M), of CSR(M^T) */
+	u32 *rp[2] = { nullptr, nullptr };
+	unsigned long long *counts = nullptr;
+	for (int t = 0; t < 2; t++) {
+		HIPCHK(tmp.alloc((void **)&rp[t], (size_t)(rows_t[t] + 1) * sizeof(u32)));
+		HIPCHK(hipMemsetAsync(rp[t], 0, (size_t)(rows_t[t] + 1) * sizeof(u32), st));
+	}
+	HIPCHK(tmp.alloc((void **)&counts, DEVMAT_COUNTS * sizeof(unsigned long long)));
+	HIPCHK(hipMemsetAsync(counts, 0, DEVMAT_COUNTS * sizeof(unsigned long long), st));
+	trace.mark(DevmatTrace::COUNT0);
+	HIPCHK(launch_devmat_count(c->cfg, idx_bytes, val_bytes, i, j, x, nnz, nrows, ncols, rp[0], rp[1], counts, st));
+	trace.mark(DevmatTrace::COUNT1);
+	unsigned long long hc[DEVMAT_COUNTS];
+	HIPCHK(hipStreamSynchronize(st));
+	HIPCHK(hipMemcpy(hc, counts, sizeof hc, hipMemcpyDeviceToHost));
+	if (hc[DEVMAT_BAD_ROW] || hc[DEVMAT_BAD_COL] || hc[DEVMAT_BAD_VAL])
+		return blz_fail(BLZ_EINVAL, "%s: %llu row indices outside [0, %lld), %llu column indices outside [0, %lld), %llu values "
+				"not below p (of %lld entries)", who, hc[DEVMAT_BAD_ROW], (long long)nrows, hc[DEVMAT_BAD_COL],
+				(long long)ncols, hc[DEVMAT_BAD_VAL], (long long)nnz);
+	u32 *sums = nullptr;
+	HIPCHK(tmp.alloc((void **)&sums, (size_t)devmat_scan_tiles(std::max(nrows, ncols) + 1) * sizeof(u32)));
+	std::vector<u32> hrp[2];
+	for (int t = 0; t < 2; t++) {
+		HIPCHK(launch_devmat_scan(rp[t], rows_t[t] + 1, sums, st));
+		hrp[t].resize((size_t)rows_t[t] + 1);
+	}
+	trace.mark(DevmatTrace::SCAN1);
+	HIPCHK(hipStreamSynchronize(st));
+	for (int t = 0; t < 2; t++) {
+		HIPCHK(hipMemcpy(hrp[t].data(), rp[t], hrp[t].size() * sizeof(u32), hipMemcpyDeviceToHost));
+		if (hrp[t][0] != 0 || (int64_t)hrp[t][(size_t)rows_t[t]] != nnz)
+			return blz_fail(BLZ_EHIP, "%s: the scan of the %s counts ends at %u, not at nnz = %lld", who, t ? "column" : "row",
+					hrp[t][(size_t)rows_t[t]], (long long)nnz);
+	}
+	/* the choices the host path makes from the values (csr_from_coo_window, upload_csr) */
+	const bool pattern = val_bytes == 0 || hc[DEVMAT_NOT_ONE] == 0;
+	const bool wide = !pattern && hc[DEVMAT_HIGH] != 0 && c->cfg.word == 8;
+	if (wide)
+		for (int t = 0; t < 2; t++)
+			for (int64_t r = 0; r < rows_t[t]; r++)
+				if (hrp[t][(size_t)r + 1] - hrp[t][(size_t)r] > (1u << 30))
+					return blz_fail(BLZ_EINVAL, "a row of a wide slab has more than 2^30 entries: its unreduced sum is not "
+							"bounded (csrc/modp.h)");
+
+	/* ---- the matrix that was resident goes; the context is that of BLZ_NO_REORDER=1 after blz_set_matrix(M, right, 0, 1) ---- */
+	matrix_reset(c, right ? 1 : 0, 0, 1);
+	c->have_matrix = false;
+	c->device_built = false;
+	c->values_wide = wide;
+	c->glob_rows[0] = right ? ncols : nrows;
+	c->glob_rows[1] = right ? nrows : ncols;
+	c->row_side[0] = right ? 1 : 0;
+	c->row_side[1] = right ? 0 : 1;
+	for (int sd = 0; sd < 2; sd++) {
+		c->perm[sd].clear();
+		c->inv[sd].clear();
+		c->bounds[sd].assign({ (int64_t)0, c->glob_rows[sd] });
+		c->stride[sd] = c->glob_rows[sd];
+		c->first[sd] = 0;
+		c->count[sd] = c->glob_rows[sd];
+	}
+	c->hot_share[0] = c->hot_share[1] = 0.0;
+	c->locality[0] = c->locality[1] = 1.0;
+	c->order_kind = 0;
+	for (int t = 0; t < 2; t++) {
+		for (auto &A : c->csr[t])
+			free_csr(A);
+		c->csr[t].assign((size_t)1, DevCsr{});
+		free_csr(c->csr_short[t]);
+		c->short_side[t] = false;
+	}
+	u32 *cur[2] = { nullptr, nullptr };
+	for (int t = 0; t < 2; t++) {
+		DevCsr &D = c->csr[t][0];
+		D.rows = rows_t[t];
+		D.cols = rows_t[1 - t];
+		D.nnz = nnz;
+		D.wide = wide;
+		D.locality = 1.0;
+		D.row_ptr = rp[t];
+		tmp.keep(rp[t]);
+		HIPCHK(hipMalloc(&D.col_idx, (size_t)(nnz + BLZ_STREAM_PAD) * sizeof(int)));
+		HIPCHK(hipMemsetAsync(D.col_idx + nnz, 0, BLZ_STREAM_PAD * sizeof(int), st));
+		if (!pattern) {
+			HIPCHK(hipMalloc(&D.val, (size_t)(nnz + BLZ_STREAM_PAD) * sizeof(u32)));
+			HIPCHK(hipMemsetAsync(D.val + nnz, 0, BLZ_STREAM_PAD * sizeof(u32), st));
+			if (wide) {
+				HIPCHK(hipMalloc(&D.val_hi, (size_t)(nnz + BLZ_STREAM_PAD) * sizeof(u32)));
+				HIPCHK(hipMemsetAsync(D.val_hi + nnz, 0, BLZ_STREAM_PAD * sizeof(u32), st));
+			}
+		}
+		/* the cursors: a transient copy of the row pointers */
+		HIPCHK(tmp.alloc((void **)&cur[t], (size_t)std::max<int64_t>(rows_t[t], 1) * sizeof(u32)));
+		HIPCHK(hipMemcpyAsync(cur[t], rp[t], (size_t)rows_t[t] * sizeof(u32), hipMemcpyDeviceToDevice, st));
+	}
+	{
+		DevCsr &A = c->csr[0][0], &B = c->csr[1][0];
+		trace.mark(DevmatTrace::SCATTER0);
+		HIPCHK(launch_devmat_scatter(c->cfg, idx_bytes, val_bytes, i, j, x, nnz, nrows, ncols, cur[0], cur[1], A.col_idx, A.val,
+					     A.val_hi, B.col_idx, B.val, B.val_hi, st));
+		trace.mark(DevmatTrace::SCATTER1);
+	}
+	/* Packed stream, by upload_csr's rule: at most 256 distinct values and fewer than 2^24 columns, unless BLZ_NO_PACK.  Both
+	 * slabs hold the same values: one palette, made from CSR(M), ascending, serves both. */
+	bool packable[2];
+	for (int t = 0; t < 2; t++)
+		packable[t] = !pattern && c->pack && c->csr[t][0].cols < (1 << 24);
+	if (packable[0] || packable[1]) {
+		unsigned long long *table = nullptr, *keys = nullptr;
+		unsigned int *pcount = nullptr, hcount = 0;
+		HIPCHK(tmp.alloc((void **)&table, DEVMAT_PAL_SLOTS * sizeof(unsigned long long)));
+		HIPCHK(tmp.alloc((void **)&keys, DEVMAT_PAL_MAX * sizeof(unsigned long long)));
+		HIPCHK(tmp.alloc((void **)&pcount, sizeof(unsigned int)));
+		HIPCHK(hipMemsetAsync(table, 0xFF, DEVMAT_PAL_SLOTS * sizeof(unsigned long long), st));
+		HIPCHK(hipMemsetAsync(pcount, 0, sizeof(unsigned int), st));
+		HIPCHK(launch_devmat_palette(c->cfg, c->csr[0][0].val, c->csr[0][0].val_hi, nnz, table, pcount, keys, st));
+		trace.mark(DevmatTrace::PALETTE1);
+		HIPCHK(hipStreamSynchronize(st));
+		HIPCHK(hipMemcpy(&hcount, pcount, sizeof hcount, hipMemcpyDeviceToHost));
+		if (hcount >= 1 && hcount <= DEVMAT_PAL_MAX) {
+			std::vector<unsigned long long> hk((size_t)hcount);
+			HIPCHK(hipMemcpy(hk.data(), keys, hk.size() * sizeof(unsigned long long), hipMemcpyDeviceToHost));
+			std::sort(hk.begin(), hk.end());
+			HIPCHK(hipMemcpy(keys, hk.data(), hk.size() * sizeof(unsigned long long), hipMemcpyHostToDevice));
+			std::vector<u32> pal((size_t)(wide ? 512 : 256), 0u);	/* (wide: 256 low limbs, then 256 high limbs) */
+			for (size_t q = 0; q < hk.size(); q++) {
+				pal[q] = (u32)hk[q];
+				if (wide)
+					pal[256 + q] = (u32)(hk[q] >> 32);
+			}
+			for (int t = 0; t < 2; t++) {
+				if (!packable[t])
+					continue;
+				DevCsr &D = c->csr[t][0];
+				HIPCHK(hipMalloc(&D.palette, pal.size() * sizeof(u32)));
+				HIPCHK(hipMemcpy(D.palette, pal.data(), pal.size() * sizeof(u32), hipMemcpyHostToDevice));
+				HIPCHK(launch_devmat_pack(c->cfg, D.col_idx, D.val, D.val_hi, nnz, keys, (int)hcount, st));
+			}
+			trace.mark(DevmatTrace::PACK1);
+			HIPCHK(hipStreamSynchronize(st));
+			for (int t = 0; t < 2; t++) {
+				if (!packable[t])
+					continue;
+				DevCsr &D = c->csr[t][0];	/* the value arrays of a packed slab were transient */
+				hipFree(D.val);
+				D.val = nullptr;
+				if (D.val_hi)
+					hipFree(D.val_hi);
+				D.val_hi = nullptr;
+			}
+		}
+	}
+	HIPCHK(hipStreamSynchronize(st));
+	for (int t = 0; t < 2; t++) {
+		/* product `right` is the second one of the iteration: its launch carries the inner products where that form exists */
+		const bool dot_slab = t == (right ? 1 : 0) && c->fuse_dot && spmv_dot_supported(c->cfg);
+		const int rc = plan_csr(c, hrp[t].data(), c->csr[t][0], 0, dot_slab);
+		if (rc != BLZ_OK)
+			return rc;
+		slab_whole_choices(c, t, hrp[t].data(), c->csr[t][0].cols, dot_slab, 1, true);
+	}
+	const int rc = matrix_blocks(c, 1, 1);
+	c->device_built = rc == BLZ_OK;
+	return rc;
+}
+
+extern "C" int blz_set_matrix_device(blz_ctx *c, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
+				     int idx_bytes, const void *x, int val_bytes, int right, void *stream)
+{
+	const char *who = "blz_set_matrix_device";
+	int rc = devmat_refuse(c, who, nrows, ncols, nnz, idx_bytes, x, val_bytes);
+	if (rc != BLZ_OK)
+		return rc;
+	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
+		return rc;
+	HIPCHK(hipSetDevice(c->device));
+	if ((rc = devmat_refuse_ptr(c, who, "i", i, nnz, idx_bytes)) != BLZ_OK ||
+	    (rc = devmat_refuse_ptr(c, who, "j", j, nnz, idx_bytes)) != BLZ_OK ||
+	    (val_bytes && (rc = devmat_refuse_ptr(c, who, "x", x, nnz, val_bytes)) != BLZ_OK))
+		return rc;
+	if ((rc = devio_wait_caller(c, (hipStream_t)stream)) != BLZ_OK)
+		return rc;
+	return devmat_build(c, who, nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right);
+}
+
+extern "C" int blz_set_matrix_upload(blz_ctx *c, const blz_coo *M, int right)
+{
+	const char *who = "blz_set_matrix_upload";
+	if (!c || !M)
+		return blz_fail(BLZ_EINVAL, "%s: NULL argument", who);
+	if (M->nnz >= (int64_t)UINT32_MAX)
+		return blz_fail(BLZ_EINVAL, "%s: nnz >= 2^32 per slab is not supported", who);
+	if (M->nnz > 0 && (!M->i || !M->j || !M->x))
+		return blz_fail(BLZ_EINVAL, "%s: the triplets of M are NULL", who);
+	int rc = devmat_refuse(c, who, M->nrows, M->ncols, M->nnz, 4, M->x, 4);
+	if (rc != BLZ_OK)
+		return rc;
+	HIPCHK(hipSetDevice(c->device));
+	DevmatTmp tmp;		/* the triplets on the device, for the length of the call */
+	void *dev[3] = { nullptr, nullptr, nullptr };
+	const void *host[3] = { M->i, M->j, M->x };
+	const size_t bytes = (size_t)M->nnz * 4;
+	for (int q = 0; q < 3; q++) {
+		HIPCHK(tmp.alloc(&dev[q], bytes));
+		if (bytes)
+			HIPCHK(hipMemcpy(dev[q], host[q], bytes, hipMemcpyHostToDevice));
+	}
+	return devmat_build(c, who, M->nrows, M->ncols, M->nnz, dev[0], dev[1], 4, dev[2], 4, right);
+}
+
+extern "C" int blz_matrix_device_built(const blz_ctx *c) { return c && c->have_matrix && c->device_built ? 1 : 0; }
 
 extern "C" int blz_set_block_device(blz_ctx *c, int block, const uint64_t *dev, int64_t ld, void *stream, int64_t *bad)
 {

@@ -29,7 +29,7 @@
 static long n = 1;
 static uint64_t prime;
 static char *matrix_filename, *kernel_filename, *rhs_filename;
-static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis, rhs_gpus_given, values_signed, values_wide;
+static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis, rhs_gpus_given, values_signed, values_wide, device_build;
 static int stop_after = -1, checkpoint_timer = 60, device, gpus = 1, rhs_gpus;
 
 static double wtime(void)
@@ -90,6 +90,10 @@ static void usage(char **argv)
 	printf("                            mod P, so every element of F_P can be an entry (-1 is P-1, P is 0).  One GPU only: not\n");
 	printf("                            with --cache, --gpus above 1, --rhs-gpus or --signed.  Check the result with\n");
 	printf("                            checker_modp --wide.  Like --signed, the mode is NOT recorded in a checkpoint\n");
+	printf("--device-build              build CSR(M) and CSR(M^T) on the GPU from the file's triplets (blz_set_matrix_upload): no\n");
+	printf("                            host renumbering and no host CSR build; the file's numbering is kept, the output is\n");
+	printf("                            the same, byte for byte.  One GPU only: not with --gpus above 1, --rhs, --rhs-gpus,\n");
+	printf("                            --cache, --signed or --wide\n");
 	printf("--device D                  first HIP device to run on [default 0]\n");
 	printf("--gpus G                    row-partition the matrix over G GPUs of this node (devices D..D+G-1), RCCL\n");
 	printf("                            all-gather of the block before each product [default 1]\n");
@@ -100,6 +104,7 @@ static void usage(char **argv)
 	printf("The --rhs argument excludes --stop-after and --gpus above 1, and --basis (the solution is taken from the\n");
 	printf("kernel basis of the bordered matrix, which --rhs computes itself; it is one vector per system, not a kernel block)\n");
 	printf("The --rhs-gpus argument needs --rhs and excludes --gpus above 1\n");
+	printf("The --device-build argument excludes --gpus above 1, --rhs, --rhs-gpus, --cache, --signed and --wide\n");
 	exit(0);
 }
 
@@ -114,7 +119,7 @@ static void process_command_line_options(int argc, char **argv)
 		{"gpus", required_argument, NULL, 'g'}, {"verify", no_argument, NULL, 'V'},
 		{"cache", no_argument, NULL, 'C'}, {"basis", no_argument, NULL, 'B'}, {"rhs", required_argument, NULL, 'R'},
 		{"rhs-gpus", required_argument, NULL, 'G'}, {"signed", no_argument, NULL, 'S'},
-		{"wide", no_argument, NULL, 'W'},
+		{"wide", no_argument, NULL, 'W'}, {"device-build", no_argument, NULL, 'D'},
 		{"help", no_argument, NULL, 'h'}, {NULL, 0, NULL, 0}
 	};
 	int ch;
@@ -144,6 +149,7 @@ static void process_command_line_options(int argc, char **argv)
 		case 'G': rhs_gpus = atoi(optarg); rhs_gpus_given = true; break;
 		case 'S': values_signed = true; break;
 		case 'W': values_wide = true; break;
+		case 'D': device_build = true; break;
 		case 'h': usage(argv); break;
 		default: errx(1, "Unknown option\n");
 		}
@@ -159,6 +165,8 @@ static void process_command_line_options(int argc, char **argv)
 	if (rhs_gpus_given && (rhs_filename == NULL || gpus > 1))
 		usage(argv);
 	if (values_wide && (use_cache || gpus > 1 || rhs_gpus_given || values_signed))
+		usage(argv);
+	if (device_build && (gpus > 1 || rhs_filename != NULL || rhs_gpus_given || use_cache || values_signed || values_wide))
 		usage(argv);
 	if (prime >= (1ull << 62))
 		errx(1, "p is capped at 2**62 - 1.");
@@ -508,7 +516,11 @@ int main(int argc, char **argv)
 		if (fh && blz_prepared_load(cache_path, key, &P) == BLZ_OK)
 			fprintf(stderr, "  - Set-up mapped from %s in %.2fs\n", cache_path, wtime() - t_prep);
 	}
-	if (x_hi) {
+	if (device_build) {
+		/* both CSRs are built on the GPU from the file's triplets; the file's numbering is the solver's (one GPU, no cache) */
+		CHECK(blz_set_matrix_upload(ctx, &M, right_kernel));
+		fprintf(stderr, "  - Device build of CSR(M), CSR(M^T) (upload, check, scan, scatter; numbering kept): %.2fs\n", wtime() - t_prep);
+	} else if (x_hi) {
 		/* the one-call form carries the high limbs through the renumbering and the CSR builds (one GPU, no cache) */
 		CHECK(blz_set_values_wide(ctx, x_hi, M.nnz));
 		CHECK(blz_set_matrix(ctx, &M, right_kernel, 0, 1));

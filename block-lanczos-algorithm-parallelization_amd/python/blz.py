@@ -277,6 +277,45 @@ def device_pair_out(out, n, rows, device=None, block=None):
     return res
 
 
+TRIPLET_INDEX_DTYPES = {"torch.int32": 4, "torch.int64": 8}
+TRIPLET_VALUE_DTYPES = {"torch.uint32": 4, "torch.int32": 4, "torch.uint64": 8, "torch.int64": 8}   # bits read as unsigned
+
+
+def _device_vector(t, what, dtypes, device, length=None):
+    """(pointer, element bytes, length) of a 1-D contiguous tensor of one of `dtypes` on the context's device"""
+    if str(t.dtype) not in dtypes:
+        raise ValueError(f"device triplets: {what}: dtype {t.dtype} is not one of {', '.join(dtypes)}")
+    if getattr(t.device, "type", None) != "cuda":
+        raise ValueError(f"device triplets: {what} lives on {t.device}, not on a GPU")
+    index = t.device.index if t.device.index is not None else 0
+    if device is not None and index != device:
+        raise ValueError(f"device triplets: {what} lives on device {index}, the context on device {device}")
+    shape, stride = tuple(t.shape), tuple(t.stride())
+    if len(shape) != 1:
+        raise ValueError(f"device triplets: {what} has {len(shape)} dimensions, not 1")
+    if shape[0] > 1 and stride[0] != 1:
+        raise ValueError(f"device triplets: {what} must be contiguous (stride {stride[0]})")
+    if length is not None and shape[0] != length:
+        raise ValueError(f"device triplets: {what} has {shape[0]} elements, i has {length}")
+    return int(t.data_ptr()), dtypes[str(t.dtype)], int(shape[0])
+
+
+def device_triplets(i, j, x=None, device=None):
+    """(pointer of i, pointer of j, idx_bytes, pointer of x or None, val_bytes, nnz) of the triplets of
+    Context.set_matrix_device held by torch tensors -- or by anything with data_ptr(), shape, stride(), dtype and device: i
+    and j 1-D contiguous of ONE dtype, int32 or int64 (a row of a (2, nnz) index tensor is such a vector), x None or 1-D
+    contiguous of TRIPLET_VALUE_DTYPES with as many elements.  Anything else is a ValueError that names the fault.  torch is
+    not imported here."""
+    pi, ib, nnz = _device_vector(i, "i", TRIPLET_INDEX_DTYPES, device)
+    pj, jb, _ = _device_vector(j, "j", TRIPLET_INDEX_DTYPES, device, nnz)
+    if ib != jb:
+        raise ValueError(f"device triplets: i is {i.dtype} and j is {j.dtype}; the two must agree")
+    if x is None:
+        return pi, pj, ib, None, 0, nnz
+    px, vb, _ = _device_vector(x, "x", TRIPLET_VALUE_DTYPES, device, nnz)
+    return pi, pj, ib, px, vb, nnz
+
+
 class Matrix:
     """struct sparsematrix_t of the reference (sequential/lanczos_modp.c:55-62) as numpy arrays."""
 
@@ -729,6 +768,44 @@ class Context:
         self._hand_over_wide(M)
         check(lib().blz_set_matrix(self.h, C.byref(M.c), C.c_int(int(right)), C.c_int(rank), C.c_int(nranks)))
         self.right = bool(right)
+
+    # ---- device matrix: the triplets are torch tensors on the context's device; torch is imported inside these methods only
+
+    def set_matrix_device(self, i, j, x=None, nrows=None, ncols=None, right=False, stream=None):
+        """blz_set_matrix_device(): M from triplets on the GPU (device_triplets() says what i, j, x may be); both CSRs are
+        built there and the caller's numbering is kept.  nrows / ncols default to 1 + the largest index (a device
+        reduction; an empty matrix needs them given).  Ordered on `stream` (default: torch's current stream); synchronises."""
+        pi, pj, ib, px, vb, nnz = device_triplets(i, j, x, self.device)
+        if nrows is None or ncols is None:
+            if nnz == 0:
+                raise ValueError("set_matrix_device: an empty matrix needs nrows and ncols")
+            nrows = int(i.max()) + 1 if nrows is None else nrows
+            ncols = int(j.max()) + 1 if ncols is None else ncols
+        check(lib().blz_set_matrix_device(self.h, C.c_int64(nrows), C.c_int64(ncols), C.c_int64(nnz), C.c_void_p(pi),
+                                          C.c_void_p(pj), C.c_int(ib), C.c_void_p(px), C.c_int(vb), C.c_int(int(bool(right))),
+                                          C.c_void_p(self._stream(stream))))
+        self.right = bool(right)
+
+    def set_matrix_sparse(self, t, right=False, stream=None):
+        """set_matrix_device() of a 2-D torch sparse COO tensor: rows 0 and 1 of its _indices() and its _values(), dimensions
+        from t.shape.  The tensor need not be coalesced: duplicates add up."""
+        if len(tuple(t.shape)) != 2:
+            raise ValueError(f"set_matrix_sparse: {len(tuple(t.shape))} dimensions, a matrix has 2")
+        idx, val = t._indices(), t._values()
+        if not idx.is_contiguous():
+            idx = idx.contiguous()
+        self.set_matrix_device(idx[0], idx[1], val.contiguous(), nrows=int(t.shape[0]), ncols=int(t.shape[1]), right=right,
+                               stream=stream)
+
+    def set_matrix_upload(self, M, right=False):
+        """blz_set_matrix_upload(): the host triplets of M through the device build (numbering kept, as set_matrix_device)."""
+        if getattr(M, "x_hi", None) is not None:
+            raise ValueError("set_matrix_upload: wide entries go through set_matrix_device as 8-byte values")
+        check(lib().blz_set_matrix_upload(self.h, C.byref(M.c), C.c_int(int(bool(right)))))
+        self.right = bool(right)
+
+    def matrix_device_built(self):
+        return bool(lib().blz_matrix_device_built(self.h))
 
     def set_matrix_prepared(self, P, rank=0):
         check(lib().blz_set_matrix_prepared(self.h, P.h, C.c_int(rank)))
@@ -1386,19 +1463,27 @@ def solve_rhs(M, b, prime, n, right=False, batch=16, device=0, signed=False, wid
         return dict(status=status, x=x, iterations=ctx.iterations, final_check=fc)
 
 
-def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0, basis=False, signed=False, wide=False):
+def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0, basis=False, signed=False, wide=False,
+          device_build=False):
     """block_lanczos(), sequential/lanczos_modp.c:585-669, on one GPU.  Returns dict(v, tmp, iterations).
     basis=True (not with stop_after): also reduce the final block to independent kernel vectors (blz_kernel_basis) --
     adds basis (rows x k array), k and z to the result; v, tmp and p stay those of the plain solve.
     signed=True: M.x holds int32 bit patterns (Matrix.load_signed) and an entry a means a mod p.
     wide: the wide value mode comes from the matrix (M.x_hi, handed over by set_matrix); the argument only says so at the
-    call site and changes nothing -- a matrix whose residues all fit 32 bits has x_hi None and is an ordinary one."""
+    call site and changes nothing -- a matrix whose residues all fit 32 bits has x_hi None and is an ordinary one.
+    device_build=True: the matrix is set with set_matrix_upload (both CSRs built on the GPU, the file's numbering kept; not
+    with signed or wide entries); every block of the result is the same, word for word."""
     if basis and stop_after > 0:
         raise ValueError("basis=True needs a run to the end (stop_after < 0)")
+    if device_build and (signed or getattr(M, "x_hi", None) is not None):
+        raise ValueError("device_build=True takes neither signed nor wide entries")
     with Context(prime, n, device) as ctx:
         if signed:
             ctx.set_values_signed()
-        ctx.set_matrix(M, right)
+        if device_build:
+            ctx.set_matrix_upload(M, right)
+        else:
+            ctx.set_matrix(M, right)
         ctx.init_v()
         while True:
             todo = batch

@@ -355,6 +355,40 @@ int blz_slab_wide(const blz_ctx *ctx, int transpose, int piece);
  * rank/nranks = 0/1 for a single GPU. */
 int blz_set_matrix(blz_ctx *ctx, const blz_coo *M, int right, int rank, int nranks);
 
+/* Device matrix: the same matrix from triplets that live on the context's GPU -- CSR(M) and CSR(M^T)
+ * are built there (check + histogram, scan, scatter, palette: csrc/blz_devmat.hip) and the triplets never visit the host.
+ * blz_set_matrix_device means what blz_set_matrix(ctx, M, right, 0, 1) means for the same triplets; afterwards every call
+ * that works on a one-rank context works (blz_set_rhs / blz_set_rhs_block want the extra empty line in nrows / ncols).
+ *   i, j       nnz zero-based indices each, contiguous, idx_bytes = 4 (int32) or 8 (int64: rows 0 and 1 of the indices of a
+ *              torch sparse COO tensor).  Duplicate (i, j) pairs are separate entries that add up.
+ *   x          val_bytes = 0 with x == NULL: every entry is 1; 4: uint32_t residues; 8: uint64_t residues.  Every value is
+ *              below p.  Entries that are all 1 give a pattern slab, 8-byte values of which one reaches 2^32 a wide slab
+ *              (blz_values_wide() == 1, the limits of wide value mode: at most 2^30 entries per row and column), 8-byte
+ *              values that are all below 2^32 exactly what the 4-byte form gives.
+ *   bounds     nrows, ncols < 2^31, nnz < 2^32 - 1.
+ * The caller's numbering is kept: the context is what one created under BLZ_NO_REORDER=1 is after blz_set_matrix -- no
+ * permutation (device blocks go in and out as they are), blz_locality reports 1.0 / kind 0, no panel, no hot rows.  The
+ * scored locality renumbering stays a host feature.
+ * The call is ordered after what the caller has enqueued on `stream` (NULL: the null stream) and synchronises the host: it
+ * reads back the counts of the check pass, the two row_ptr arrays (the outlier lists and the staged plans are made from them on
+ * the host, as ever) and at most 256 palette values, and returns when the matrix is resident.  The caller's arrays are never
+ * written and not referenced after the return.
+ * BLZ_EINVAL, by name, before anything is enqueued: idx_bytes / val_bytes other than the above, x and val_bytes disagreeing, a
+ * pointer not aligned to its element or not inside ONE allocation of the context's device for its whole range, a capturing
+ * stream, a context in signed value mode, pending high limbs (blz_set_values_wide), a matrix on several ranks, a
+ * communicator, a loopback group, BLZ_FORCE_COMM.  BLZ_EINVAL with the counts in the message after the check pass: indices
+ * outside [0, nrows) / [0, ncols) (any int64 index of 2^31 or more or below 0 included) and values not below p; no index
+ * is used as an address before it has been checked and nothing is scattered before the host has read the counts as zero.
+ * A refused or invalid call leaves the context exactly as it was: the matrix that was resident still applies.  A failure
+ * after that point (out of memory, a HIP error) leaves the context WITHOUT a matrix.
+ *   blz_set_matrix_upload    host triplets through the same build: they are copied into temporary device buffers.  The same
+ *                            refusals, and those of blz_set_matrix for the blz_coo itself.  (The CLI's --device-build.)
+ *   blz_matrix_device_built  1 when the resident matrix was built on the device, 0 otherwise */
+int blz_set_matrix_device(blz_ctx *ctx, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j, int idx_bytes,
+			  const void *x, int val_bytes, int right, void *stream);
+int blz_set_matrix_upload(blz_ctx *ctx, const blz_coo *M, int right);
+int blz_matrix_device_built(const blz_ctx *ctx);
+
 /* The same with the rank-independent work done once and shared (blz_prepare / blz_prepared_load above):
  *   blz_prepare_for   prepares M with the parameters THIS context wants (pieces per exchange from the slab sizes and
  *                     BLZ_AG_CHUNKS, renumbering, panel capacity from its block width and word size)
