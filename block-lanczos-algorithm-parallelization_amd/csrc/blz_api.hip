@@ -3293,29 +3293,36 @@ static int devio_check_alloc(const blz_ctx *c, const char *who, const char *arg,
 	return BLZ_OK;
 }
 
-/* No kernel is launched on memory the library has not checked: the words [ptr, ptr + ((rows - 1) * ld + n) * 8) must lie
- * inside ONE allocation of the context's device.  A host pointer, another device's memory, managed or pinned host memory,
- * a range that runs past its allocation and ld < n are all BLZ_EINVAL, named by argument.  *bytes_out = the size checked.
+/* No kernel is launched on memory the library has not checked: the words [ptr, ptr + ((rows - 1) * ld + n) * word) must lie
+ * inside ONE allocation of the context's device, `word` being the bytes of a word of the caller's block (8, or 4 for the
+ * 32-bit family).  A host pointer, another device's memory, managed or pinned host memory, a range that runs past its
+ * allocation and ld < n are all BLZ_EINVAL, named by argument.  *bytes_out = the size checked.
  * `rows` is the block's own: a side of the matrix for set / get / apply, the caller's for the block algebra (an n x n operand
- * is n rows of stride n).  A block of no rows has no words: any pointer will do, nothing is looked up and *bytes_out = 0. */
+ * is n rows of stride n).  A block of no rows has no words: any pointer will do, nothing is looked up and *bytes_out = 0.
+ * The size limits are each width's own: rows and stride at most 2^40 for 8-byte words, the byte count at most 2^62 for 4-byte
+ * ones (whose callers have refused a negative row count before they come here). */
 static int devio_check_range(const blz_ctx *c, const char *who, const char *arg, const void *ptr, int64_t rows, int64_t ld,
-			     size_t *bytes_out)
+			     size_t *bytes_out, int word = 8)
 {
 	const int n = c->un;
 	if (!ptr && rows != 0)
 		return blz_fail(BLZ_EINVAL, "%s: %s is NULL", who, arg);
 	if (ld < n)
 		return blz_fail(BLZ_EINVAL, "%s: the row stride of %s is %lld words, less than n = %d", who, arg, (long long)ld, n);
-	if (((uintptr_t)ptr & 7) != 0)
-		return blz_fail(BLZ_EINVAL, "%s: %s is not aligned to 8 bytes", who, arg);
-	if (rows < 0 || rows > ((int64_t)1 << 40) || ld > ((int64_t)1 << 40))
+	if (((uintptr_t)ptr & (uintptr_t)(word - 1)) != 0)
+		return blz_fail(BLZ_EINVAL, "%s: %s is not aligned to %d bytes", who, arg, word);
+	if (rows < 0 || (word == 8 && (rows > ((int64_t)1 << 40) || ld > ((int64_t)1 << 40))))
 		return blz_fail(BLZ_EINVAL, "%s: %s: %lld rows with a row stride of %lld words", who, arg, (long long)rows, (long long)ld);
 	if (rows == 0) {
 		if (bytes_out)
 			*bytes_out = 0;
 		return BLZ_OK;
 	}
-	const size_t bytes = ((size_t)(rows - 1) * (size_t)ld + (size_t)n) * 8;
+	const unsigned __int128 wide = ((unsigned __int128)(rows - 1) * (unsigned __int128)ld + (unsigned __int128)n) * (unsigned)word;
+	if (word == 4 && wide > ((unsigned __int128)1 << 62))
+		return blz_fail(BLZ_EINVAL, "%s: %s of %lld rows with a row stride of %lld words leaves 64-bit byte offsets", who, arg,
+				(long long)rows, (long long)ld);
+	const size_t bytes = (size_t)wide;
 	const int rc = devio_check_alloc(c, who, arg, ptr, bytes, rows, ld);
 	if (rc != BLZ_OK)
 		return rc;
@@ -3339,6 +3346,11 @@ static int devio_check_words(const blz_ctx *c, const char *who, const char *arg,
 	return BLZ_OK;
 }
 
+static bool devalg_overlap(const void *a, size_t ab, const void *b, size_t bb)
+{
+	return (const char *)a < (const char *)b + bb && (const char *)b < (const char *)a + ab;
+}
+
 /* Ordering on the caller's stream, without the host: our stream waits for everything the caller has enqueued so far
  * (devio_enter), the caller's stream for everything we enqueue (devio_leave).  A capturing stream is refused: the work
  * runs on the context's own streams and cannot become part of the caller's graph. */
@@ -3349,6 +3361,33 @@ static int devio_refuse_capture(const char *who, hipStream_t caller)
 	if (cap != hipStreamCaptureStatusNone)
 		return blz_fail(BLZ_EINVAL, "%s: the stream is capturing a graph", who);
 	return BLZ_OK;
+}
+
+/* What every call on caller-owned blocks asks before it looks at an argument, for blocks of `word`-byte words.  The 32-bit
+ * family (word 4) is for a plain single rank and a context of 4-byte words, and says so in its own words. */
+static int devio_begin(blz_ctx *c, const char *who, int word, bool need_matrix, void *stream)
+{
+	if (word == 8) {
+		const int rc = devio_refuse_ranks(c, who);
+		if (rc != BLZ_OK)
+			return rc;
+	} else {
+		if (!c)
+			return blz_fail(BLZ_EINVAL, "%s: NULL context", who);
+		if (c->device_ranks)
+			return blz_fail(BLZ_EINVAL, "%s: 32-bit device blocks need a plain single rank, and device blocks on ranks are "
+					"switched on (blz_set_device_ranks)", who);
+		if (c->nranks > 1 || c->comm || c->loop || c->force_comm)
+			return blz_fail(BLZ_EINVAL, "%s: 32-bit device blocks need a single rank without a communicator, a loopback group or "
+					"BLZ_FORCE_COMM", who);
+		if (c->prime >= ((uint64_t)1 << 32) || c->cfg.word != 4)
+			return blz_fail(BLZ_EINVAL, "%s: p = %llu: residues do not fit 32-bit words (blz_word_bytes is %d)", who,
+					(unsigned long long)c->prime, c->cfg.word);
+	}
+	if (need_matrix && !c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "no matrix loaded (blz_set_matrix)");
+	HIPCHK(hipSetDevice(c->device));
+	return devio_refuse_capture(who, (hipStream_t)stream);
 }
 
 /* the first of the two events: our stream waits for the caller's (no matrix is needed for this much) */
@@ -3382,6 +3421,43 @@ static int devio_leave(blz_ctx *c, hipStream_t caller)
 	HIPCHK(hipEventRecord(c->ev_ours, c->stream));
 	HIPCHK(hipStreamWaitEvent(caller, c->ev_ours, 0));
 	return BLZ_OK;
+}
+
+/* the two scratch slabs of the apply calls, one per side, and control words whose stop flag is never up.  On ranks the rows
+ * past count[side] of a slab are never written and stay zero, which the all-gather relies on */
+static int devio_apply_scratch(blz_ctx *c)
+{
+	for (int sd = 0; sd < 2; sd++)
+		if (!c->slab[APPLY_SLAB + sd]) {
+			const size_t bytes = (size_t)std::max<int64_t>(c->stride[sd], 1) * c->cfg.n * c->cfg.word;
+			HIPCHK(hipMalloc(&c->slab[APPLY_SLAB + sd], bytes));
+			HIPCHK(hipMemset(c->slab[APPLY_SLAB + sd], 0, bytes));
+			c->slab_bytes[APPLY_SLAB + sd] = bytes;
+		}
+	if (!c->apply_ctl) {
+		HIPCHK(hipMalloc((void **)&c->apply_ctl, sizeof(DevCtl)));
+		HIPCHK(hipMemset(c->apply_ctl, 0, sizeof(DevCtl)));
+	}
+	return BLZ_OK;
+}
+
+/* slab `slab`, of side sd, <- the caller's block and back, on the context's stream, by the launcher of the caller's word */
+template <typename W>
+static hipError_t devio_import(blz_ctx *c, int slab, int sd, const W *blk, int64_t ld, unsigned long long *bad)
+{
+	if constexpr (sizeof(W) == 8)
+		return launch_block_import(c->cfg, c->slab[slab], blk, ld, devio_inv(c, sd), c->count[sd], c->un, bad, c->stream);
+	else
+		return launch_w32_import(c->cfg, c->slab[slab], blk, ld, devio_inv(c, sd), c->count[sd], c->un, bad, c->stream);
+}
+
+template <typename W>
+static hipError_t devio_export(blz_ctx *c, W *blk, int64_t ld, int slab, int sd)
+{
+	if constexpr (sizeof(W) == 8)
+		return launch_block_export(c->cfg, blk, ld, c->slab[slab], devio_inv(c, sd), c->count[sd], c->un, c->stream);
+	else
+		return launch_w32_export(c->cfg, blk, ld, c->slab[slab], devio_inv(c, sd), c->count[sd], c->un, c->stream);
 }
 
 /* ---- device matrix: M from triplets on the GPU, both CSRs built there (kernels: blz_devmat.hip) ---- */
@@ -3707,18 +3783,20 @@ extern "C" int blz_set_matrix_upload(blz_ctx *c, const blz_coo *M, int right)
 
 extern "C" int blz_matrix_device_built(const blz_ctx *c) { return c && c->have_matrix && c->device_built ? 1 : 0; }
 
-extern "C" int blz_set_block_device(blz_ctx *c, int block, const uint64_t *dev, int64_t ld, void *stream, int64_t *bad)
+/* The calls below are written once for both word widths of a caller's block: W is uint64_t for blz_..._device and uint32_t
+ * for blz_..._device32, `who` the name the caller used.  The widths differ in what devio_begin refuses,
+ * in the word size of devio_check_range and in the launcher of the last line. */
+
+template <typename W>
+static int devio_set_block(blz_ctx *c, const char *who, int block, const W *dev, int64_t ld, void *stream, int64_t *bad)
 {
-	int rc = devio_refuse_ranks(c, "blz_set_block_device");
+	int rc = devio_begin(c, who, sizeof(W), true, stream);
 	if (rc != BLZ_OK)
 		return rc;
-	NEED_MATRIX(c);
-	if ((rc = devio_refuse_capture("blz_set_block_device", (hipStream_t)stream)) != BLZ_OK)
-		return rc;
 	if (block < 0 || block > 3)
-		return blz_fail(BLZ_EINVAL, "blz_set_block_device: block %d is not one of V, TMP, AV, P", block);
+		return blz_fail(BLZ_EINVAL, "%s: block %d is not one of V, TMP, AV, P", who, block);
 	const int sd = side_of(block);
-	if ((rc = devio_check_range(c, "blz_set_block_device", "dev", dev, devio_rows(c, sd), ld, nullptr)) != BLZ_OK)
+	if ((rc = devio_check_range(c, who, "dev", dev, devio_rows(c, sd), ld, nullptr, sizeof(W))) != BLZ_OK)
 		return rc;
 	if (bad && !c->bad_dev)
 		HIPCHK(hipMalloc((void **)&c->bad_dev, sizeof(unsigned long long)));
@@ -3731,8 +3809,7 @@ extern "C" int blz_set_block_device(blz_ctx *c, int block, const uint64_t *dev, 
 	}
 	if (bad)
 		HIPCHK(hipMemsetAsync(c->bad_dev, 0, sizeof(unsigned long long), c->stream));
-	HIPCHK(launch_block_import(c->cfg, c->slab[block], dev, ld, devio_inv(c, sd), c->count[sd], c->un, bad ? c->bad_dev : nullptr,
-				   c->stream));
+	HIPCHK(devio_import(c, block, sd, dev, ld, bad ? c->bad_dev : nullptr));
 	if (c->gath_holds[sd] == block)
 		c->gath_holds[sd] = -1;		/* on ranks: the gathered copy is of the rows the block had before */
 	if ((rc = devio_leave(c, caller)) != BLZ_OK)
@@ -3743,23 +3820,26 @@ extern "C" int blz_set_block_device(blz_ctx *c, int block, const uint64_t *dev, 
 		HIPCHK(hipMemcpy(&cnt, c->bad_dev, sizeof cnt, hipMemcpyDeviceToHost));
 		*bad = (int64_t)cnt;
 		if (cnt)
-			return blz_fail(BLZ_EINVAL, "blz_set_block_device: %llu words of the block are not residues below p", cnt);
+			return blz_fail(BLZ_EINVAL, "%s: %llu words of the block are not residues below p", who, cnt);
 	}
 	return BLZ_OK;
 }
 
-extern "C" int blz_get_block_device(blz_ctx *c, int block, uint64_t *dev, int64_t ld, void *stream)
+extern "C" int blz_set_block_device(blz_ctx *c, int block, const uint64_t *dev, int64_t ld, void *stream, int64_t *bad)
 {
-	int rc = devio_refuse_ranks(c, "blz_get_block_device");
+	return devio_set_block(c, "blz_set_block_device", block, dev, ld, stream, bad);
+}
+
+template <typename W>
+static int devio_get_block(blz_ctx *c, const char *who, int block, W *dev, int64_t ld, void *stream)
+{
+	int rc = devio_begin(c, who, sizeof(W), true, stream);
 	if (rc != BLZ_OK)
 		return rc;
-	NEED_MATRIX(c);
-	if ((rc = devio_refuse_capture("blz_get_block_device", (hipStream_t)stream)) != BLZ_OK)
-		return rc;
 	if (block < 0 || block > 3)
-		return blz_fail(BLZ_EINVAL, "blz_get_block_device: block %d is not one of V, TMP, AV, P", block);
+		return blz_fail(BLZ_EINVAL, "%s: block %d is not one of V, TMP, AV, P", who, block);
 	const int sd = side_of(block);
-	if ((rc = devio_check_range(c, "blz_get_block_device", "dev", dev, devio_rows(c, sd), ld, nullptr)) != BLZ_OK)
+	if ((rc = devio_check_range(c, who, "dev", dev, devio_rows(c, sd), ld, nullptr, sizeof(W))) != BLZ_OK)
 		return rc;
 	hipStream_t caller = (hipStream_t)stream;
 	if ((rc = devio_enter(c, caller)) != BLZ_OK)
@@ -3770,8 +3850,13 @@ extern "C" int blz_get_block_device(blz_ctx *c, int block, uint64_t *dev, int64_
 		HIPCHK(launch_identity_tail(c->small, np, c->stream));
 		c->p_implicit = false;
 	}
-	HIPCHK(launch_block_export(c->cfg, dev, ld, c->slab[block], devio_inv(c, sd), c->count[sd], c->un, c->stream));
+	HIPCHK(devio_export(c, dev, ld, block, sd));
 	return devio_leave(c, caller);
+}
+
+extern "C" int blz_get_block_device(blz_ctx *c, int block, uint64_t *dev, int64_t ld, void *stream)
+{
+	return devio_get_block(c, "blz_get_block_device", block, dev, ld, stream);
 }
 
 extern "C" int blz_apply_rows(const blz_ctx *c, int transpose, int64_t *x_rows, int64_t *y_rows)
@@ -3786,50 +3871,41 @@ extern "C" int blz_apply_rows(const blz_ctx *c, int transpose, int64_t *x_rows, 
 	return BLZ_OK;
 }
 
-extern "C" int blz_apply_device(blz_ctx *c, int transpose, const uint64_t *x, int64_t ldx, uint64_t *y, int64_t ldy, void *stream)
+template <typename W>
+static int devio_apply(blz_ctx *c, const char *who, int transpose, const W *x, int64_t ldx, W *y, int64_t ldy, void *stream)
 {
-	int rc = devio_refuse_ranks(c, "blz_apply_device");
+	int rc = devio_begin(c, who, sizeof(W), true, stream);
 	if (rc != BLZ_OK)
-		return rc;
-	NEED_MATRIX(c);
-	if ((rc = devio_refuse_capture("blz_apply_device", (hipStream_t)stream)) != BLZ_OK)
 		return rc;
 	const int t = transpose ? 1 : 0, ys = c->row_side[t], xs = 1 - ys;
 	size_t xb = 0, yb = 0;
-	if ((rc = devio_check_range(c, "blz_apply_device", "x", x, devio_rows(c, xs), ldx, &xb)) != BLZ_OK ||
-	    (rc = devio_check_range(c, "blz_apply_device", "y", y, devio_rows(c, ys), ldy, &yb)) != BLZ_OK)
+	if ((rc = devio_check_range(c, who, "x", x, devio_rows(c, xs), ldx, &xb, sizeof(W))) != BLZ_OK ||
+	    (rc = devio_check_range(c, who, "y", y, devio_rows(c, ys), ldy, &yb, sizeof(W))) != BLZ_OK)
 		return rc;
-	if ((const char *)x < (const char *)y + yb && (const char *)y < (const char *)x + xb)
-		return blz_fail(BLZ_EINVAL, "blz_apply_device: x and y overlap");
-	if ((rc = devrank_refuse_product(c, "blz_apply_device", t)) != BLZ_OK)
+	if (devalg_overlap(x, xb, y, yb))
+		return blz_fail(BLZ_EINVAL, "%s: x and y overlap", who);
+	if ((rc = devrank_refuse_product(c, who, t)) != BLZ_OK)
 		return rc;
 	/* (on ranks the product is collective from here on: an error exit tells the loopback peers) */
 	auto enqueue = [&]() -> int {
-		/* two scratch slabs of the context's own, one per side, and control words whose stop flag is never up.  On ranks the
-		 * rows past count[side] of a slab are never written and stay zero, which the all-gather relies on */
-		for (int sd = 0; sd < 2; sd++)
-			if (!c->slab[APPLY_SLAB + sd]) {
-				const size_t bytes = (size_t)std::max<int64_t>(c->stride[sd], 1) * c->cfg.n * c->cfg.word;
-				HIPCHK(hipMalloc(&c->slab[APPLY_SLAB + sd], bytes));
-				HIPCHK(hipMemset(c->slab[APPLY_SLAB + sd], 0, bytes));
-				c->slab_bytes[APPLY_SLAB + sd] = bytes;
-			}
-		if (!c->apply_ctl) {
-			HIPCHK(hipMalloc((void **)&c->apply_ctl, sizeof(DevCtl)));
-			HIPCHK(hipMemset(c->apply_ctl, 0, sizeof(DevCtl)));
-		}
-		hipStream_t caller = (hipStream_t)stream;
-		int rc_ = devio_enter(c, caller);
+		int rc_ = devio_apply_scratch(c);
 		if (rc_ != BLZ_OK)
 			return rc_;
-		HIPCHK(launch_block_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, devio_inv(c, xs), c->count[xs], c->un, nullptr,
-					   c->stream));
+		hipStream_t caller = (hipStream_t)stream;
+		if ((rc_ = devio_enter(c, caller)) != BLZ_OK)
+			return rc_;
+		HIPCHK(devio_import(c, APPLY_SLAB + xs, xs, x, ldx, nullptr));
 		if ((rc_ = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
 			return rc_;
-		HIPCHK(launch_block_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], devio_inv(c, ys), c->count[ys], c->un, c->stream));
+		HIPCHK(devio_export(c, y, ldy, APPLY_SLAB + ys, ys));
 		return devio_leave(c, caller);
 	};
 	return devrank_collective_exit(c, enqueue());
+}
+
+extern "C" int blz_apply_device(blz_ctx *c, int transpose, const uint64_t *x, int64_t ldx, uint64_t *y, int64_t ldy, void *stream)
+{
+	return devio_apply(c, "blz_apply_device", transpose, x, ldx, y, ldy, stream);
 }
 
 extern "C" int blz_apply_release(blz_ctx *c)
@@ -3854,123 +3930,179 @@ extern "C" int blz_apply_release(blz_ctx *c)
 /* ---- device block algebra: X^T * Y and sum_t X_t * A_t on caller-owned device memory (kernels: blz_devalg.hip; DESIGN.md
  * section 16).  No matrix is needed and nothing of a solve is read or written: the only state is the scratch of the dot. ---- */
 
-static bool devalg_overlap(const void *a, size_t ab, const void *b, size_t bb)
+/* the inner products of both arities and both word widths: nx = 1 writes n * n words, nx = 2 two contiguous panels (the fused
+ * call of DESIGN.md section 18, in its own kernel and with a scratch of its own) */
+template <typename W>
+static int devalg_dot(blz_ctx *c, const char *who, int64_t rows, int nx, const W *const *x, const int64_t *ldx, const W *y,
+		      int64_t ldy, uint64_t *out, void *stream)
 {
-	return (const char *)a < (const char *)b + bb && (const char *)b < (const char *)a + ab;
-}
-
-extern "C" int blz_dot_device(blz_ctx *c, int64_t rows, const uint64_t *x, int64_t ldx, const uint64_t *y, int64_t ldy,
-			      uint64_t *out, void *stream)
-{
-	static const char who[] = "blz_dot_device";
-	int rc = devio_refuse_ranks(c, who);
+	int rc = devio_begin(c, who, sizeof(W), false, stream);
 	if (rc != BLZ_OK)
-		return rc;
-	HIPCHK(hipSetDevice(c->device));
-	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
 		return rc;
 	if (rows < 0)
 		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
 	const int n = c->un;
-	size_t xb = 0, yb = 0, cb = 0;
-	if ((rc = devio_check_range(c, who, "x", x, rows, ldx, &xb)) != BLZ_OK ||
-	    (rc = devio_check_range(c, who, "y", y, rows, ldy, &yb)) != BLZ_OK ||
-	    (rc = devio_check_range(c, who, "c", out, n, n, &cb)) != BLZ_OK)
+	static const char *const xname[2][2] = { { "x", "" }, { "x0", "x1" } };
+	size_t xb[2] = { 0, 0 }, yb = 0, cb = 0;
+	long long ldl[2] = { 0, 0 };
+	for (int k = 0; k < nx; k++) {
+		if ((rc = devio_check_range(c, who, xname[nx - 1][k], x[k], rows, ldx[k], &xb[k], sizeof(W))) != BLZ_OK)
+			return rc;
+		ldl[k] = ldx[k];
+	}
+	if ((rc = devio_check_range(c, who, "y", y, rows, ldy, &yb, sizeof(W))) != BLZ_OK ||
+	    (rc = devio_check_words(c, who, "c", out, (int64_t)nx * n * n, &cb)) != BLZ_OK)
 		return rc;
-	if (devalg_overlap(out, cb, x, xb))
-		return blz_fail(BLZ_EINVAL, "%s: c overlaps x", who);
+	for (int k = 0; k < nx; k++)
+		if (devalg_overlap(out, cb, x[k], xb[k]))
+			return blz_fail(BLZ_EINVAL, "%s: c overlaps %s", who, xname[nx - 1][k]);
 	if (devalg_overlap(out, cb, y, yb))
 		return blz_fail(BLZ_EINVAL, "%s: c overlaps y", who);
 	int N = 1;
-	bool collective = false;
+	bool collective = false;	/* (never, for 32-bit words: they are not on ranks) */
 	if ((rc = devrank_dot_ranks(c, who, &N, &collective)) != BLZ_OK)
 		return rc;
 	auto enqueue = [&]() -> int {
-		if (!c->devalg_partial)
-			HIPCHK(hipMalloc((void **)&c->devalg_partial, (size_t)dev_dot_max_blocks(c->cfg, n) * n * n * sizeof(u64)));
+		u64 **partial = nx == 1 ? &c->devalg_partial : &c->devfuse_partial;
+		if (!*partial)
+			HIPCHK(hipMalloc((void **)partial, nx == 1 ? (size_t)dev_dot_max_blocks(c->cfg, n) * n * n * sizeof(u64)
+								   : (size_t)dev_dot2_max_blocks(c->cfg, n) * 2 * n * n * sizeof(u64)));
 		int rc_ = collective ? devrank_dot_buffers(c) : BLZ_OK;
 		if (rc_ != BLZ_OK)
 			return rc_;
 		hipStream_t caller = (hipStream_t)stream;
 		if ((rc_ = devio_wait_caller(c, caller)) != BLZ_OK)
 			return rc_;
-		/* on ranks: this rank's residues into the send buffer, their sums over the ranks, the sums' residues into c */
-		HIPCHK(launch_dev_dot(c->cfg, n, rows, x, ldx, y, ldy, c->devalg_partial, collective ? c->devrank_send : out, c->stream));
-		if (collective && (rc_ = devrank_dot_finish(c, out, n * n)) != BLZ_OK)
+		/* on ranks: this rank's residues into the send buffer, their sums over the ranks (both panels through one all-reduce),
+		 * the sums' residues into c */
+		u64 *dst = collective ? c->devrank_send : out;
+		if constexpr (sizeof(W) == 4)
+			HIPCHK(launch_w32_dot(c->cfg, n, rows, nx, x, ldl, y, ldy, *partial, dst, c->stream));
+		else if (nx == 1)
+			HIPCHK(launch_dev_dot(c->cfg, n, rows, x[0], ldl[0], y, ldy, *partial, dst, c->stream));
+		else
+			HIPCHK(launch_dev_dot2(c->cfg, n, rows, x[0], ldl[0], x[1], ldl[1], y, ldy, *partial, dst, c->stream));
+		if (collective && (rc_ = devrank_dot_finish(c, out, nx * n * n)) != BLZ_OK)
 			return rc_;
 		return devio_leave(c, caller);
 	};
 	return collective ? devrank_collective_exit(c, enqueue()) : enqueue();
 }
 
-extern "C" int blz_combine_device(blz_ctx *c, int64_t rows, int nterms, const uint64_t *const *x, const int64_t *ldx,
-				  const uint64_t *const *a, uint64_t *z, int64_t ldz, void *stream)
+extern "C" int blz_dot_device(blz_ctx *c, int64_t rows, const uint64_t *x, int64_t ldx, const uint64_t *y, int64_t ldy,
+			      uint64_t *out, void *stream)
 {
-	static const char who[] = "blz_combine_device";
-	int rc = devio_refuse_ranks(c, who);
+	return devalg_dot<uint64_t>(c, "blz_dot_device", rows, 1, &x, &ldx, y, ldy, out, stream);
+}
+
+/* the recombinations of both arities and both word widths: nz = 1 has a0 and z0 only, nz = 2 is the fused call */
+template <typename W>
+static int devalg_combine(blz_ctx *c, const char *who, int64_t rows, int nterms, const W *const *x, const int64_t *ldx, int nz,
+			  const uint64_t *const *a0, const uint64_t *const *a1, W *z0, int64_t ldz0, W *z1, int64_t ldz1, void *stream)
+{
+	int rc = devio_begin(c, who, sizeof(W), false, stream);
 	if (rc != BLZ_OK)
-		return rc;
-	HIPCHK(hipSetDevice(c->device));
-	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
 		return rc;
 	if (nterms < 1 || nterms > BLZ_MAX_TERMS)
 		return blz_fail(BLZ_EINVAL, "%s: nterms = %d is outside 1..%d", who, nterms, BLZ_MAX_TERMS);
 	if (rows < 0)
 		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
-	if (!x || !ldx || !a)
-		return blz_fail(BLZ_EINVAL, "%s: the array of %s is NULL", who, !x ? "x" : !ldx ? "ldx" : "a");
+	if (!x || !ldx || !a0 || (nz == 2 && !a1))
+		return blz_fail(BLZ_EINVAL, "%s: the array of %s is NULL", who, !x ? "x" : !ldx ? "ldx" : !a0 ? (nz == 2 ? "a0" : "a") : "a1");
+	const uint64_t *const *a[2] = { a0, a1 };
+	W *z[2] = { z0, z1 };
+	const int64_t ldz[2] = { ldz0, ldz1 };
+	if (nz == 2) {
+		int in[2] = { 0, 0 };
+		for (int t = 0; t < nterms; t++) {
+			if (!a0[t] && !a1[t])
+				return blz_fail(BLZ_EINVAL, "%s: term %d enters neither output (a0[%d] and a1[%d] are both NULL)", who, t, t, t);
+			in[0] += a0[t] != nullptr;
+			in[1] += a1[t] != nullptr;
+		}
+		for (int o = 0; o < 2; o++)
+			if (!in[o])
+				return blz_fail(BLZ_EINVAL, "%s: output z%d has no term (every a%d[t] is NULL)", who, o, o);
+	}
 	const int n = c->un;
-	size_t xb[BLZ_MAX_TERMS] = { 0 }, ab[BLZ_MAX_TERMS] = { 0 }, zb = 0;
+	size_t xb[BLZ_MAX_TERMS] = { 0 }, ab[2][BLZ_MAX_TERMS] = { { 0 } }, zb[2] = { 0, 0 };
 	long long ldl[BLZ_MAX_TERMS] = { 0 };
-	char xn[8], an[8];
+	char nm[12], zn[2][4] = { "z", "" };
+	if (nz == 2)
+		for (int o = 0; o < 2; o++)
+			snprintf(zn[o], sizeof zn[o], "z%d", o);
 	for (int t = 0; t < nterms; t++) {
-		snprintf(xn, sizeof xn, "x[%d]", t);
-		snprintf(an, sizeof an, "a[%d]", t);
-		if ((rc = devio_check_range(c, who, xn, x[t], rows, ldx[t], &xb[t])) != BLZ_OK ||
-		    (rc = devio_check_range(c, who, an, a[t], n, n, &ab[t])) != BLZ_OK)
+		snprintf(nm, sizeof nm, "x[%d]", t);
+		if ((rc = devio_check_range(c, who, nm, x[t], rows, ldx[t], &xb[t], sizeof(W))) != BLZ_OK)
 			return rc;
+		for (int o = 0; o < nz; o++) {
+			if (nz == 2)
+				snprintf(nm, sizeof nm, "a%d[%d]", o, t);
+			else
+				snprintf(nm, sizeof nm, "a[%d]", t);
+			/* (a coefficient of the pair may be NULL: the term does not enter that output) */
+			if ((nz == 1 || a[o][t]) && (rc = devio_check_range(c, who, nm, a[o][t], n, n, &ab[o][t])) != BLZ_OK)
+				return rc;
+		}
 		ldl[t] = ldx[t];
 	}
-	if ((rc = devio_check_range(c, who, "z", z, rows, ldz, &zb)) != BLZ_OK)
-		return rc;
-	for (int t = 0; t < nterms; t++) {
-		const bool in_place = x[t] == z && ldx[t] == ldz;
-		if (!in_place && devalg_overlap(z, zb, x[t], xb[t]))
-			return blz_fail(BLZ_EINVAL, "%s: z overlaps x[%d] without being it (the in-place form is the same pointer and "
-					"the same stride)", who, t);
-		if (devalg_overlap(z, zb, a[t], ab[t]))
-			return blz_fail(BLZ_EINVAL, "%s: z overlaps a[%d]", who, t);
-	}
+	for (int o = 0; o < nz; o++)
+		if ((rc = devio_check_range(c, who, zn[o], z[o], rows, ldz[o], &zb[o], sizeof(W))) != BLZ_OK)
+			return rc;
+	if (nz == 2 && rows > 0 && devalg_overlap(z0, zb[0], z1, zb[1]))
+		return blz_fail(BLZ_EINVAL, "%s: z0 overlaps z1", who);
+	for (int o = 0; o < nz; o++)
+		for (int t = 0; t < nterms; t++) {
+			const bool in_place = x[t] == z[o] && ldx[t] == ldz[o];
+			if (!in_place && devalg_overlap(z[o], zb[o], x[t], xb[t]))
+				return blz_fail(BLZ_EINVAL, "%s: %s overlaps x[%d] without being it (the in-place form is the same pointer "
+						"and the same stride)", who, zn[o], t);
+			for (int q = 0; q < nz; q++) {
+				if (!a[q][t] || !devalg_overlap(z[o], zb[o], a[q][t], ab[q][t]))
+					continue;
+				if (nz == 2)
+					return blz_fail(BLZ_EINVAL, "%s: z%d overlaps a%d[%d]", who, o, q, t);
+				return blz_fail(BLZ_EINVAL, "%s: z overlaps a[%d]", who, t);
+			}
+		}
 	if (rows == 0)
-		return BLZ_OK;	/* z has no words */
+		return BLZ_OK;	/* the outputs have no words */
 	hipStream_t caller = (hipStream_t)stream;
 	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
 		return rc;
-	HIPCHK(launch_dev_combine(c->cfg, n, rows, nterms, x, ldl, a, z, ldz, c->stream));
+	if constexpr (sizeof(W) == 4)
+		HIPCHK(launch_w32_combine(c->cfg, n, rows, nterms, x, ldl, nz, a0, a1, z0, ldz0, z1, ldz1, c->stream));
+	else if (nz == 1)
+		HIPCHK(launch_dev_combine(c->cfg, n, rows, nterms, x, ldl, a0, z0, ldz0, c->stream));
+	else
+		HIPCHK(launch_dev_combine2(c->cfg, n, rows, nterms, x, ldl, a0, a1, z0, ldz0, z1, ldz1, c->stream));
 	return devio_leave(c, caller);
+}
+
+extern "C" int blz_combine_device(blz_ctx *c, int64_t rows, int nterms, const uint64_t *const *x, const int64_t *ldx,
+				  const uint64_t *const *a, uint64_t *z, int64_t ldz, void *stream)
+{
+	return devalg_combine<uint64_t>(c, "blz_combine_device", rows, nterms, x, ldx, 1, a, nullptr, z, ldz, nullptr, 0, stream);
 }
 
 /* ---- fused device calls: z = op2 (op1 x), two inner products against one block, two recombinations of shared inputs, each in
  * one call and one pass (kernels: blz_devfuse.hip).  Nothing of a solve is read or written: the state is
  * the scratch slabs and control words of blz_apply_device and a scratch of blz_dot_pair_device's own. ---- */
 
-extern "C" int blz_apply_pair_device(blz_ctx *c, int transpose_first, const uint64_t *x, int64_t ldx, uint64_t *y, int64_t ldy,
-				     uint64_t *z, int64_t ldz, void *stream)
+template <typename W>
+static int devfuse_apply_pair(blz_ctx *c, const char *who, int transpose_first, const W *x, int64_t ldx, W *y, int64_t ldy, W *z,
+			      int64_t ldz, void *stream)
 {
-	static const char who[] = "blz_apply_pair_device";
-	int rc = devio_refuse_ranks(c, who);
+	int rc = devio_begin(c, who, sizeof(W), true, stream);
 	if (rc != BLZ_OK)
-		return rc;
-	NEED_MATRIX(c);
-	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
 		return rc;
 	const int t = transpose_first ? 1 : 0, ys = c->row_side[t], xs = 1 - ys;
 	size_t xb = 0, yb = 0, zb = 0;
-	if ((rc = devio_check_range(c, who, "x", x, devio_rows(c, xs), ldx, &xb)) != BLZ_OK ||
-	    (y && (rc = devio_check_range(c, who, "y", y, devio_rows(c, ys), ldy, &yb)) != BLZ_OK) ||
-	    (rc = devio_check_range(c, who, "z", z, devio_rows(c, xs), ldz, &zb)) != BLZ_OK)
+	if ((rc = devio_check_range(c, who, "x", x, devio_rows(c, xs), ldx, &xb, sizeof(W))) != BLZ_OK ||
+	    (y && (rc = devio_check_range(c, who, "y", y, devio_rows(c, ys), ldy, &yb, sizeof(W))) != BLZ_OK) ||
+	    (rc = devio_check_range(c, who, "z", z, devio_rows(c, xs), ldz, &zb, sizeof(W))) != BLZ_OK)
 		return rc;
-	const bool in_place = (const uint64_t *)z == x && ldz == ldx;
+	const bool in_place = (const W *)z == x && ldz == ldx;
 	if (!in_place && devalg_overlap(z, zb, x, xb))
 		return blz_fail(BLZ_EINVAL, "%s: z overlaps x without being it (the in-place form is the same pointer and the same "
 				"stride)", who);
@@ -3980,154 +4112,46 @@ extern "C" int blz_apply_pair_device(blz_ctx *c, int transpose_first, const uint
 		return blz_fail(BLZ_EINVAL, "%s: y overlaps z", who);
 	if ((rc = devrank_refuse_product(c, who, t)) != BLZ_OK || (rc = devrank_refuse_product(c, who, 1 - t)) != BLZ_OK)
 		return rc;
-	auto enqueue = [&]() -> int {	/* (collective on ranks, as blz_apply_device) */
-		/* the two scratch slabs and the control words of blz_apply_device */
-		for (int sd = 0; sd < 2; sd++)
-			if (!c->slab[APPLY_SLAB + sd]) {
-				const size_t bytes = (size_t)std::max<int64_t>(c->stride[sd], 1) * c->cfg.n * c->cfg.word;
-				HIPCHK(hipMalloc(&c->slab[APPLY_SLAB + sd], bytes));
-				HIPCHK(hipMemset(c->slab[APPLY_SLAB + sd], 0, bytes));
-				c->slab_bytes[APPLY_SLAB + sd] = bytes;
-			}
-		if (!c->apply_ctl) {
-			HIPCHK(hipMalloc((void **)&c->apply_ctl, sizeof(DevCtl)));
-			HIPCHK(hipMemset(c->apply_ctl, 0, sizeof(DevCtl)));
-		}
-		hipStream_t caller = (hipStream_t)stream;
-		int rc_ = devio_enter(c, caller);
+	auto enqueue = [&]() -> int {	/* (collective on ranks, as the single product) */
+		int rc_ = devio_apply_scratch(c);
 		if (rc_ != BLZ_OK)
 			return rc_;
-		HIPCHK(launch_block_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, devio_inv(c, xs), c->count[xs], c->un, nullptr,
-					   c->stream));
+		hipStream_t caller = (hipStream_t)stream;
+		if ((rc_ = devio_enter(c, caller)) != BLZ_OK)
+			return rc_;
+		HIPCHK(devio_import(c, APPLY_SLAB + xs, xs, x, ldx, nullptr));
 		if ((rc_ = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
 			return rc_;
 		if (y)	/* the intermediate is wanted: one pass more; otherwise it lives in its slab only */
-			HIPCHK(launch_block_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], devio_inv(c, ys), c->count[ys], c->un,
-						   c->stream));
-		/* back into the slab x was imported to: the first product has consumed it */
+			HIPCHK(devio_export(c, y, ldy, APPLY_SLAB + ys, ys));
+		/* back into the slab x was imported to: the first product has consumed it (so z may be x) */
 		if ((rc_ = enqueue_product(c, 1 - t, APPLY_SLAB + ys, APPLY_SLAB + xs, false, nullptr, c->apply_ctl)) != BLZ_OK)
 			return rc_;
-		HIPCHK(launch_block_export(c->cfg, z, ldz, c->slab[APPLY_SLAB + xs], devio_inv(c, xs), c->count[xs], c->un, c->stream));
+		HIPCHK(devio_export(c, z, ldz, APPLY_SLAB + xs, xs));
 		return devio_leave(c, caller);
 	};
 	return devrank_collective_exit(c, enqueue());
 }
 
+extern "C" int blz_apply_pair_device(blz_ctx *c, int transpose_first, const uint64_t *x, int64_t ldx, uint64_t *y, int64_t ldy,
+				     uint64_t *z, int64_t ldz, void *stream)
+{
+	return devfuse_apply_pair(c, "blz_apply_pair_device", transpose_first, x, ldx, y, ldy, z, ldz, stream);
+}
+
 extern "C" int blz_dot_pair_device(blz_ctx *c, int64_t rows, const uint64_t *x0, int64_t ldx0, const uint64_t *x1, int64_t ldx1,
 				   const uint64_t *y, int64_t ldy, uint64_t *out, void *stream)
 {
-	static const char who[] = "blz_dot_pair_device";
-	int rc = devio_refuse_ranks(c, who);
-	if (rc != BLZ_OK)
-		return rc;
-	HIPCHK(hipSetDevice(c->device));
-	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
-		return rc;
-	if (rows < 0)
-		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
-	const int n = c->un;
-	size_t x0b = 0, x1b = 0, yb = 0, cb = 0;
-	if ((rc = devio_check_range(c, who, "x0", x0, rows, ldx0, &x0b)) != BLZ_OK ||
-	    (rc = devio_check_range(c, who, "x1", x1, rows, ldx1, &x1b)) != BLZ_OK ||
-	    (rc = devio_check_range(c, who, "y", y, rows, ldy, &yb)) != BLZ_OK ||
-	    (rc = devio_check_words(c, who, "c", out, (int64_t)2 * n * n, &cb)) != BLZ_OK)
-		return rc;
-	if (devalg_overlap(out, cb, x0, x0b))
-		return blz_fail(BLZ_EINVAL, "%s: c overlaps x0", who);
-	if (devalg_overlap(out, cb, x1, x1b))
-		return blz_fail(BLZ_EINVAL, "%s: c overlaps x1", who);
-	if (devalg_overlap(out, cb, y, yb))
-		return blz_fail(BLZ_EINVAL, "%s: c overlaps y", who);
-	int N = 1;
-	bool collective = false;
-	if ((rc = devrank_dot_ranks(c, who, &N, &collective)) != BLZ_OK)
-		return rc;
-	auto enqueue = [&]() -> int {
-		if (!c->devfuse_partial)
-			HIPCHK(hipMalloc((void **)&c->devfuse_partial, (size_t)dev_dot2_max_blocks(c->cfg, n) * 2 * n * n * sizeof(u64)));
-		int rc_ = collective ? devrank_dot_buffers(c) : BLZ_OK;
-		if (rc_ != BLZ_OK)
-			return rc_;
-		hipStream_t caller = (hipStream_t)stream;
-		if ((rc_ = devio_wait_caller(c, caller)) != BLZ_OK)
-			return rc_;
-		/* on ranks: both panels through one all-reduce of 2 n^2 words (blz_dot_device) */
-		HIPCHK(launch_dev_dot2(c->cfg, n, rows, x0, ldx0, x1, ldx1, y, ldy, c->devfuse_partial, collective ? c->devrank_send : out,
-				       c->stream));
-		if (collective && (rc_ = devrank_dot_finish(c, out, 2 * n * n)) != BLZ_OK)
-			return rc_;
-		return devio_leave(c, caller);
-	};
-	return collective ? devrank_collective_exit(c, enqueue()) : enqueue();
+	const uint64_t *x[2] = { x0, x1 };
+	const int64_t ldx[2] = { ldx0, ldx1 };
+	return devalg_dot<uint64_t>(c, "blz_dot_pair_device", rows, 2, x, ldx, y, ldy, out, stream);
 }
 
 extern "C" int blz_combine_pair_device(blz_ctx *c, int64_t rows, int nterms, const uint64_t *const *x, const int64_t *ldx,
 				       const uint64_t *const *a0, const uint64_t *const *a1, uint64_t *z0, int64_t ldz0, uint64_t *z1,
 				       int64_t ldz1, void *stream)
 {
-	static const char who[] = "blz_combine_pair_device";
-	int rc = devio_refuse_ranks(c, who);
-	if (rc != BLZ_OK)
-		return rc;
-	HIPCHK(hipSetDevice(c->device));
-	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
-		return rc;
-	if (nterms < 1 || nterms > BLZ_MAX_TERMS)
-		return blz_fail(BLZ_EINVAL, "%s: nterms = %d is outside 1..%d", who, nterms, BLZ_MAX_TERMS);
-	if (rows < 0)
-		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
-	if (!x || !ldx || !a0 || !a1)
-		return blz_fail(BLZ_EINVAL, "%s: the array of %s is NULL", who, !x ? "x" : !ldx ? "ldx" : !a0 ? "a0" : "a1");
-	int in[2] = { 0, 0 };
-	for (int t = 0; t < nterms; t++) {
-		if (!a0[t] && !a1[t])
-			return blz_fail(BLZ_EINVAL, "%s: term %d enters neither output (a0[%d] and a1[%d] are both NULL)", who, t, t, t);
-		in[0] += a0[t] != nullptr;
-		in[1] += a1[t] != nullptr;
-	}
-	for (int o = 0; o < 2; o++)
-		if (!in[o])
-			return blz_fail(BLZ_EINVAL, "%s: output z%d has no term (every a%d[t] is NULL)", who, o, o);
-	const int n = c->un;
-	const uint64_t *const *a[2] = { a0, a1 };
-	uint64_t *z[2] = { z0, z1 };
-	const int64_t ldz[2] = { ldz0, ldz1 };
-	size_t xb[BLZ_MAX_TERMS] = { 0 }, ab[2][BLZ_MAX_TERMS] = { { 0 } }, zb[2] = { 0, 0 };
-	long long ldl[BLZ_MAX_TERMS] = { 0 };
-	char nm[12];
-	for (int t = 0; t < nterms; t++) {
-		snprintf(nm, sizeof nm, "x[%d]", t);
-		if ((rc = devio_check_range(c, who, nm, x[t], rows, ldx[t], &xb[t])) != BLZ_OK)
-			return rc;
-		for (int o = 0; o < 2; o++) {
-			snprintf(nm, sizeof nm, "a%d[%d]", o, t);
-			if (a[o][t] && (rc = devio_check_range(c, who, nm, a[o][t], n, n, &ab[o][t])) != BLZ_OK)
-				return rc;
-		}
-		ldl[t] = ldx[t];
-	}
-	if ((rc = devio_check_range(c, who, "z0", z0, rows, ldz0, &zb[0])) != BLZ_OK ||
-	    (rc = devio_check_range(c, who, "z1", z1, rows, ldz1, &zb[1])) != BLZ_OK)
-		return rc;
-	if (rows > 0 && devalg_overlap(z0, zb[0], z1, zb[1]))
-		return blz_fail(BLZ_EINVAL, "%s: z0 overlaps z1", who);
-	for (int o = 0; o < 2; o++)
-		for (int t = 0; t < nterms; t++) {
-			const bool in_place = x[t] == z[o] && ldx[t] == ldz[o];
-			if (!in_place && devalg_overlap(z[o], zb[o], x[t], xb[t]))
-				return blz_fail(BLZ_EINVAL, "%s: z%d overlaps x[%d] without being it (the in-place form is the same pointer "
-						"and the same stride)", who, o, t);
-			for (int q = 0; q < 2; q++)
-				if (a[q][t] && devalg_overlap(z[o], zb[o], a[q][t], ab[q][t]))
-					return blz_fail(BLZ_EINVAL, "%s: z%d overlaps a%d[%d]", who, o, q, t);
-		}
-	if (rows == 0)
-		return BLZ_OK;	/* the outputs have no words */
-	hipStream_t caller = (hipStream_t)stream;
-	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
-		return rc;
-	HIPCHK(launch_dev_combine2(c->cfg, n, rows, nterms, x, ldl, a0, a1, z0, ldz0, z1, ldz1, c->stream));
-	return devio_leave(c, caller);
+	return devalg_combine(c, "blz_combine_pair_device", rows, nterms, x, ldx, 2, a0, a1, z0, ldz0, z1, ldz1, stream);
 }
 
 /* ---- device small algebra: the n x n chain of a Krylov step and the echelon form of a caller's block (kernels:
@@ -4299,243 +4323,34 @@ extern "C" int blz_put_local_device(blz_ctx *c, int block, const uint64_t *local
 /* ---- 32-bit device blocks: the family above on a caller's blocks of uint32_t words, for contexts of 4-byte words (p < 2^32;
  * kernels: blz_devw32.hip).  Each call writes the words its 64-bit namesake writes, truncated; the n x n
  * operands stay u64, the scratch is the namesake's (the apply slabs, devalg_partial, devfuse_partial), and the two families
- * interleave freely on one context.  A plain single rank only: no device blocks on ranks, no echelon. ---- */
-
-static int w32_begin(blz_ctx *c, const char *who, void *stream, bool need_matrix)
-{
-	if (!c)
-		return blz_fail(BLZ_EINVAL, "%s: NULL context", who);
-	if (c->device_ranks)
-		return blz_fail(BLZ_EINVAL, "%s: 32-bit device blocks need a plain single rank, and device blocks on ranks are "
-				"switched on (blz_set_device_ranks)", who);
-	if (c->nranks > 1 || c->comm || c->loop || c->force_comm)
-		return blz_fail(BLZ_EINVAL, "%s: 32-bit device blocks need a single rank without a communicator, a loopback group or "
-				"BLZ_FORCE_COMM", who);
-	if (c->prime >= ((uint64_t)1 << 32) || c->cfg.word != 4)
-		return blz_fail(BLZ_EINVAL, "%s: p = %llu: residues do not fit 32-bit words (blz_word_bytes is %d)", who,
-				(unsigned long long)c->prime, c->cfg.word);
-	if (need_matrix && !c->have_matrix)
-		return blz_fail(BLZ_EINVAL, "no matrix loaded (blz_set_matrix)");
-	HIPCHK(hipSetDevice(c->device));
-	return devio_refuse_capture(who, (hipStream_t)stream);
-}
-
-/* devio_check_range for a block of 4-byte words: [ptr, ptr + ((rows - 1) * ld + n) * 4) inside ONE allocation of the
- * context's device, ptr aligned to 4 bytes, ld >= n, the byte offsets within 64 bits. */
-static int w32_check_range(const blz_ctx *c, const char *who, const char *arg, const void *ptr, int64_t rows, int64_t ld,
-			   size_t *bytes_out)
-{
-	const int n = c->un;
-	if (!ptr && rows != 0)
-		return blz_fail(BLZ_EINVAL, "%s: %s is NULL", who, arg);
-	if (ld < n)
-		return blz_fail(BLZ_EINVAL, "%s: the row stride of %s is %lld words, less than n = %d", who, arg, (long long)ld, n);
-	if (((uintptr_t)ptr & 3) != 0)
-		return blz_fail(BLZ_EINVAL, "%s: %s is not aligned to 4 bytes", who, arg);
-	if (rows < 0)
-		return blz_fail(BLZ_EINVAL, "%s: %s: %lld rows", who, arg, (long long)rows);
-	if (rows == 0) {
-		if (bytes_out)
-			*bytes_out = 0;
-		return BLZ_OK;
-	}
-	const unsigned __int128 wide = ((unsigned __int128)(rows - 1) * (unsigned __int128)ld + (unsigned __int128)n) * 4;
-	if (wide > ((unsigned __int128)1 << 62))
-		return blz_fail(BLZ_EINVAL, "%s: %s of %lld rows with a row stride of %lld words leaves 64-bit byte offsets", who, arg,
-				(long long)rows, (long long)ld);
-	const size_t bytes = (size_t)wide;
-	const int rc = devio_check_alloc(c, who, arg, ptr, bytes, rows, ld);
-	if (rc != BLZ_OK)
-		return rc;
-	if (bytes_out)
-		*bytes_out = bytes;
-	return BLZ_OK;
-}
-
-/* the two scratch slabs and the control words of blz_apply_device, shared with it */
-static int w32_apply_scratch(blz_ctx *c)
-{
-	for (int sd = 0; sd < 2; sd++)
-		if (!c->slab[APPLY_SLAB + sd]) {
-			const size_t bytes = (size_t)std::max<int64_t>(c->stride[sd], 1) * c->cfg.n * c->cfg.word;
-			HIPCHK(hipMalloc(&c->slab[APPLY_SLAB + sd], bytes));
-			HIPCHK(hipMemset(c->slab[APPLY_SLAB + sd], 0, bytes));
-			c->slab_bytes[APPLY_SLAB + sd] = bytes;
-		}
-	if (!c->apply_ctl) {
-		HIPCHK(hipMalloc((void **)&c->apply_ctl, sizeof(DevCtl)));
-		HIPCHK(hipMemset(c->apply_ctl, 0, sizeof(DevCtl)));
-	}
-	return BLZ_OK;
-}
+ * interleave freely on one context.  A plain single rank only: no device blocks on ranks, no echelon.  The bodies are the
+ * namesakes', at W = uint32_t. ---- */
 
 extern "C" int blz_set_block_device32(blz_ctx *c, int block, const uint32_t *dev, int64_t ld, void *stream, int64_t *bad)
 {
-	static const char who[] = "blz_set_block_device32";
-	int rc = w32_begin(c, who, stream, true);
-	if (rc != BLZ_OK)
-		return rc;
-	if (block < 0 || block > 3)
-		return blz_fail(BLZ_EINVAL, "%s: block %d is not one of V, TMP, AV, P", who, block);
-	const int sd = side_of(block);
-	if ((rc = w32_check_range(c, who, "dev", dev, c->glob_rows[sd], ld, nullptr)) != BLZ_OK)
-		return rc;
-	if (bad && !c->bad_dev)
-		HIPCHK(hipMalloc((void **)&c->bad_dev, sizeof(unsigned long long)));
-	hipStream_t caller = (hipStream_t)stream;
-	if ((rc = devio_enter(c, caller)) != BLZ_OK)
-		return rc;
-	if (block == BLZ_P) {	/* p is what the caller says from here on (as blz_set_block_device) */
-		HIPCHK(launch_identity_tail(c->small, c->cfg.n, c->stream));
-		c->p_implicit = false;
-	}
-	if (bad)
-		HIPCHK(hipMemsetAsync(c->bad_dev, 0, sizeof(unsigned long long), c->stream));
-	HIPCHK(launch_w32_import(c->cfg, c->slab[block], dev, ld, c->inv_dev[sd], c->count[sd], c->un, bad ? c->bad_dev : nullptr,
-				 c->stream));
-	if (c->gath_holds[sd] == block)
-		c->gath_holds[sd] = -1;
-	if ((rc = devio_leave(c, caller)) != BLZ_OK)
-		return rc;
-	if (bad) {
-		unsigned long long cnt = 0;
-		HIPCHK(hipStreamSynchronize(c->stream));
-		HIPCHK(hipMemcpy(&cnt, c->bad_dev, sizeof cnt, hipMemcpyDeviceToHost));
-		*bad = (int64_t)cnt;
-		if (cnt)
-			return blz_fail(BLZ_EINVAL, "%s: %llu words of the block are not residues below p", who, cnt);
-	}
-	return BLZ_OK;
+	return devio_set_block(c, "blz_set_block_device32", block, dev, ld, stream, bad);
 }
 
 extern "C" int blz_get_block_device32(blz_ctx *c, int block, uint32_t *dev, int64_t ld, void *stream)
 {
-	static const char who[] = "blz_get_block_device32";
-	int rc = w32_begin(c, who, stream, true);
-	if (rc != BLZ_OK)
-		return rc;
-	if (block < 0 || block > 3)
-		return blz_fail(BLZ_EINVAL, "%s: block %d is not one of V, TMP, AV, P", who, block);
-	const int sd = side_of(block);
-	if ((rc = w32_check_range(c, who, "dev", dev, c->glob_rows[sd], ld, nullptr)) != BLZ_OK)
-		return rc;
-	hipStream_t caller = (hipStream_t)stream;
-	if ((rc = devio_enter(c, caller)) != BLZ_OK)
-		return rc;
-	if (block == BLZ_P && c->p_implicit) {	/* materialize_p, on the stream (as blz_get_block_device) */
-		const int np = c->cfg.n;
-		HIPCHK(launch_block_mul(c->cfg, c->slab[BLZ_P], c->count[0], np, np, c->small + small_E(np), c->stream));
-		HIPCHK(launch_identity_tail(c->small, np, c->stream));
-		c->p_implicit = false;
-	}
-	HIPCHK(launch_w32_export(c->cfg, dev, ld, c->slab[block], c->inv_dev[sd], c->count[sd], c->un, c->stream));
-	return devio_leave(c, caller);
+	return devio_get_block(c, "blz_get_block_device32", block, dev, ld, stream);
 }
 
 extern "C" int blz_apply_device32(blz_ctx *c, int transpose, const uint32_t *x, int64_t ldx, uint32_t *y, int64_t ldy, void *stream)
 {
-	static const char who[] = "blz_apply_device32";
-	int rc = w32_begin(c, who, stream, true);
-	if (rc != BLZ_OK)
-		return rc;
-	const int t = transpose ? 1 : 0, ys = c->row_side[t], xs = 1 - ys;
-	size_t xb = 0, yb = 0;
-	if ((rc = w32_check_range(c, who, "x", x, c->glob_rows[xs], ldx, &xb)) != BLZ_OK ||
-	    (rc = w32_check_range(c, who, "y", y, c->glob_rows[ys], ldy, &yb)) != BLZ_OK)
-		return rc;
-	if (devalg_overlap(x, xb, y, yb))
-		return blz_fail(BLZ_EINVAL, "%s: x and y overlap", who);
-	if ((rc = w32_apply_scratch(c)) != BLZ_OK)
-		return rc;
-	hipStream_t caller = (hipStream_t)stream;
-	if ((rc = devio_enter(c, caller)) != BLZ_OK)
-		return rc;
-	HIPCHK(launch_w32_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, c->inv_dev[xs], c->count[xs], c->un, nullptr, c->stream));
-	if ((rc = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
-		return rc;
-	HIPCHK(launch_w32_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], c->inv_dev[ys], c->count[ys], c->un, c->stream));
-	return devio_leave(c, caller);
+	return devio_apply(c, "blz_apply_device32", transpose, x, ldx, y, ldy, stream);
 }
 
 extern "C" int blz_apply_pair_device32(blz_ctx *c, int transpose_first, const uint32_t *x, int64_t ldx, uint32_t *y, int64_t ldy,
 				       uint32_t *z, int64_t ldz, void *stream)
 {
-	static const char who[] = "blz_apply_pair_device32";
-	int rc = w32_begin(c, who, stream, true);
-	if (rc != BLZ_OK)
-		return rc;
-	const int t = transpose_first ? 1 : 0, ys = c->row_side[t], xs = 1 - ys;
-	size_t xb = 0, yb = 0, zb = 0;
-	if ((rc = w32_check_range(c, who, "x", x, c->glob_rows[xs], ldx, &xb)) != BLZ_OK ||
-	    (y && (rc = w32_check_range(c, who, "y", y, c->glob_rows[ys], ldy, &yb)) != BLZ_OK) ||
-	    (rc = w32_check_range(c, who, "z", z, c->glob_rows[xs], ldz, &zb)) != BLZ_OK)
-		return rc;
-	const bool in_place = (const uint32_t *)z == x && ldz == ldx;
-	if (!in_place && devalg_overlap(z, zb, x, xb))
-		return blz_fail(BLZ_EINVAL, "%s: z overlaps x without being it (the in-place form is the same pointer and the same "
-				"stride)", who);
-	if (y && devalg_overlap(y, yb, x, xb))
-		return blz_fail(BLZ_EINVAL, "%s: y overlaps x", who);
-	if (y && devalg_overlap(y, yb, z, zb))
-		return blz_fail(BLZ_EINVAL, "%s: y overlaps z", who);
-	if ((rc = w32_apply_scratch(c)) != BLZ_OK)
-		return rc;
-	hipStream_t caller = (hipStream_t)stream;
-	if ((rc = devio_enter(c, caller)) != BLZ_OK)
-		return rc;
-	HIPCHK(launch_w32_import(c->cfg, c->slab[APPLY_SLAB + xs], x, ldx, c->inv_dev[xs], c->count[xs], c->un, nullptr, c->stream));
-	if ((rc = enqueue_product(c, t, APPLY_SLAB + xs, APPLY_SLAB + ys, false, nullptr, c->apply_ctl)) != BLZ_OK)
-		return rc;
-	if (y)	/* the intermediate is wanted: one pass more; otherwise it lives in its slab only */
-		HIPCHK(launch_w32_export(c->cfg, y, ldy, c->slab[APPLY_SLAB + ys], c->inv_dev[ys], c->count[ys], c->un, c->stream));
-	/* back into the slab x was imported to: the first product has consumed it (so z may be x) */
-	if ((rc = enqueue_product(c, 1 - t, APPLY_SLAB + ys, APPLY_SLAB + xs, false, nullptr, c->apply_ctl)) != BLZ_OK)
-		return rc;
-	HIPCHK(launch_w32_export(c->cfg, z, ldz, c->slab[APPLY_SLAB + xs], c->inv_dev[xs], c->count[xs], c->un, c->stream));
-	return devio_leave(c, caller);
-}
-
-/* the inner products of both arities: nx = 1 writes n * n words, nx = 2 two contiguous panels */
-static int w32_dot(blz_ctx *c, const char *who, int64_t rows, int nx, const uint32_t *const *x, const int64_t *ldx,
-		   const uint32_t *y, int64_t ldy, uint64_t *out, void *stream)
-{
-	int rc = w32_begin(c, who, stream, false);
-	if (rc != BLZ_OK)
-		return rc;
-	if (rows < 0)
-		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
-	const int n = c->un;
-	static const char *const xname[2][2] = { { "x", "" }, { "x0", "x1" } };
-	size_t xb[2] = { 0, 0 }, yb = 0, cb = 0;
-	long long ldl[2] = { 0, 0 };
-	for (int k = 0; k < nx; k++) {
-		if ((rc = w32_check_range(c, who, xname[nx - 1][k], x[k], rows, ldx[k], &xb[k])) != BLZ_OK)
-			return rc;
-		ldl[k] = ldx[k];
-	}
-	if ((rc = w32_check_range(c, who, "y", y, rows, ldy, &yb)) != BLZ_OK ||
-	    (rc = devio_check_words(c, who, "c", out, (int64_t)nx * n * n, &cb)) != BLZ_OK)
-		return rc;
-	for (int k = 0; k < nx; k++)
-		if (devalg_overlap(out, cb, x[k], xb[k]))
-			return blz_fail(BLZ_EINVAL, "%s: c overlaps %s", who, xname[nx - 1][k]);
-	if (devalg_overlap(out, cb, y, yb))
-		return blz_fail(BLZ_EINVAL, "%s: c overlaps y", who);
-	u64 **partial = nx == 1 ? &c->devalg_partial : &c->devfuse_partial;
-	if (!*partial)	/* the namesake's scratch, of the namesake's size */
-		HIPCHK(hipMalloc((void **)partial, nx == 1 ? (size_t)dev_dot_max_blocks(c->cfg, n) * n * n * sizeof(u64)
-							   : (size_t)dev_dot2_max_blocks(c->cfg, n) * 2 * n * n * sizeof(u64)));
-	hipStream_t caller = (hipStream_t)stream;
-	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
-		return rc;
-	HIPCHK(launch_w32_dot(c->cfg, n, rows, nx, x, ldl, y, ldy, *partial, out, c->stream));
-	return devio_leave(c, caller);
+	return devfuse_apply_pair(c, "blz_apply_pair_device32", transpose_first, x, ldx, y, ldy, z, ldz, stream);
 }
 
 extern "C" int blz_dot_device32(blz_ctx *c, int64_t rows, const uint32_t *x, int64_t ldx, const uint32_t *y, int64_t ldy,
 				uint64_t *out, void *stream)
 {
-	return w32_dot(c, "blz_dot_device32", rows, 1, &x, &ldx, y, ldy, out, stream);
+	return devalg_dot<uint32_t>(c, "blz_dot_device32", rows, 1, &x, &ldx, y, ldy, out, stream);
 }
 
 extern "C" int blz_dot_pair_device32(blz_ctx *c, int64_t rows, const uint32_t *x0, int64_t ldx0, const uint32_t *x1, int64_t ldx1,
@@ -4543,95 +4358,19 @@ extern "C" int blz_dot_pair_device32(blz_ctx *c, int64_t rows, const uint32_t *x
 {
 	const uint32_t *x[2] = { x0, x1 };
 	const int64_t ldx[2] = { ldx0, ldx1 };
-	return w32_dot(c, "blz_dot_pair_device32", rows, 2, x, ldx, y, ldy, out, stream);
-}
-
-/* the recombinations of both arities: nz = 1 has a0 and z0 only */
-static int w32_combine(blz_ctx *c, const char *who, int64_t rows, int nterms, const uint32_t *const *x, const int64_t *ldx, int nz,
-		       const uint64_t *const *a0, const uint64_t *const *a1, uint32_t *z0, int64_t ldz0, uint32_t *z1, int64_t ldz1,
-		       void *stream)
-{
-	int rc = w32_begin(c, who, stream, false);
-	if (rc != BLZ_OK)
-		return rc;
-	if (nterms < 1 || nterms > BLZ_MAX_TERMS)
-		return blz_fail(BLZ_EINVAL, "%s: nterms = %d is outside 1..%d", who, nterms, BLZ_MAX_TERMS);
-	if (rows < 0)
-		return blz_fail(BLZ_EINVAL, "%s: rows = %lld is negative", who, (long long)rows);
-	if (!x || !ldx || !a0 || (nz == 2 && !a1))
-		return blz_fail(BLZ_EINVAL, "%s: the array of %s is NULL", who, !x ? "x" : !ldx ? "ldx" : !a0 ? (nz == 2 ? "a0" : "a") : "a1");
-	const uint64_t *const *a[2] = { a0, a1 };
-	uint32_t *z[2] = { z0, z1 };
-	const int64_t ldz[2] = { ldz0, ldz1 };
-	if (nz == 2) {
-		int in[2] = { 0, 0 };
-		for (int t = 0; t < nterms; t++) {
-			if (!a0[t] && !a1[t])
-				return blz_fail(BLZ_EINVAL, "%s: term %d enters neither output (a0[%d] and a1[%d] are both NULL)", who, t, t, t);
-			in[0] += a0[t] != nullptr;
-			in[1] += a1[t] != nullptr;
-		}
-		for (int o = 0; o < 2; o++)
-			if (!in[o])
-				return blz_fail(BLZ_EINVAL, "%s: output z%d has no term (every a%d[t] is NULL)", who, o, o);
-	}
-	const int n = c->un;
-	size_t xb[BLZ_MAX_TERMS] = { 0 }, ab[2][BLZ_MAX_TERMS] = { { 0 } }, zb[2] = { 0, 0 };
-	long long ldl[BLZ_MAX_TERMS] = { 0 };
-	char nm[12], zn[4];
-	for (int t = 0; t < nterms; t++) {
-		snprintf(nm, sizeof nm, "x[%d]", t);
-		if ((rc = w32_check_range(c, who, nm, x[t], rows, ldx[t], &xb[t])) != BLZ_OK)
-			return rc;
-		for (int o = 0; o < nz; o++) {
-			if (nz == 2)
-				snprintf(nm, sizeof nm, "a%d[%d]", o, t);
-			else
-				snprintf(nm, sizeof nm, "a[%d]", t);
-			if (nz == 1 && !a[o][t])
-				return blz_fail(BLZ_EINVAL, "%s: %s is NULL", who, nm);
-			if (a[o][t] && (rc = devio_check_range(c, who, nm, a[o][t], n, n, &ab[o][t])) != BLZ_OK)
-				return rc;
-		}
-		ldl[t] = ldx[t];
-	}
-	for (int o = 0; o < nz; o++) {
-		snprintf(zn, sizeof zn, nz == 2 ? "z%d" : "z", o);
-		if ((rc = w32_check_range(c, who, zn, z[o], rows, ldz[o], &zb[o])) != BLZ_OK)
-			return rc;
-	}
-	if (nz == 2 && rows > 0 && devalg_overlap(z0, zb[0], z1, zb[1]))
-		return blz_fail(BLZ_EINVAL, "%s: z0 overlaps z1", who);
-	for (int o = 0; o < nz; o++) {
-		snprintf(zn, sizeof zn, nz == 2 ? "z%d" : "z", o);
-		for (int t = 0; t < nterms; t++) {
-			const bool in_place = x[t] == z[o] && ldx[t] == ldz[o];
-			if (!in_place && devalg_overlap(z[o], zb[o], x[t], xb[t]))
-				return blz_fail(BLZ_EINVAL, "%s: %s overlaps x[%d] without being it (the in-place form is the same pointer "
-						"and the same stride)", who, zn, t);
-			for (int q = 0; q < nz; q++)
-				if (a[q][t] && devalg_overlap(z[o], zb[o], a[q][t], ab[q][t]))
-					return blz_fail(BLZ_EINVAL, "%s: %s overlaps a coefficient of term %d", who, zn, t);
-		}
-	}
-	if (rows == 0)
-		return BLZ_OK;	/* the outputs have no words */
-	hipStream_t caller = (hipStream_t)stream;
-	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
-		return rc;
-	HIPCHK(launch_w32_combine(c->cfg, n, rows, nterms, x, ldl, nz, a0, a1, z0, ldz0, z1, ldz1, c->stream));
-	return devio_leave(c, caller);
+	return devalg_dot<uint32_t>(c, "blz_dot_pair_device32", rows, 2, x, ldx, y, ldy, out, stream);
 }
 
 extern "C" int blz_combine_device32(blz_ctx *c, int64_t rows, int nterms, const uint32_t *const *x, const int64_t *ldx,
 				    const uint64_t *const *a, uint32_t *z, int64_t ldz, void *stream)
 {
-	return w32_combine(c, "blz_combine_device32", rows, nterms, x, ldx, 1, a, nullptr, z, ldz, nullptr, 0, stream);
+	return devalg_combine<uint32_t>(c, "blz_combine_device32", rows, nterms, x, ldx, 1, a, nullptr, z, ldz, nullptr, 0, stream);
 }
 
 extern "C" int blz_combine_pair_device32(blz_ctx *c, int64_t rows, int nterms, const uint32_t *const *x, const int64_t *ldx,
 					 const uint64_t *const *a0, const uint64_t *const *a1, uint32_t *z0, int64_t ldz0, uint32_t *z1,
 					 int64_t ldz1, void *stream)
 {
-	return w32_combine(c, "blz_combine_pair_device32", rows, nterms, x, ldx, 2, a0, a1, z0, ldz0, z1, ldz1, stream);
+	return devalg_combine(c, "blz_combine_pair_device32", rows, nterms, x, ldx, 2, a0, a1, z0, ldz0, z1, ldz1, stream);
 }
+

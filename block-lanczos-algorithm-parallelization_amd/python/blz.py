@@ -974,7 +974,8 @@ class Context:
             return int(torch.cuda.current_stream(self.device).cuda_stream)
         return int(getattr(stream, "cuda_stream", stream))
 
-    def _new_block(self, rows):
+    def _new_block(self, rows, like=None):
+        """a block the wrapper allocates: torch.uint64 whatever `like` is (_new_block32 takes its dtype from it)"""
         import torch
         return torch.empty((rows, self.n), dtype=torch.uint64, device=f"cuda:{self.device}")
 
@@ -1022,26 +1023,108 @@ class Context:
                                          C.c_void_p(self._stream(stream))))
         return whole
 
+    # ---- what a method and its ...32 namesake share: `read` is device_block or device_block32, `new` the allocator of a block
+    # the wrapper makes (_new_block or _new_block32: rows, and the block whose dtype a 32-bit one takes), `fn` the C function
+
+    def _dev_set(self, read, fn, block, t, validate, stream):
+        rows = self._block_rows(block) if 0 <= block <= 3 else None
+        p, _, ld, _ = read(t, self.n, rows, self.device)
+        bad = C.c_int64(-1)
+        check(fn(self.h, C.c_int(block), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream)),
+                 C.byref(bad) if validate else None))
+        return int(bad.value) if validate else None
+
+    def _dev_get(self, read, new, fn, block, out, stream):
+        rows = self._block_rows(block) if 0 <= block <= 3 else None
+        if out is None:
+            out = new(rows if rows is not None else 1)
+        p, _, ld, _ = read(out, self.n, rows, self.device)
+        check(fn(self.h, C.c_int(block), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream))))
+        return out
+
+    def _dev_apply(self, read, new, fn, transpose, x, out, stream):
+        xr, yr = self.apply_rows(transpose)
+        px, _, ldx, _ = read(x, self.n, xr, self.device)
+        if out is None:
+            out = new(yr, x)
+        py, _, ldy, _ = read(out, self.n, yr, self.device)
+        check(fn(self.h, C.c_int(int(bool(transpose))), C.c_void_p(px), C.c_int64(ldx), C.c_void_p(py), C.c_int64(ldy),
+                 C.c_void_p(self._stream(stream))))
+        return out
+
+    def _dev_apply_pair(self, read, new, fn, transpose_first, x, out, mid, stream):
+        xr, yr = self.apply_rows(transpose_first)
+        px, _, ldx, _ = read(x, self.n, xr, self.device)
+        if out is None:
+            out = new(xr, x)
+        pz, _, ldz, _ = read(out, self.n, xr, self.device)
+        if mid is True:
+            mid = new(yr, x)
+        py, ldy = None, 0
+        if mid is not None:
+            py, _, ldy, _ = read(mid, self.n, yr, self.device)
+        check(fn(self.h, C.c_int(int(bool(transpose_first))), C.c_void_p(px), C.c_int64(ldx), C.c_void_p(py), C.c_int64(ldy),
+                 C.c_void_p(pz), C.c_int64(ldz), C.c_void_p(self._stream(stream))))
+        return out if mid is None else (out, mid)
+
+    def _dev_dot(self, read, fn, xs, y, out, stream):
+        """x^T y for each x of xs, one or two: out is (n, n) for one, (2, n, n) for two"""
+        rows, args = None, []
+        for x in xs + (y,):
+            px, rows, ldx, _ = read(x, self.n, rows, self.device)
+            args += [C.c_void_p(px), C.c_int64(ldx)]
+        if out is None:
+            out = self._empty((self.n, self.n) if len(xs) == 1 else (2, self.n, self.n))
+        pc = device_square(out, self.n, self.device) if len(xs) == 1 else device_pair(out, self.n, self.device)
+        check(fn(self.h, C.c_int64(rows), *args, C.c_void_p(pc), C.c_void_p(self._stream(stream))))
+        return out
+
+    def _dev_combine(self, read, new, fn, terms, out, stream):
+        terms = list(terms)
+        if not 1 <= len(terms) <= MAX_TERMS:
+            raise ValueError(f"combine: {len(terms)} terms, not 1..{MAX_TERMS}")
+        terms = [(pair[0], self._coefficient(pair[1], stream)) for pair in terms]
+        rows, args = device_terms(terms, self.n, self.device, read)
+        if out is None:
+            out = new(rows, terms[0][0])
+        pz, _, ldz, _ = read(out, self.n, rows, self.device)
+        k = len(args)
+        xs = (C.c_void_p * k)(*[a[0] for a in args])
+        lds = (C.c_int64 * k)(*[a[1] for a in args])
+        cs = (C.c_void_p * k)(*[a[2] for a in args])
+        check(fn(self.h, C.c_int64(rows), C.c_int(k), xs, lds, cs, C.c_void_p(pz), C.c_int64(ldz),
+                 C.c_void_p(self._stream(stream))))
+        return out
+
+    def _dev_combine_pair(self, read, new, fn, terms, out, stream):
+        terms = [tuple(t) for t in terms]
+        if not 1 <= len(terms) <= MAX_TERMS:
+            raise ValueError(f"combine_pair: {len(terms)} terms, not 1..{MAX_TERMS}")
+        terms = [t if len(t) != 3 else (t[0],) + tuple(None if a is None else self._coefficient(a, stream) for a in t[1:])
+                 for t in terms]
+        rows, args = device_pair_terms(terms, self.n, self.device, read)
+        if out is None:
+            out = (new(rows, terms[0][0]), new(rows, terms[0][0]))
+        (pz0, ldz0), (pz1, ldz1) = device_pair_out(out, self.n, rows, self.device, read)
+        k = len(args)
+        xs = (C.c_void_p * k)(*[a[0] for a in args])
+        lds = (C.c_int64 * k)(*[a[1] for a in args])
+        c0 = (C.c_void_p * k)(*[a[2] for a in args])
+        c1 = (C.c_void_p * k)(*[a[3] for a in args])
+        check(fn(self.h, C.c_int64(rows), C.c_int(k), xs, lds, c0, c1, C.c_void_p(pz0), C.c_int64(ldz0), C.c_void_p(pz1),
+                 C.c_int64(ldz1), C.c_void_p(self._stream(stream))))
+        return out[0], out[1]
+
     def set_block_device(self, block, t, validate=False, stream=None):
         """blz_set_block_device(): block <- the tensor t, (rows(block), n) with strides (ld, 1) or flat, ordered on `stream`
         (default: torch's current stream) without a host synchronisation.  validate=True counts the words that are not
         below p (synchronises) and returns the count, 0; a count that is not 0 raises BlzError(EINVAL) with it.
         (With device_ranks() the tensor is the rank's own rows, here and in get_block_device.)"""
-        rows = self._block_rows(block) if 0 <= block <= 3 else None
-        p, _, ld, _ = device_block(t, self.n, rows, self.device)
-        bad = C.c_int64(-1)
-        check(lib().blz_set_block_device(self.h, C.c_int(block), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream)),
-                                         C.byref(bad) if validate else None))
-        return int(bad.value) if validate else None
+        return self._dev_set(device_block, lib().blz_set_block_device, block, t, validate, stream)
 
     def get_block_device(self, block, out=None, stream=None):
         """blz_get_block_device(): the block as a tensor on the device (out, or a new (rows, n) torch.uint64 one)."""
-        rows = self._block_rows(block) if 0 <= block <= 3 else None
-        if out is None:
-            out = self._new_block(rows if rows is not None else 1)
-        p, _, ld, _ = device_block(out, self.n, rows, self.device)
-        check(lib().blz_get_block_device(self.h, C.c_int(block), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream))))
-        return out
+        return self._dev_get(device_block, self._new_block, lib().blz_get_block_device, block, out, stream)
 
     def apply_rows(self, transpose):
         """blz_apply_rows(): (rows of x, rows of y) of y = M x (transpose False) / M^T x."""
@@ -1052,14 +1135,7 @@ class Context:
     def apply(self, transpose, x, out=None, stream=None):
         """blz_apply_device(): out = M x (transpose False) / M^T x on tensors of the context's device, ordered on `stream`;
         the blocks and the state of a solve are left alone.  Returns out (a new torch.uint64 tensor when not given)."""
-        xr, yr = self.apply_rows(transpose)
-        px, _, ldx, _ = device_block(x, self.n, xr, self.device)
-        if out is None:
-            out = self._new_block(yr)
-        py, _, ldy, _ = device_block(out, self.n, yr, self.device)
-        check(lib().blz_apply_device(self.h, C.c_int(int(bool(transpose))), C.c_void_p(px), C.c_int64(ldx), C.c_void_p(py),
-                                     C.c_int64(ldy), C.c_void_p(self._stream(stream))))
-        return out
+        return self._dev_apply(device_block, self._new_block, lib().blz_apply_device, transpose, x, out, stream)
 
     def apply_release(self):
         """blz_apply_release(): free the two scratch slabs apply() works in (they come back on the next call)."""
@@ -1084,35 +1160,13 @@ class Context:
     def dot(self, x, y, out=None, stream=None):
         """blz_dot_device(): out = x^T y mod p, an (n, n) torch.uint64 tensor on the device (out, or a new one); x and y are
         blocks of the same number of rows (any, 0 included), `x is y` gives the Gram matrix.  Ordered on `stream`."""
-        px, rows, ldx, _ = device_block(x, self.n, None, self.device)
-        py, _, ldy, _ = device_block(y, self.n, rows, self.device)
-        if out is None:
-            import torch
-            out = torch.empty((self.n, self.n), dtype=torch.uint64, device=f"cuda:{self.device}")
-        pc = device_square(out, self.n, self.device)
-        check(lib().blz_dot_device(self.h, C.c_int64(rows), C.c_void_p(px), C.c_int64(ldx), C.c_void_p(py), C.c_int64(ldy),
-                                   C.c_void_p(pc), C.c_void_p(self._stream(stream))))
-        return out
+        return self._dev_dot(device_block, lib().blz_dot_device, (x,), y, out, stream)
 
     def combine(self, terms, out=None, stream=None):
         """blz_combine_device(): out = sum of X @ A mod p over the 1..4 pairs (X, A) of `terms`, row by row.  X: blocks of the
         same number of rows; A: (n, n) tensors on the device, or numpy arrays / nested lists of residues, which are moved
         there on `stream`.  out: a new (rows, n) torch.uint64 tensor, the caller's, or one of the X (the in-place form)."""
-        terms = list(terms)
-        if not 1 <= len(terms) <= MAX_TERMS:
-            raise ValueError(f"combine: {len(terms)} terms, not 1..{MAX_TERMS}")
-        terms = [(pair[0], self._coefficient(pair[1], stream)) for pair in terms]
-        rows, args = device_terms(terms, self.n, self.device)
-        if out is None:
-            out = self._new_block(rows)
-        pz, _, ldz, _ = device_block(out, self.n, rows, self.device)
-        k = len(args)
-        xs = (C.c_void_p * k)(*[a[0] for a in args])
-        lds = (C.c_int64 * k)(*[a[1] for a in args])
-        cs = (C.c_void_p * k)(*[a[2] for a in args])
-        check(lib().blz_combine_device(self.h, C.c_int64(rows), C.c_int(k), xs, lds, cs, C.c_void_p(pz), C.c_int64(ldz),
-                                       C.c_void_p(self._stream(stream))))
-        return out
+        return self._dev_combine(device_block, self._new_block, lib().blz_combine_device, terms, out, stream)
 
     # ---- fused device calls: op2 (op1 x), two inner products against one block, two recombinations of shared inputs
 
@@ -1120,57 +1174,20 @@ class Context:
         """blz_apply_pair_device(): z = M^T (M x) (transpose_first False) / M (M^T x) in one call.  Returns z (out, or a new
         torch.uint64 tensor; out=x is the in-place form).  mid=True allocates the intermediate, a tensor for mid receives
         it; either way the return is (z, mid).  mid=None: the intermediate never leaves the library's scratch."""
-        xr, yr = self.apply_rows(transpose_first)
-        px, _, ldx, _ = device_block(x, self.n, xr, self.device)
-        if out is None:
-            out = self._new_block(xr)
-        pz, _, ldz, _ = device_block(out, self.n, xr, self.device)
-        if mid is True:
-            mid = self._new_block(yr)
-        py, ldy = None, 0
-        if mid is not None:
-            py, _, ldy, _ = device_block(mid, self.n, yr, self.device)
-        check(lib().blz_apply_pair_device(self.h, C.c_int(int(bool(transpose_first))), C.c_void_p(px), C.c_int64(ldx),
-                                          C.c_void_p(py), C.c_int64(ldy), C.c_void_p(pz), C.c_int64(ldz),
-                                          C.c_void_p(self._stream(stream))))
-        return out if mid is None else (out, mid)
+        return self._dev_apply_pair(device_block, self._new_block, lib().blz_apply_pair_device, transpose_first, x, out, mid,
+                                    stream)
 
     def dot_pair(self, x0, x1, y, out=None, stream=None):
         """blz_dot_pair_device(): out[0] = x0^T y and out[1] = x1^T y mod p in one pass, a contiguous (2, n, n) torch.uint64
         tensor on the device (out, or a new one) whose two views go straight into ortho_coeffs.  Blocks that are the same
         tensor are read once."""
-        px0, rows, ldx0, _ = device_block(x0, self.n, None, self.device)
-        px1, _, ldx1, _ = device_block(x1, self.n, rows, self.device)
-        py, _, ldy, _ = device_block(y, self.n, rows, self.device)
-        if out is None:
-            out = self._empty((2, self.n, self.n))
-        pc = device_pair(out, self.n, self.device)
-        check(lib().blz_dot_pair_device(self.h, C.c_int64(rows), C.c_void_p(px0), C.c_int64(ldx0), C.c_void_p(px1),
-                                        C.c_int64(ldx1), C.c_void_p(py), C.c_int64(ldy), C.c_void_p(pc),
-                                        C.c_void_p(self._stream(stream))))
-        return out
+        return self._dev_dot(device_block, lib().blz_dot_pair_device, (x0, x1), y, out, stream)
 
     def combine_pair(self, terms, out=None, stream=None):
         """blz_combine_pair_device(): (z0, z1) with z0 = sum of X @ A0 and z1 = sum of X @ A1 mod p over the 1..4 triples
         (X, A0, A1) of `terms`, every X read once; A0 or A1 may be None (the term does not enter that output).  Coefficients
         as in combine().  out: (z0, z1), each a new block, the caller's, or one of the X (the in-place form), or None."""
-        terms = [tuple(t) for t in terms]
-        if not 1 <= len(terms) <= MAX_TERMS:
-            raise ValueError(f"combine_pair: {len(terms)} terms, not 1..{MAX_TERMS}")
-        terms = [t if len(t) != 3 else (t[0],) + tuple(None if a is None else self._coefficient(a, stream) for a in t[1:])
-                 for t in terms]
-        rows, args = device_pair_terms(terms, self.n, self.device)
-        if out is None:
-            out = (self._new_block(rows), self._new_block(rows))
-        (pz0, ldz0), (pz1, ldz1) = device_pair_out(out, self.n, rows, self.device)
-        k = len(args)
-        xs = (C.c_void_p * k)(*[a[0] for a in args])
-        lds = (C.c_int64 * k)(*[a[1] for a in args])
-        c0 = (C.c_void_p * k)(*[a[2] for a in args])
-        c1 = (C.c_void_p * k)(*[a[3] for a in args])
-        check(lib().blz_combine_pair_device(self.h, C.c_int64(rows), C.c_int(k), xs, lds, c0, c1, C.c_void_p(pz0),
-                                            C.c_int64(ldz0), C.c_void_p(pz1), C.c_int64(ldz1), C.c_void_p(self._stream(stream))))
-        return out[0], out[1]
+        return self._dev_combine_pair(device_block, self._new_block, lib().blz_combine_pair_device, terms, out, stream)
 
     # ---- 32-bit device blocks: the methods above on torch.uint32 / torch.int32 tensors, for contexts with word_bytes == 4
     # (p < 2**32).  A block the wrapper allocates takes the dtype of the first block passed in (torch.uint32 where there is
@@ -1183,113 +1200,38 @@ class Context:
 
     def set_block_device32(self, block, t, validate=False, stream=None):
         """blz_set_block_device32(): set_block_device() from a tensor of 32-bit words."""
-        rows = self.rows(block) if 0 <= block <= 3 else None
-        p, _, ld, _ = device_block32(t, self.n, rows, self.device)
-        bad = C.c_int64(-1)
-        check(lib().blz_set_block_device32(self.h, C.c_int(block), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream)),
-                                           C.byref(bad) if validate else None))
-        return int(bad.value) if validate else None
+        return self._dev_set(device_block32, lib().blz_set_block_device32, block, t, validate, stream)
 
     def get_block_device32(self, block, out=None, stream=None):
         """blz_get_block_device32(): the block as a tensor of 32-bit words (out, or a new (rows, n) torch.uint32 one)."""
-        rows = self.rows(block) if 0 <= block <= 3 else None
-        if out is None:
-            out = self._new_block32(rows if rows is not None else 1)
-        p, _, ld, _ = device_block32(out, self.n, rows, self.device)
-        check(lib().blz_get_block_device32(self.h, C.c_int(block), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream))))
-        return out
+        return self._dev_get(device_block32, self._new_block32, lib().blz_get_block_device32, block, out, stream)
 
     def apply32(self, transpose, x, out=None, stream=None):
         """blz_apply_device32(): apply() on tensors of 32-bit words.  Returns out (a new tensor of x's dtype when not given)."""
-        xr, yr = self.apply_rows(transpose)
-        px, _, ldx, _ = device_block32(x, self.n, xr, self.device)
-        if out is None:
-            out = self._new_block32(yr, x)
-        py, _, ldy, _ = device_block32(out, self.n, yr, self.device)
-        check(lib().blz_apply_device32(self.h, C.c_int(int(bool(transpose))), C.c_void_p(px), C.c_int64(ldx), C.c_void_p(py),
-                                       C.c_int64(ldy), C.c_void_p(self._stream(stream))))
-        return out
+        return self._dev_apply(device_block32, self._new_block32, lib().blz_apply_device32, transpose, x, out, stream)
 
     def apply_pair32(self, transpose_first, x, out=None, mid=None, stream=None):
         """blz_apply_pair_device32(): apply_pair() on tensors of 32-bit words; out, mid and the return as there."""
-        xr, yr = self.apply_rows(transpose_first)
-        px, _, ldx, _ = device_block32(x, self.n, xr, self.device)
-        if out is None:
-            out = self._new_block32(xr, x)
-        pz, _, ldz, _ = device_block32(out, self.n, xr, self.device)
-        if mid is True:
-            mid = self._new_block32(yr, x)
-        py, ldy = None, 0
-        if mid is not None:
-            py, _, ldy, _ = device_block32(mid, self.n, yr, self.device)
-        check(lib().blz_apply_pair_device32(self.h, C.c_int(int(bool(transpose_first))), C.c_void_p(px), C.c_int64(ldx),
-                                            C.c_void_p(py), C.c_int64(ldy), C.c_void_p(pz), C.c_int64(ldz),
-                                            C.c_void_p(self._stream(stream))))
-        return out if mid is None else (out, mid)
+        return self._dev_apply_pair(device_block32, self._new_block32, lib().blz_apply_pair_device32, transpose_first, x, out,
+                                    mid, stream)
 
     def dot32(self, x, y, out=None, stream=None):
         """blz_dot_device32(): dot() of two blocks of 32-bit words; out is (n, n) torch.uint64, as there."""
-        px, rows, ldx, _ = device_block32(x, self.n, None, self.device)
-        py, _, ldy, _ = device_block32(y, self.n, rows, self.device)
-        if out is None:
-            out = self._empty((self.n, self.n))
-        pc = device_square(out, self.n, self.device)
-        check(lib().blz_dot_device32(self.h, C.c_int64(rows), C.c_void_p(px), C.c_int64(ldx), C.c_void_p(py), C.c_int64(ldy),
-                                     C.c_void_p(pc), C.c_void_p(self._stream(stream))))
-        return out
+        return self._dev_dot(device_block32, lib().blz_dot_device32, (x,), y, out, stream)
 
     def dot_pair32(self, x0, x1, y, out=None, stream=None):
         """blz_dot_pair_device32(): dot_pair() of blocks of 32-bit words; out is (2, n, n) torch.uint64, as there."""
-        px0, rows, ldx0, _ = device_block32(x0, self.n, None, self.device)
-        px1, _, ldx1, _ = device_block32(x1, self.n, rows, self.device)
-        py, _, ldy, _ = device_block32(y, self.n, rows, self.device)
-        if out is None:
-            out = self._empty((2, self.n, self.n))
-        pc = device_pair(out, self.n, self.device)
-        check(lib().blz_dot_pair_device32(self.h, C.c_int64(rows), C.c_void_p(px0), C.c_int64(ldx0), C.c_void_p(px1),
-                                          C.c_int64(ldx1), C.c_void_p(py), C.c_int64(ldy), C.c_void_p(pc),
-                                          C.c_void_p(self._stream(stream))))
-        return out
+        return self._dev_dot(device_block32, lib().blz_dot_pair_device32, (x0, x1), y, out, stream)
 
     def combine32(self, terms, out=None, stream=None):
         """blz_combine_device32(): combine() on blocks of 32-bit words.  The coefficients are what combine() takes ((n, n)
         uint64 / int64 tensors, numpy arrays, nested lists); out: a new block of the first X's dtype, the caller's, or one
         of the X (the in-place form)."""
-        terms = list(terms)
-        if not 1 <= len(terms) <= MAX_TERMS:
-            raise ValueError(f"combine: {len(terms)} terms, not 1..{MAX_TERMS}")
-        terms = [(pair[0], self._coefficient(pair[1], stream)) for pair in terms]
-        rows, args = device_terms(terms, self.n, self.device, device_block32)
-        if out is None:
-            out = self._new_block32(rows, terms[0][0])
-        pz, _, ldz, _ = device_block32(out, self.n, rows, self.device)
-        k = len(args)
-        xs = (C.c_void_p * k)(*[a[0] for a in args])
-        lds = (C.c_int64 * k)(*[a[1] for a in args])
-        cs = (C.c_void_p * k)(*[a[2] for a in args])
-        check(lib().blz_combine_device32(self.h, C.c_int64(rows), C.c_int(k), xs, lds, cs, C.c_void_p(pz), C.c_int64(ldz),
-                                         C.c_void_p(self._stream(stream))))
-        return out
+        return self._dev_combine(device_block32, self._new_block32, lib().blz_combine_device32, terms, out, stream)
 
     def combine_pair32(self, terms, out=None, stream=None):
         """blz_combine_pair_device32(): combine_pair() on blocks of 32-bit words; terms, out and the return as there."""
-        terms = [tuple(t) for t in terms]
-        if not 1 <= len(terms) <= MAX_TERMS:
-            raise ValueError(f"combine_pair: {len(terms)} terms, not 1..{MAX_TERMS}")
-        terms = [t if len(t) != 3 else (t[0],) + tuple(None if a is None else self._coefficient(a, stream) for a in t[1:])
-                 for t in terms]
-        rows, args = device_pair_terms(terms, self.n, self.device, device_block32)
-        if out is None:
-            out = (self._new_block32(rows, terms[0][0]), self._new_block32(rows, terms[0][0]))
-        (pz0, ldz0), (pz1, ldz1) = device_pair_out(out, self.n, rows, self.device, device_block32)
-        k = len(args)
-        xs = (C.c_void_p * k)(*[a[0] for a in args])
-        lds = (C.c_int64 * k)(*[a[1] for a in args])
-        c0 = (C.c_void_p * k)(*[a[2] for a in args])
-        c1 = (C.c_void_p * k)(*[a[3] for a in args])
-        check(lib().blz_combine_pair_device32(self.h, C.c_int64(rows), C.c_int(k), xs, lds, c0, c1, C.c_void_p(pz0),
-                                              C.c_int64(ldz0), C.c_void_p(pz1), C.c_int64(ldz1), C.c_void_p(self._stream(stream))))
-        return out[0], out[1]
+        return self._dev_combine_pair(device_block32, self._new_block32, lib().blz_combine_pair_device32, terms, out, stream)
 
     # ---- device small algebra: the n x n chain of a Krylov step and the echelon form of a block, results on the device
 

@@ -792,7 +792,7 @@ def test_refusals_launch_nothing(monkeypatch):
         refused(raw_dot2(ctx, n, X, n, Cc, n, Y, n, Cc), "c overlaps x1")
         refused(raw_combine(ctx, rows, [Bp, Y], [n, n], [A, A], Bp + 4 * n, n), "z overlaps x[0]")      # a row on
         refused(raw_combine(ctx, half, [Bp, Y], [n, n], [A, A], Bp, 2 * n), "z overlaps x[0]")           # another stride
-        refused(raw_combine(ctx, n, [X], [n], [Bp], Bp, n), "z overlaps a coefficient")
+        refused(raw_combine(ctx, n, [X], [n], [Bp], Bp, n), "z overlaps a[0]")
         refused(raw_combine2(ctx, rows, [X, Y], [n, n], [A, A], [A, A], Bp, n, Bp + 4 * n * (rows - 1), n), "z0 overlaps z1")
         refused(raw_combine2(ctx, rows, [X, Y], [n, n], [A, A], [A, A], X, n, X, n), "z0 overlaps z1")
         refused(raw_combine2(ctx, half, [X, Bp], [n, n], [A, A], [A, A], Z, n, Bp, 2 * n), "z1 overlaps x[1]")
