@@ -42,6 +42,7 @@
 #include "blz_devrank.h"
 #include "blz_devw32.h"
 #include "blz_devmat.h"
+#include "blz_devrhs.h"
 
 #define HIPCHK(expr)                                                                                     \
 	do {                                                                                             \
@@ -2713,12 +2714,12 @@ static int solution_residual(blz_ctx *c, int *nonzero)
 
 static inline uint64_t host_mulmod(uint64_t a, uint64_t b, uint64_t p) { return (uint64_t)((unsigned __int128)a * b % p); }
 
-extern "C" int blz_solution_block(blz_ctx *c, uint64_t *x, int *status)
+/* What blz_solution_block and blz_solution_device share, everything but the way x leaves the slab: the kernel basis, the small
+ * elimination on the host, V <- V * C and the verification product.  status[0..k) as blz_solution_block documents them;
+ * *verified = the residual is zero, and then column i of V is (y_i, -e_i) where status[i] == 0 and zero where it is 1. */
+static int solution_block_reduce(blz_ctx *c, int *status, bool *verified)
 {
-	NEED_MATRIX(c);
-	if (!c->rhs || !x || !status)
-		return blz_fail(BLZ_EINVAL, "blz_solution_block: %s",
-				!c->rhs ? "the context has no right-hand side (blz_set_matrix_rhs_block)" : "NULL argument");
+	*verified = false;
 	const int n = c->un, np = c->cfg.n, k = c->rhs_k > 1 ? c->rhs_k : 1;
 	const u64 p = c->prime;
 	int kb = 0;
@@ -2786,6 +2787,21 @@ extern "C" int blz_solution_block(blz_ctx *c, uint64_t *x, int *status)
 			status[i] = 2;
 		return BLZ_OK;
 	}
+	*verified = true;
+	return BLZ_OK;
+}
+
+extern "C" int blz_solution_block(blz_ctx *c, uint64_t *x, int *status)
+{
+	NEED_MATRIX(c);
+	if (!c->rhs || !x || !status)
+		return blz_fail(BLZ_EINVAL, "blz_solution_block: %s",
+				!c->rhs ? "the context has no right-hand side (blz_set_matrix_rhs_block)" : "NULL argument");
+	const int n = c->un, k = c->rhs_k > 1 ? c->rhs_k : 1;
+	bool verified = false;
+	int rc = solution_block_reduce(c, status, &verified);
+	if (rc != BLZ_OK || !verified)
+		return rc;
 	std::vector<uint64_t> v((size_t)c->glob_rows[0] * n);
 	if ((rc = blz_get_block(c, BLZ_V, v.data())) != BLZ_OK)
 		return rc;
@@ -3268,7 +3284,7 @@ static int devrank_dot_buffers(blz_ctx *c)
 
 /* the look-up the two checks below share: `bytes` from ptr on lie inside ONE allocation of the context's device */
 static int devio_check_alloc(const blz_ctx *c, const char *who, const char *arg, const void *ptr, size_t bytes, int64_t rows,
-			     int64_t ld)
+			     int64_t ld, int width = 0)	/* (width: the k words per row of a right-hand side or a solution) */
 {
 	hipPointerAttribute_t at;
 	memset(&at, 0, sizeof at);
@@ -3288,8 +3304,9 @@ static int devio_check_alloc(const blz_ctx *c, const char *who, const char *arg,
 	}
 	const size_t off = (size_t)((const char *)ptr - (const char *)base);
 	if (off > size || bytes > size - off)
-		return blz_fail(BLZ_EINVAL, "%s: %s needs %zu bytes (%lld rows, row stride %lld, n = %d) but its allocation ends after %zu",
-				who, arg, bytes, (long long)rows, (long long)ld, c->un, off > size ? (size_t)0 : size - off);
+		return blz_fail(BLZ_EINVAL, "%s: %s needs %zu bytes (%lld rows, row stride %lld, %s = %d) but its allocation ends after %zu",
+				who, arg, bytes, (long long)rows, (long long)ld, width > 0 ? "k" : "n", width > 0 ? width : c->un,
+				off > size ? (size_t)0 : size - off);
 	return BLZ_OK;
 }
 
@@ -3302,13 +3319,14 @@ static int devio_check_alloc(const blz_ctx *c, const char *who, const char *arg,
  * The size limits are each width's own: rows and stride at most 2^40 for 8-byte words, the byte count at most 2^62 for 4-byte
  * ones (whose callers have refused a negative row count before they come here). */
 static int devio_check_range(const blz_ctx *c, const char *who, const char *arg, const void *ptr, int64_t rows, int64_t ld,
-			     size_t *bytes_out, int word = 8)
+			     size_t *bytes_out, int word = 8, int width = 0)
 {
-	const int n = c->un;
+	const int n = width > 0 ? width : c->un;	/* (width: the k words per row of a right-hand side or a solution) */
 	if (!ptr && rows != 0)
 		return blz_fail(BLZ_EINVAL, "%s: %s is NULL", who, arg);
 	if (ld < n)
-		return blz_fail(BLZ_EINVAL, "%s: the row stride of %s is %lld words, less than n = %d", who, arg, (long long)ld, n);
+		return blz_fail(BLZ_EINVAL, "%s: the row stride of %s is %lld words, less than %s = %d", who, arg, (long long)ld,
+				width > 0 ? "k" : "n", n);
 	if (((uintptr_t)ptr & (uintptr_t)(word - 1)) != 0)
 		return blz_fail(BLZ_EINVAL, "%s: %s is not aligned to %d bytes", who, arg, word);
 	if (rows < 0 || (word == 8 && (rows > ((int64_t)1 << 40) || ld > ((int64_t)1 << 40))))
@@ -3323,7 +3341,7 @@ static int devio_check_range(const blz_ctx *c, const char *who, const char *arg,
 		return blz_fail(BLZ_EINVAL, "%s: %s of %lld rows with a row stride of %lld words leaves 64-bit byte offsets", who, arg,
 				(long long)rows, (long long)ld);
 	const size_t bytes = (size_t)wide;
-	const int rc = devio_check_alloc(c, who, arg, ptr, bytes, rows, ld);
+	const int rc = devio_check_alloc(c, who, arg, ptr, bytes, rows, ld, width);
 	if (rc != BLZ_OK)
 		return rc;
 	if (bytes_out)
@@ -4372,5 +4390,168 @@ extern "C" int blz_combine_pair_device32(blz_ctx *c, int64_t rows, int nterms, c
 					 int64_t ldz1, void *stream)
 {
 	return devalg_combine(c, "blz_combine_pair_device32", rows, nterms, x, ldx, 2, a0, a1, z0, ldz0, z1, ldz1, stream);
+}
+
+/* ---- device right-hand sides: b from device memory into the border, the solution from the slab into device memory (kernels:
+ * blz_devrhs.hip).  A plain single rank only.  Written once for both word widths of the caller's block,
+ * like the device blocks above. ---- */
+
+/* what both calls refuse before they look at an argument: the family's refusals, and device blocks on ranks (which the 64-bit
+ * device blocks welcome: the border of this path is not distributed) */
+static int devrhs_begin(blz_ctx *c, const char *who, int word, void *stream)
+{
+	if (c && c->device_ranks)
+		return blz_fail(BLZ_EINVAL, "%s: a device right-hand side needs a plain single rank, and device blocks on ranks are "
+				"switched on (blz_set_device_ranks)", who);
+	return devio_begin(c, who, word, true, stream);
+}
+
+template <typename W>
+static int devrhs_set(blz_ctx *c, const char *who, int k, const W *b, int64_t ldb, void *stream)
+{
+	int rc = devrhs_begin(c, who, sizeof(W), stream);
+	if (rc != BLZ_OK || (rc = rhs_block_refuse_k(c, who, k)) != BLZ_OK)
+		return rc;
+	if (c->csr[0].size() != 1 || c->csr[1].size() != 1 || c->short_side[0] || c->short_side[1] || c->glob_rows[0] < k)
+		return blz_fail(BLZ_EINVAL, "%s: the matrix was not set for a single rank in one piece", who);
+	const int64_t first = c->glob_rows[0] - k, len = c->glob_rows[1];
+	if ((rc = devio_check_range(c, who, "b", b, len, ldb, nullptr, sizeof(W), k)) != BLZ_OK)
+		return rc;
+	HIPCHK(hipStreamSynchronize(c->stream));
+	const int kp = k > 1 ? border_kp(k) : 0, kw = k > 1 ? kp : 1;
+	std::vector<int64_t> rows((size_t)k);
+	{	/* the k border rows / columns of the matrix itself must be empty: the product whose rows live on side 0 says so */
+		const DevCsr &A = c->csr[c->row_side[0] == 0 ? 0 : 1][0];
+		if (A.rows != c->glob_rows[0])
+			return blz_fail(BLZ_EINVAL, "%s: unexpected slab shape", who);
+		for (int i = 0; i < k; i++) {
+			u32 rp[2] = { 0, 0 };
+			rows[(size_t)i] = c->perm[0].empty() ? first + i : c->perm[0][(size_t)(first + i)];
+			HIPCHK(hipMemcpy(rp, A.row_ptr + rows[(size_t)i], sizeof rp, hipMemcpyDeviceToHost));
+			if (rp[0] != rp[1] && k == 1)
+				return blz_fail(BLZ_EINVAL, "%s: the last %s of the matrix must be empty (it stands for the right-hand side)",
+						who, c->right ? "column" : "row");
+			if (rp[0] != rp[1])
+				return blz_fail(BLZ_EINVAL, "%s: the last %d %s of the matrix must be empty (they stand for the right-hand "
+						"sides)", who, k, c->right ? "columns" : "rows");
+		}
+	}
+	/* the import goes into a fresh buffer, zero filled like the host's: the border that is resident applies until the count
+	 * has been read as zero */
+	DevmatTmp tmp;
+	void *fresh = nullptr;
+	const size_t fresh_bytes = (size_t)std::max<int64_t>(len, 1) * kw * c->cfg.word;
+	HIPCHK(tmp.alloc(&fresh, fresh_bytes));
+	if (!c->bad_dev)
+		HIPCHK(hipMalloc((void **)&c->bad_dev, sizeof(unsigned long long)));
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_enter(c, caller)) != BLZ_OK)
+		return rc;
+	unsigned long long cnt = 0;
+	{
+		/* (from the first enqueue on nothing returns before the stream has drained: `fresh` is freed on the way out) */
+		hipError_t e = hipMemsetAsync(c->bad_dev, 0, sizeof(unsigned long long), c->stream);
+		if (e == hipSuccess && len == 0)
+			e = hipMemsetAsync(fresh, 0, fresh_bytes, c->stream);
+		if (e == hipSuccess)
+			e = launch_rhs_import<W>(c->cfg, fresh, b, ldb, c->inv_dev[1], len, k, kp, c->bad_dev, c->stream);
+		rc = e == hipSuccess ? devio_leave(c, caller) : BLZ_OK;
+		const hipError_t e2 = hipStreamSynchronize(c->stream);
+		HIPCHK(e);
+		HIPCHK(e2);
+		if (rc != BLZ_OK)
+			return rc;
+		HIPCHK(hipMemcpy(&cnt, c->bad_dev, sizeof cnt, hipMemcpyDeviceToHost));
+	}
+	if (cnt)
+		return blz_fail(BLZ_EINVAL, "%s: %llu words of b are not below p", who, cnt);
+	/* what the host calls leave behind, in their order: everything that can fail first, then the swap */
+	if (k == 1) {
+		if (!c->border_partial)
+			HIPCHK(hipMalloc(&c->border_partial, (size_t)border_dot_max_blocks(c->cfg) * BLZ_BORDER_MAXN * sizeof(u64)));
+	} else {
+		const size_t need = (size_t)border_dot_max_blocks(c->cfg) * kp * BLZ_BORDER_MAXN;
+		if (c->border_partial_words < need) {
+			if (c->border_partial)
+				hipFree(c->border_partial);
+			c->border_partial = nullptr;
+			c->border_partial_words = 0;
+			HIPCHK(hipMalloc(&c->border_partial, need * sizeof(u64)));
+			c->border_partial_words = need;
+		}
+		if (!c->border_rows_dev)
+			HIPCHK(hipMalloc(&c->border_rows_dev, BLZ_MAX_RHS * sizeof(long long)));
+		long long dev_rows[BLZ_MAX_RHS] = { 0 };
+		for (int i = 0; i < k; i++)
+			dev_rows[i] = rows[(size_t)i];
+		HIPCHK(hipMemcpy(c->border_rows_dev, dev_rows, sizeof dev_rows, hipMemcpyHostToDevice));
+	}
+	if (c->rhs)
+		hipFree(c->rhs);
+	c->rhs = fresh;
+	tmp.keep(fresh);
+	c->border = rows[(size_t)k - 1];
+	c->rhs_k = k;
+	c->rhs_kp = kp;
+	if (k == 1)
+		c->border_rows.clear();
+	else
+		c->border_rows = rows;
+	c->fuse_local_off = true;	/* as in blz_set_rhs */
+	if (c->iter_graph) {
+		hipGraphExecDestroy(c->iter_graph);
+		c->iter_graph = nullptr;
+	}
+	return BLZ_OK;
+}
+
+extern "C" int blz_set_rhs_device(blz_ctx *c, int k, const uint64_t *b, int64_t ldb, void *stream)
+{
+	return devrhs_set(c, "blz_set_rhs_device", k, b, ldb, stream);
+}
+
+extern "C" int blz_set_rhs_device32(blz_ctx *c, int k, const uint32_t *b, int64_t ldb, void *stream)
+{
+	return devrhs_set(c, "blz_set_rhs_device32", k, b, ldb, stream);
+}
+
+template <typename W>
+static int devrhs_solution(blz_ctx *c, const char *who, W *x, int64_t ldx, int *status, void *stream)
+{
+	int rc = devrhs_begin(c, who, sizeof(W), stream);
+	if (rc != BLZ_OK)
+		return rc;
+	if (!c->rhs)
+		return blz_fail(BLZ_EINVAL, "%s: the context has no right-hand side (blz_set_rhs_device)", who);
+	if (!status)
+		return blz_fail(BLZ_EINVAL, "%s: status is NULL", who);
+	const int k = c->rhs_k > 1 ? c->rhs_k : 1;
+	const int64_t xrows = c->glob_rows[0] - k;
+	if ((rc = devio_check_range(c, who, "x", x, xrows, ldx, nullptr, sizeof(W), k)) != BLZ_OK)
+		return rc;
+	hipStream_t caller = (hipStream_t)stream;
+	if ((rc = devio_enter(c, caller)) != BLZ_OK)
+		return rc;
+	/* (from here on the caller's stream is ordered behind whatever has been enqueued, on an error exit too) */
+	bool verified = false;
+	rc = solution_block_reduce(c, status, &verified);
+	hipError_t e = hipSuccess;
+	if (rc == BLZ_OK && verified)	/* (a failed verification leaves x untouched: nothing is launched) */
+		e = launch_solution_export<W>(c->cfg, x, ldx, c->slab[BLZ_V], c->inv_dev[0], c->count[0], xrows, k, c->stream);
+	const int rc_leave = devio_leave(c, caller);
+	if (rc != BLZ_OK)
+		return rc;	/* (the message of the first failure may have been replaced by devio_leave's, the code is the first's) */
+	HIPCHK(e);
+	return rc_leave;
+}
+
+extern "C" int blz_solution_device(blz_ctx *c, uint64_t *x, int64_t ldx, int *status, void *stream)
+{
+	return devrhs_solution(c, "blz_solution_device", x, ldx, status, stream);
+}
+
+extern "C" int blz_solution_device32(blz_ctx *c, uint32_t *x, int64_t ldx, int *status, void *stream)
+{
+	return devrhs_solution(c, "blz_solution_device32", x, ldx, status, stream);
 }
 

@@ -316,6 +316,48 @@ def device_triplets(i, j, x=None, device=None):
     return pi, pj, ib, px, vb, nnz
 
 
+def device_rhs(t, n, rows=None, device=None):
+    """(pointer, rows, k, ld) of the right-hand sides of Context.set_rhs_device -- or of the x of Context.solution_device --
+    held by a torch tensor, or by anything with data_ptr(), shape, stride(), dtype and device: (rows,) for one right-hand
+    side or (rows, k) for k of them, 1 <= k <= min(n, MAX_RHS), the last dimension contiguous, the row stride ld >= k taken
+    from the tensor, one of DEVICE_DTYPES, on the context's device.  Anything else is a ValueError that names the fault.
+    torch is not imported here."""
+    return _device_rhs(t, n, rows, device, DEVICE_DTYPES)
+
+
+def device_rhs32(t, n, rows=None, device=None):
+    """device_rhs() for 32-bit words (the ...32 methods of Context, p < 2**32): the dtype one of DEVICE_DTYPES32 and ld
+    counted in 32-bit words."""
+    return _device_rhs(t, n, rows, device, DEVICE_DTYPES32)
+
+
+def _device_rhs(t, n, rows, device, dtypes):
+    if str(t.dtype) not in dtypes:
+        raise ValueError(f"device right-hand side: dtype {t.dtype} is not one of {', '.join(dtypes)}")
+    if getattr(t.device, "type", None) != "cuda":
+        raise ValueError(f"device right-hand side: the tensor lives on {t.device}, not on a GPU")
+    index = t.device.index if t.device.index is not None else 0
+    if device is not None and index != device:
+        raise ValueError(f"device right-hand side: the tensor lives on device {index}, the context on device {device}")
+    shape, stride = tuple(t.shape), tuple(t.stride())
+    if len(shape) == 1:
+        got, k, ld = shape[0], 1, (stride[0] if shape[0] > 1 else max(stride[0], 1))
+    elif len(shape) == 2:
+        got, k = shape
+        if k > 1 and stride[1] != 1 and got > 0:
+            raise ValueError(f"device right-hand side: inner stride {stride[1]}, the last dimension must be contiguous")
+        ld = stride[0] if got > 1 else max(stride[0], k)
+    else:
+        raise ValueError(f"device right-hand side: {len(shape)} dimensions; it is (rows,) or (rows, k)")
+    if not 1 <= k <= min(n, MAX_RHS):
+        raise ValueError(f"device right-hand side: k = {k} right-hand sides: between 1 and min(n = {n}, {MAX_RHS}) are possible")
+    if ld < k:
+        raise ValueError(f"device right-hand side: row stride ld = {ld} is less than k = {k}")
+    if rows is not None and got != rows:
+        raise ValueError(f"device right-hand side: {got} rows, not {rows}")
+    return int(t.data_ptr()), int(got), int(k), int(ld)
+
+
 class Matrix:
     """struct sparsematrix_t of the reference (sequential/lanczos_modp.c:55-62) as numpy arrays."""
 
@@ -771,16 +813,22 @@ class Context:
 
     # ---- device matrix: the triplets are torch tensors on the context's device; torch is imported inside these methods only
 
+    @staticmethod
+    def _matrix_dims(i, j, nrows, ncols, who):
+        """(nrows, ncols) of a matrix of device triplets: what is not given is 1 + the largest index (a device reduction)"""
+        if nrows is None or ncols is None:
+            if tuple(i.shape)[0] == 0:
+                raise ValueError(f"{who}: an empty matrix needs nrows and ncols")
+            nrows = int(i.max()) + 1 if nrows is None else nrows
+            ncols = int(j.max()) + 1 if ncols is None else ncols
+        return nrows, ncols
+
     def set_matrix_device(self, i, j, x=None, nrows=None, ncols=None, right=False, stream=None):
         """blz_set_matrix_device(): M from triplets on the GPU (device_triplets() says what i, j, x may be); both CSRs are
         built there and the caller's numbering is kept.  nrows / ncols default to 1 + the largest index (a device
         reduction; an empty matrix needs them given).  Ordered on `stream` (default: torch's current stream); synchronises."""
         pi, pj, ib, px, vb, nnz = device_triplets(i, j, x, self.device)
-        if nrows is None or ncols is None:
-            if nnz == 0:
-                raise ValueError("set_matrix_device: an empty matrix needs nrows and ncols")
-            nrows = int(i.max()) + 1 if nrows is None else nrows
-            ncols = int(j.max()) + 1 if ncols is None else ncols
+        nrows, ncols = self._matrix_dims(i, j, nrows, ncols, "set_matrix_device")
         check(lib().blz_set_matrix_device(self.h, C.c_int64(nrows), C.c_int64(ncols), C.c_int64(nnz), C.c_void_p(pi),
                                           C.c_void_p(pj), C.c_int(ib), C.c_void_p(px), C.c_int(vb), C.c_int(int(bool(right))),
                                           C.c_void_p(self._stream(stream))))
@@ -884,6 +932,57 @@ class Context:
         check(lib().blz_solution_block(self.h, ptr(x), status))
         st = [int(status[i]) for i in range(k)]
         return st, (None if 2 in st else x[:length * k].reshape(length, k))
+
+    # ---- device right-hand sides: b and x are torch tensors on the context's device; torch is imported inside these methods only
+
+    def _set_rhs_device(self, read, fn, b, stream):
+        rows = self.rows(TMP)       # (0 without a matrix: the library says so)
+        p, _, k, ld = read(b, self.n, rows if rows > 0 else None, self.device)
+        check(fn(self.h, C.c_int(k), C.c_void_p(p), C.c_int64(ld), C.c_void_p(self._stream(stream))))
+
+    def set_rhs_device(self, b, stream=None):
+        """blz_set_rhs_device(): set_rhs_block() (set_rhs() for one column) from a tensor on the GPU -- device_rhs() says what
+        b may be: (rows(TMP),) or (rows(TMP), k), uint64 / int64, any row stride.  The matrix is already set with its k empty
+        last rows / columns.  Ordered on `stream` (default: torch's current stream); validates and synchronises."""
+        self._set_rhs_device(device_rhs, lib().blz_set_rhs_device, b, stream)
+
+    def set_rhs_device32(self, b, stream=None):
+        """blz_set_rhs_device32(): set_rhs_device() from a tensor of 32-bit words (uint32 / int32; p < 2**32)."""
+        self._set_rhs_device(device_rhs32, lib().blz_set_rhs_device32, b, stream)
+
+    def _solution_device(self, read, dtype, fn, out, stream):
+        k = self.rhs_count
+        if k < 1:
+            raise ValueError("solution_device: the context has no right-hand side")
+        length = self.rows(V) - k
+        if out is None:
+            import torch
+            # (zeroed through the signed dtype of the same width: fills of the unsigned ones are not everywhere in torch)
+            out = torch.zeros((length, k), dtype=getattr(torch, dtype[1:]), device=f"cuda:{self.device}").view(getattr(torch, dtype))
+        p, _, kk, ld = read(out, self.n, length, self.device)
+        if kk != k:
+            raise ValueError(f"solution_device: out has {kk} columns, the context {k} right-hand sides")
+        status = (C.c_int * MAX_RHS)(*([-1] * MAX_RHS))
+        check(fn(self.h, C.c_void_p(p), C.c_int64(ld), status, C.c_void_p(self._stream(stream))))
+        return [int(status[i]) for i in range(k)], out
+
+    def solution_device(self, out=None, stream=None):
+        """blz_solution_device(): (statuses, x) as solution_block() gives them, x a (rows(V) - k, k) tensor on the GPU: `out`
+        (uint64 / int64, any row stride; words past k of a row are not written) or a new torch.uint64 one.  Columns of
+        unsolved systems are zero; when the verification fails every status is 2 and x is as it was (zero when new)."""
+        return self._solution_device(device_rhs, "uint64", lib().blz_solution_device, out, stream)
+
+    def solution_device32(self, out=None, stream=None):
+        """blz_solution_device32(): solution_device() into a tensor of 32-bit words (a new torch.uint32 one when not given)."""
+        return self._solution_device(device_rhs32, "uint32", lib().blz_solution_device32, out, stream)
+
+    def set_matrix_rhs_device(self, i, j, x, b, nrows=None, ncols=None, right=False, stream=None):
+        """set_matrix_device() with the dimension raised by k, then set_rhs_device(): M x = b (right; b has nrows rows) or
+        x M = b (b has ncols rows) from triplets and right-hand sides that all live on the GPU."""
+        nrows, ncols = self._matrix_dims(i, j, nrows, ncols, "set_matrix_rhs_device")
+        k = device_rhs(b, self.n, nrows if right else ncols, self.device)[2]
+        self.set_matrix_device(i, j, x, nrows + (0 if right else k), ncols + (k if right else 0), right, stream)
+        self.set_rhs_device(b, stream)
 
     def rows(self, block):
         return int(lib().blz_rows(self.h, C.c_int(block)))
@@ -1403,6 +1502,30 @@ def solve_rhs(M, b, prime, n, right=False, batch=16, device=0, signed=False, wid
         fc = ctx.final_check()
         status, x = ctx.solution()
         return dict(status=status, x=x, iterations=ctx.iterations, final_check=fc)
+
+
+def solve_rhs_device(t_or_triplets, b, prime, n, right=False, batch=16, device=0):
+    """M X = B (right) / X M = B with nothing tall on the host: M a 2-D torch sparse COO tensor or a tuple (i, j, x[, nrows,
+    ncols]) of device triplets (Context.set_matrix_device), b a (rows,) or (rows, k) tensor on the same GPU (device_rhs()).
+    Returns dict(status, x, iterations, final_check): status the list of k statuses of solution_block(), x a (length, k)
+    torch.uint64 tensor on the GPU."""
+    with Context(prime, n, device) as ctx:
+        if isinstance(t_or_triplets, (tuple, list)):
+            i, j, x, *dims = t_or_triplets
+            nrows, ncols = (list(dims) + [None, None])[:2]
+        else:
+            t = t_or_triplets
+            if len(tuple(t.shape)) != 2:
+                raise ValueError(f"solve_rhs_device: {len(tuple(t.shape))} dimensions, a matrix has 2")
+            idx = t._indices().contiguous()
+            i, j, x, nrows, ncols = idx[0], idx[1], t._values().contiguous(), int(t.shape[0]), int(t.shape[1])
+        ctx.set_matrix_rhs_device(i, j, x, b, nrows, ncols, right)
+        ctx.init_v()
+        while not ctx.iterate(batch)[1]:
+            pass
+        fc = ctx.final_check()
+        status, xs = ctx.solution_device()
+        return dict(status=status, x=xs, iterations=ctx.iterations, final_check=fc)
 
 
 def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0, basis=False, signed=False, wide=False,

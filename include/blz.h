@@ -389,6 +389,35 @@ int blz_set_matrix_device(blz_ctx *ctx, int64_t nrows, int64_t ncols, int64_t nn
 int blz_set_matrix_upload(blz_ctx *ctx, const blz_coo *M, int right);
 int blz_matrix_device_built(const blz_ctx *ctx);
 
+/* Device right-hand sides: the two ends of M x = b / x M = b on memory of the context's GPU, so that a
+ * solve whose matrix came from blz_set_matrix_device needs nothing tall on the host.  The 64 / 32-bit twins follow the device
+ * blocks' pattern (the ...32 forms: contexts of 4-byte words, blz_word_bytes(ctx) == 4, p < 2^32).  A plain single rank.
+ *
+ * blz_set_rhs_device means what blz_set_rhs_block(ctx, k, a host copy of b) means (k == 1: what blz_set_rhs means): the
+ * border it leaves is that call's byte for byte, and so is every later product, iteration, checkpoint and solution.
+ *   b          blz_rows(ctx, BLZ_TMP) rows of k words, row-major, ORIGINAL numbering, row stride ldb >= k words; words
+ *              k .. ldb-1 of a row are never read.  All words below p.  Never written, not referenced after the return.
+ *   the matrix already set with the k empty last rows (right == 0) / columns, by blz_set_matrix, _prepared, _device or _upload.
+ * One kernel gathers b through the device copy of the numbering into a FRESH border (narrowed to the context's word, zero
+ * padded) and counts the words that are not below p; the call synchronises the host, reads the count, and swaps the border in
+ * only when it is zero.  BLZ_EINVAL by name, before anything is enqueued: no matrix, k outside 1..min(n, BLZ_MAX_RHS), ldb < k,
+ * a NULL / host / misaligned pointer, a range ((rows - 1) * ldb + k words) that leaves its allocation, a capturing stream, a
+ * matrix not set for one rank in one piece, a communicator, a loopback group, BLZ_FORCE_COMM, device blocks on ranks, border
+ * lines that are not empty, and (the 32-bit twin) a context of 8-byte words.  After the pass: "N words of b are not below p".
+ * A refused or invalid call leaves the context exactly as it was: the border that was resident still applies.
+ *
+ * blz_solution_device means what blz_solution_block means for every k, 1 included: the same state before, the same statuses
+ * (status: a HOST array of BLZ_MAX_RHS ints), the same V and TMP afterwards.
+ *   x          device memory, (blz_rows(ctx, BLZ_V) - k) rows of k words, row stride ldx >= k, original numbering; words
+ *              past k of a row are never written.  Unsolved systems give zero columns; when the verification fails every
+ *              status is 2 and x is untouched.
+ * The kernel basis, the k x n border words and the small elimination go through the host as in blz_solution_block (the call
+ * synchronises); the rows of V leave the slab through one kernel, ordered on `stream` like the device blocks. */
+int blz_set_rhs_device(blz_ctx *ctx, int k, const uint64_t *b, int64_t ldb, void *stream);
+int blz_set_rhs_device32(blz_ctx *ctx, int k, const uint32_t *b, int64_t ldb, void *stream);
+int blz_solution_device(blz_ctx *ctx, uint64_t *x, int64_t ldx, int *status, void *stream);
+int blz_solution_device32(blz_ctx *ctx, uint32_t *x, int64_t ldx, int *status, void *stream);
+
 /* The same with the rank-independent work done once and shared (blz_prepare / blz_prepared_load above):
  *   blz_prepare_for   prepares M with the parameters THIS context wants (pieces per exchange from the slab sizes and
  *                     BLZ_AG_CHUNKS, renumbering, panel capacity from its block width and word size)
