@@ -26,6 +26,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <vector>
 #include <atomic>
 #include <chrono>
@@ -165,6 +166,32 @@ struct ProfSpan {
 	hipEvent_t a, b;
 };
 
+/*
+ * The border of a solve with right-hand sides: the matrix has k extra empty rows / columns, the last
+ * k of side 0 in the original numbering, and the k columns of b are applied behind each product (enqueue_border).  Every
+ * entry point leaves it through border_install, and while a border is resident (rhs != nullptr), for every k:
+ *   k >= 1, and row_words = the words per row of rhs: 1 for k = 1, border_kp(k) (zero padded) otherwise;
+ *   rhs = one row of row_words words of the context's width per row of side 1 that this rank holds, solver's numbering;
+ *   rows[i], rows_dev[i], i < k = border row i's position in the operand a product of side 0 reads: its row in the solver's
+ *     numbering on one rank, its position in the GATHERED operand on several (blz_gathered_position);
+ *   distributed = set by blz_set_rhs_ranks on a context with a communicator; then own[i], own_dev[i], i < k = the local row
+ *     of border row i where this rank owns it, -1 elsewhere, send = the rank's k x n share of the border dot and recv = where
+ *     its all-reduce lands (k_border_place reads it while the stop flag is down: allreduce_dots' rule);
+ *   partial_words = the room in `partial`, at least border_dot_max_blocks * row_words * BLZ_BORDER_MAXN.
+ * rows_dev and own_dev hold BLZ_MAX_RHS entries, send and recv BLZ_MAX_RHS x cfg.n words; they and `partial` outlive the
+ * border (border_release keeps them until the context goes).
+ */
+struct Border {
+	void *rhs = nullptr;
+	int k = 0, row_words = 0;
+	std::vector<int64_t> rows, own;
+	long long *rows_dev = nullptr, *own_dev = nullptr;
+	bool distributed = false;
+	u64 *partial = nullptr;		/* partial rows of the border dot */
+	size_t partial_words = 0;
+	u64 *send = nullptr, *recv = nullptr;
+};
+
 struct blz_ctx {
 	bool profiling = false;
 	std::vector<ProfSpan> spans;
@@ -247,25 +274,7 @@ struct blz_ctx {
 	u64 *rref_out = nullptr;	/* the RREF, n x n */
 	u64 *rref_z = nullptr;		/* n x n operand of the block product */
 	int *rref_ctl = nullptr;	/* [rank-n flag, stacked rows, rank, pivots[n]] */
-	/* the border of a solve with a right-hand side (blz_set_rhs): the matrix has one extra empty row / column and b is
-	 * applied behind each product (enqueue_border) */
-	void *rhs = nullptr;		/* b: one word of the context's width per row of side 1, solver's numbering */
-	int64_t border = -1;		/* the border row of side 0 in the solver's numbering (perm[0][last]) */
-	u64 *border_partial = nullptr;	/* partial rows of the border dot */
-	/* several right-hand sides (blz_set_rhs_block, k > 1): rhs = rows x rhs_kp words, zero padded, and the k border rows of
-	 * side 0 (the last k of the original numbering) in the solver's numbering, on the host and on the device */
-	int rhs_k = 0, rhs_kp = 0;	/* 0 / 1: at most the single border above */
-	size_t border_partial_words = 0;	/* room in border_partial when the block form sized it */
-	std::vector<int64_t> border_rows;
-	long long *border_rows_dev = nullptr;
-	/* the border on several ranks (blz_set_rhs_ranks): rhs = this rank's own rows of B; border / border_rows[_dev] = the
-	 * border rows' positions in the GATHERED operand of side 0 (the slab's own rows on one rank); border_own[_dev][i] = the
-	 * local row of border row i where this rank owns it, -1 elsewhere; border_send = the rank's k x n share of the border dot,
-	 * border_recv = where its all-reduce lands (k_border_place reads it while the stop flag is down: allreduce_dots' rule) */
-	bool rhs_ranks = false;
-	std::vector<int64_t> border_own;
-	long long *border_own_dev = nullptr;
-	u64 *border_send = nullptr, *border_recv = nullptr;	/* BLZ_MAX_RHS x cfg.n words each */
+	Border bd;			/* the border of a solve with right-hand sides (above) */
 	/* device blocks (blz_set_block_device, blz_get_block_device, blz_apply_device) */
 	int32_t *inv_dev[2] = { nullptr, nullptr };	/* inv[side] on the device: uploaded on first use, freed with the matrix */
 	bool inv_ready = false;
@@ -291,6 +300,27 @@ struct blz_ctx {
 
 enum { APPLY_SLAB = 4 };
 static void devio_release_matrix(blz_ctx *c);
+
+/* no border is resident from here on; scratch_too: the context goes, and the tables and buffers that outlive a border with it */
+static void border_release(blz_ctx *c, bool scratch_too)
+{
+	Border &B = c->bd;
+	if (B.rhs)
+		hipFree(B.rhs);
+	B.rhs = nullptr;
+	B.k = B.row_words = 0;
+	B.rows.clear();
+	B.own.clear();
+	B.distributed = false;
+	if (!scratch_too)
+		return;
+	for (void *q : { (void *)B.partial, (void *)B.rows_dev, (void *)B.own_dev, (void *)B.send, (void *)B.recv })
+		if (q)
+			hipFree(q);
+	B.partial = B.send = B.recv = nullptr;
+	B.rows_dev = B.own_dev = nullptr;
+	B.partial_words = 0;
+}
 
 /* HIP-event span around one enqueue on the context's stream (only while profiling is on). */
 struct Span {
@@ -555,12 +585,7 @@ extern "C" void blz_destroy(blz_ctx *c)
 	for (u64 *b : { c->rref_stack, c->rref_gath, c->rref_out, c->rref_z })
 		if (b) hipFree(b);
 	if (c->rref_ctl) hipFree(c->rref_ctl);
-	if (c->rhs) hipFree(c->rhs);
-	if (c->border_partial) hipFree(c->border_partial);
-	if (c->border_rows_dev) hipFree(c->border_rows_dev);
-	if (c->border_own_dev) hipFree(c->border_own_dev);
-	if (c->border_send) hipFree(c->border_send);
-	if (c->border_recv) hipFree(c->border_recv);
+	border_release(c, true);
 	if (c->dot_send) hipFree(c->dot_send);
 	if (c->dot_recv) hipFree(c->dot_recv);
 	if (c->rs_recv) hipFree(c->rs_recv);
@@ -884,15 +909,7 @@ static void matrix_reset(blz_ctx *c, int right, int rank, int nranks)
 	c->rank = rank;
 	c->nranks = nranks;
 	c->fuse_local_off = false;
-	if (c->rhs) {		/* a border belongs to the matrix it was set for */
-		hipFree(c->rhs);
-		c->rhs = nullptr;
-	}
-	c->border = -1;
-	c->rhs_k = c->rhs_kp = 0;
-	c->border_rows.clear();
-	c->rhs_ranks = false;
-	c->border_own.clear();
+	border_release(c, false);	/* a border belongs to the matrix it was set for */
 }
 
 /* The last step of every matrix-setting call, once csr[] and stride[] are what the new matrix wants: the four blocks
@@ -1171,9 +1188,12 @@ extern "C" int blz_set_matrix(blz_ctx *c, const blz_coo *M, int right, int rank,
 	return rc;
 }
 
-/* ---- a right-hand side: M x = b / x M = b as kernel vectors of the bordered operator [M | b] / [M ; b] ---- */
+/* ---- right-hand sides: M x = b / x M = b as kernel vectors of the bordered operator [M | b] / [M ; b].  Every setter ends in
+ * border_install; who delegates to whom is listed in DESIGN.md section 11.3 ---- */
 
 static int put_words(blz_ctx *c, void *dst, const uint64_t *src, int64_t words);
+static inline bool exchanging(const blz_ctx *c);
+static int coll_allreduce_i32(blz_ctx *c, const void *send, void *recv, size_t words, hipStream_t st);
 
 static int rhs_refuse_ranks(const blz_ctx *c, const char *who, bool matrix_is_set)
 {
@@ -1184,50 +1204,147 @@ static int rhs_refuse_ranks(const blz_ctx *c, const char *who, bool matrix_is_se
 	return BLZ_OK;
 }
 
-extern "C" int blz_set_rhs(blz_ctx *c, const uint64_t *b)
+static int rhs_block_refuse_k(const blz_ctx *c, const char *who, int k)
 {
-	if (!c || !c->have_matrix)
-		return blz_fail(BLZ_EINVAL, "no matrix loaded (blz_set_matrix)");
-	HIPCHK(hipSetDevice(c->device));
-	if (!b)
-		return blz_fail(BLZ_EINVAL, "blz_set_rhs: b is NULL");
-	int rc = rhs_refuse_ranks(c, "blz_set_rhs", true);
-	if (rc != BLZ_OK)
-		return rc;
-	if (c->csr[0].size() != 1 || c->csr[1].size() != 1 || c->short_side[0] || c->short_side[1] || c->glob_rows[0] < 1)
-		return blz_fail(BLZ_EINVAL, "blz_set_rhs: the matrix was not set for a single rank in one piece");
-	HIPCHK(hipStreamSynchronize(c->stream));
-	const int64_t last = c->glob_rows[0] - 1, len = c->glob_rows[1];
-	const int64_t border = c->perm[0].empty() ? last : c->perm[0][(size_t)last];
-	{	/* the border row / column of the matrix itself must be empty: the product whose rows live on side 0 says so */
-		const DevCsr &A = c->csr[c->row_side[0] == 0 ? 0 : 1][0];
-		u32 rp[2] = { 0, 0 };
-		if (A.rows != c->glob_rows[0])
-			return blz_fail(BLZ_EINVAL, "blz_set_rhs: unexpected slab shape");
-		HIPCHK(hipMemcpy(rp, A.row_ptr + border, sizeof rp, hipMemcpyDeviceToHost));
-		if (rp[0] != rp[1])
-			return blz_fail(BLZ_EINVAL, "blz_set_rhs: the last %s of the matrix must be empty (it stands for the right-hand side)",
-					c->right ? "column" : "row");
+	if (k < 1 || k > c->un || k > BLZ_MAX_RHS)
+		return blz_fail(BLZ_EINVAL, "%s: %d right-hand sides: between 1 and min(n = %d, BLZ_MAX_RHS = %d) are possible", who, k,
+				c->un, BLZ_MAX_RHS);
+	return BLZ_OK;
+}
+
+/* what the one-rank setters, host and device, ask of the resident matrix */
+static int rhs_refuse_pieces(const blz_ctx *c, const char *who, int k)
+{
+	if (c->csr[0].size() != 1 || c->csr[1].size() != 1 || c->short_side[0] || c->short_side[1] || c->glob_rows[0] < k)
+		return blz_fail(BLZ_EINVAL, "%s: the matrix was not set for a single rank in one piece", who);
+	return BLZ_OK;
+}
+
+static inline int border_row_words(int k) { return k == 1 ? 1 : border_kp(k); }
+
+/* the same triplets under a dimension raised by k: k empty rows (x M = b) / columns (M x = b) */
+static blz_coo bordered_coo(const blz_coo *M, int right, int k)
+{
+	blz_coo Mb = *M;
+	(right ? Mb.ncols : Mb.nrows) += k;
+	return Mb;
+}
+
+/*
+ * Where the k border rows live, and are the ones this rank owns empty?  rows[i] = the position of border row i in the operand
+ * of side 0 (on one rank in one piece: its row in the solver's numbering), own[i] = its local row where this rank owns it, -1
+ * elsewhere.  The product whose rows live on side 0 says whether a row is empty, piece by piece.  A refusal is written to `why`
+ * and not returned (nothing is read once `why` holds one): the one-rank setters return it at once, blz_set_rhs_ranks behind its
+ * collective.  What is returned is the same on every rank (bounds and strides are every rank's).  single: the wording of
+ * the one-column setters.
+ */
+static int border_locate(blz_ctx *c, const char *who, int k, bool single, std::vector<int64_t> &rows, std::vector<int64_t> &own,
+			 char *why, size_t why_len)
+{
+	const int K = (int)c->csr[0].size(), t0 = c->row_side[0] == 0 ? 0 : 1;
+	const int64_t first = c->glob_rows[0] - k;
+	rows.assign((size_t)k, 0);
+	own.assign((size_t)k, -1);
+	for (int i = 0; i < k; i++) {
+		const int64_t row = c->perm[0].empty() ? first + i : c->perm[0][(size_t)(first + i)];
+		int owner = 0;
+		int64_t local = 0;
+		const int64_t pos = blz_gathered_position(c->bounds[0].data(), c->nranks, c->stride[0], K, row, &owner, &local);
+		if (pos < 0)
+			return (int)pos;
+		rows[(size_t)i] = pos;
+		if (owner != c->rank)
+			continue;
+		own[(size_t)i] = local;
+		for (int q = 0; q < K && !why[0]; q++) {
+			const DevCsr &A = c->csr[t0][(size_t)q];
+			u32 rp[2] = { 0, 1 };
+			if (A.rows != c->count[0] || local >= A.rows ||
+			    hipMemcpy(rp, A.row_ptr + local, sizeof rp, hipMemcpyDeviceToHost) != hipSuccess)
+				snprintf(why, why_len, "%s: unexpected slab shape", who);
+			else if (rp[0] != rp[1] && single)
+				snprintf(why, why_len, "%s: the last %s of the matrix must be empty (it stands for the right-hand side)", who,
+					 c->right ? "column" : "row");
+			else if (rp[0] != rp[1])
+				snprintf(why, why_len, "%s: the last %d %s of the matrix must be empty (they stand for the right-hand sides)",
+					 who, k, c->right ? "columns" : "rows");
+		}
 	}
-	std::vector<uint64_t> bs((size_t)std::max<int64_t>(len, 1), 0);
-	for (int64_t r = 0; r < len; r++) {
-		if (b[r] >= c->prime)
-			return blz_fail(BLZ_EINVAL, "blz_set_rhs: b[%lld] is not below p", (long long)r);
-		bs[(size_t)(c->perm[1].empty() ? r : c->perm[1][(size_t)r])] = b[r];
+	return BLZ_OK;
+}
+
+/* the words the host setters upload: rows of border_row_words(k) words (allocated bare: blz_rhs_cut fills every one) */
+struct BorderWords {
+	std::unique_ptr<uint64_t[]> w;
+	size_t count = 0;
+};
+
+/* bs = the rows [first, first + count) of side 1 (solver's numbering) of the len x k block b, border_row_words(k) words each;
+ * a refusal (a word not below p) goes to `why` like border_locate's */
+static void border_cut(blz_ctx *c, const char *who, int k, const uint64_t *b, int64_t first, int64_t count, BorderWords &bs,
+		       char *why, size_t why_len)
+{
+	const int kw = border_row_words(k);
+	if (why[0])
+		return;
+	bs.count = (size_t)std::max<int64_t>(count, 1) * kw;
+	bs.w.reset(new uint64_t[bs.count]);
+	if (blz_rhs_cut(b, c->glob_rows[1], k, kw, c->prime, c->perm[1].empty() ? nullptr : c->perm[1].data(), first, count,
+			bs.w.get()) != BLZ_OK)
+		snprintf(why, why_len, "%s: %s", who, blz_last_error());
+}
+
+/* everything of border_install that can fail: room for the partial rows of the border dot, the row tables on the device.  The
+ * allocations come first, so that a border that is resident keeps tables of its own until all of them have succeeded. */
+static hipError_t border_tables(blz_ctx *c, int k, const std::vector<int64_t> &rows, const std::vector<int64_t> *own)
+{
+	Border &B = c->bd;
+	hipError_t e;
+	long long tab[BLZ_MAX_RHS];
+	const size_t need = (size_t)border_dot_max_blocks(c->cfg) * border_row_words(k) * BLZ_BORDER_MAXN;
+	if (B.partial_words < need) {
+		u64 *roomier = nullptr;
+		if ((e = hipMalloc(&roomier, need * sizeof(u64))) != hipSuccess)
+			return e;
+		if (B.partial)
+			hipFree(B.partial);
+		B.partial = roomier;
+		B.partial_words = need;
 	}
-	if (c->rhs)
-		hipFree(c->rhs);
-	c->rhs = nullptr;
-	HIPCHK(hipMalloc(&c->rhs, bs.size() * c->cfg.word));
-	if ((rc = put_words(c, c->rhs, bs.data(), (int64_t)bs.size())) != BLZ_OK)
-		return rc;
-	if (!c->border_partial)
-		HIPCHK(hipMalloc(&c->border_partial, (size_t)border_dot_max_blocks(c->cfg) * BLZ_BORDER_MAXN * sizeof(u64)));
-	c->border = border;
-	c->rhs_k = 1;
-	c->rhs_kp = 0;
-	c->border_rows.clear();
-	/* the fused inner products would read the border row of Av before the border dot has written it: the second product
+	if (!B.rows_dev && (e = hipMalloc(&B.rows_dev, sizeof tab)) != hipSuccess)
+		return e;
+	if (own && !B.own_dev && (e = hipMalloc(&B.own_dev, sizeof tab)) != hipSuccess)
+		return e;
+	for (int i = 0; i < BLZ_MAX_RHS; i++)
+		tab[i] = i < k ? rows[(size_t)i] : 0;
+	if ((e = hipMemcpy(B.rows_dev, tab, sizeof tab, hipMemcpyHostToDevice)) != hipSuccess || !own)
+		return e;
+	for (int i = 0; i < BLZ_MAX_RHS; i++)
+		tab[i] = i < k ? (*own)[(size_t)i] : -1;
+	return hipMemcpy(B.own_dev, tab, sizeof tab, hipMemcpyHostToDevice);
+}
+
+/* The one way a border becomes resident.  rhs = a finished device buffer of border_row_words(k) words per row, which belongs to
+ * the context from here on (freed if the call fails); rows, own = border_locate's, own = nullptr unless the border is
+ * distributed.  The caller has drained the streams.  Everything that can fail comes before the swap: a failing call leaves
+ * the border that was resident in place. */
+static int border_install(blz_ctx *c, int k, const std::vector<int64_t> &rows, const std::vector<int64_t> *own, void *rhs)
+{
+	const hipError_t e = border_tables(c, k, rows, own);
+	if (e != hipSuccess) {
+		hipFree(rhs);
+		return blz_fail(BLZ_EHIP, "border_install: %s", hipGetErrorString(e));
+	}
+	Border &B = c->bd;
+	if (B.rhs)
+		hipFree(B.rhs);
+	B.rhs = rhs;
+	B.k = k;
+	B.row_words = border_row_words(k);
+	B.rows = rows;
+	B.distributed = own != nullptr;
+	B.own = own ? *own : std::vector<int64_t>();
+	/* the fused inner products would read the border rows of Av before the border dot has written them: the second product
 	 * runs plain and block_dot as its own kernel */
 	c->fuse_local_off = true;
 	if (c->iter_graph) {
@@ -1237,6 +1354,49 @@ extern "C" int blz_set_rhs(blz_ctx *c, const uint64_t *b)
 	return BLZ_OK;
 }
 
+/* border_install for the host setters: bs = border_cut's words, uploaded in the context's width */
+static int border_install_host(blz_ctx *c, int k, const std::vector<int64_t> &rows, const std::vector<int64_t> *own,
+			       const BorderWords &bs)
+{
+	void *rhs = nullptr;
+	HIPCHK(hipMalloc(&rhs, bs.count * c->cfg.word));
+	const int rc = put_words(c, rhs, bs.w.get(), (int64_t)bs.count);
+	if (rc != BLZ_OK) {
+		hipFree(rhs);
+		return rc;
+	}
+	return border_install(c, k, rows, own, rhs);
+}
+
+/* the one-rank host setters past their own argument checks: blz_set_rhs (k = 1) and blz_set_rhs_block (k > 1), each under
+ * its own name */
+static int set_rhs_host(blz_ctx *c, const char *who, int k, const uint64_t *b)
+{
+	int rc = rhs_refuse_ranks(c, who, true);
+	if (rc != BLZ_OK || (rc = rhs_refuse_pieces(c, who, k)) != BLZ_OK)
+		return rc;
+	HIPCHK(hipStreamSynchronize(c->stream));
+	std::vector<int64_t> rows, own;
+	BorderWords bs;
+	char why[512] = "";
+	if ((rc = border_locate(c, who, k, k == 1, rows, own, why, sizeof why)) != BLZ_OK)
+		return rc;
+	border_cut(c, who, k, b, 0, c->glob_rows[1], bs, why, sizeof why);
+	if (why[0])
+		return blz_fail(BLZ_EINVAL, "%s", why);
+	return border_install_host(c, k, rows, nullptr, bs);
+}
+
+extern "C" int blz_set_rhs(blz_ctx *c, const uint64_t *b)
+{
+	if (!c || !c->have_matrix)
+		return blz_fail(BLZ_EINVAL, "no matrix loaded (blz_set_matrix)");
+	HIPCHK(hipSetDevice(c->device));
+	if (!b)
+		return blz_fail(BLZ_EINVAL, "blz_set_rhs: b is NULL");
+	return set_rhs_host(c, "blz_set_rhs", 1, b);
+}
+
 extern "C" int blz_set_matrix_rhs(blz_ctx *c, const blz_coo *M, int right, const uint64_t *b)
 {
 	if (!c || !M || !b)
@@ -1244,27 +1404,15 @@ extern "C" int blz_set_matrix_rhs(blz_ctx *c, const blz_coo *M, int right, const
 	int rc = rhs_refuse_ranks(c, "blz_set_matrix_rhs", false);
 	if (rc != BLZ_OK)
 		return rc;
-	blz_coo Mb = *M;	/* the same triplets under a dimension raised by one: an empty row (x M = b) / column (M x = b) */
-	if (right)
-		Mb.ncols++;
-	else
-		Mb.nrows++;
+	const blz_coo Mb = bordered_coo(M, right, 1);
 	if ((rc = blz_set_matrix(c, &Mb, right, 0, 1)) != BLZ_OK)
 		return rc;
 	return blz_set_rhs(c, b);
 }
 
-extern "C" int blz_has_rhs(const blz_ctx *c) { return c && c->have_matrix && c->rhs != nullptr; }
+extern "C" int blz_has_rhs(const blz_ctx *c) { return c && c->have_matrix && c->bd.rhs != nullptr; }
 
-extern "C" int blz_rhs_count(const blz_ctx *c) { return blz_has_rhs(c) ? (c->rhs_k > 1 ? c->rhs_k : 1) : 0; }
-
-static int rhs_block_refuse_k(const blz_ctx *c, const char *who, int k)
-{
-	if (k < 1 || k > c->un || k > BLZ_MAX_RHS)
-		return blz_fail(BLZ_EINVAL, "%s: %d right-hand sides: between 1 and min(n = %d, BLZ_MAX_RHS = %d) are possible", who, k,
-				c->un, BLZ_MAX_RHS);
-	return BLZ_OK;
-}
+extern "C" int blz_rhs_count(const blz_ctx *c) { return blz_has_rhs(c) ? c->bd.k : 0; }
 
 extern "C" int blz_set_rhs_block(blz_ctx *c, int k, const uint64_t *b)
 {
@@ -1277,70 +1425,8 @@ extern "C" int blz_set_rhs_block(blz_ctx *c, int k, const uint64_t *b)
 	if (rc != BLZ_OK)
 		return rc;
 	if (k == 1)
-		return blz_set_rhs(c, b);	/* one column is today's border, kernels and all */
-	if ((rc = rhs_refuse_ranks(c, "blz_set_rhs_block", true)) != BLZ_OK)
-		return rc;
-	if (c->csr[0].size() != 1 || c->csr[1].size() != 1 || c->short_side[0] || c->short_side[1] || c->glob_rows[0] < k)
-		return blz_fail(BLZ_EINVAL, "blz_set_rhs_block: the matrix was not set for a single rank in one piece");
-	HIPCHK(hipStreamSynchronize(c->stream));
-	const int64_t first = c->glob_rows[0] - k, len = c->glob_rows[1];
-	const int kp = border_kp(k);
-	std::vector<int64_t> rows((size_t)k);
-	{	/* the k border rows / columns of the matrix itself must be empty: the product whose rows live on side 0 says so */
-		const DevCsr &A = c->csr[c->row_side[0] == 0 ? 0 : 1][0];
-		if (A.rows != c->glob_rows[0])
-			return blz_fail(BLZ_EINVAL, "blz_set_rhs_block: unexpected slab shape");
-		for (int i = 0; i < k; i++) {
-			u32 rp[2] = { 0, 0 };
-			rows[(size_t)i] = c->perm[0].empty() ? first + i : c->perm[0][(size_t)(first + i)];
-			HIPCHK(hipMemcpy(rp, A.row_ptr + rows[(size_t)i], sizeof rp, hipMemcpyDeviceToHost));
-			if (rp[0] != rp[1])
-				return blz_fail(BLZ_EINVAL, "blz_set_rhs_block: the last %d %s of the matrix must be empty (they stand for the "
-						"right-hand sides)", k, c->right ? "columns" : "rows");
-		}
-	}
-	std::vector<uint64_t> bs((size_t)std::max<int64_t>(len, 1) * kp, 0);
-	for (int64_t r = 0; r < len; r++) {
-		const size_t at = (size_t)(c->perm[1].empty() ? r : c->perm[1][(size_t)r]) * kp;
-		for (int i = 0; i < k; i++) {
-			if (b[r * k + i] >= c->prime)
-				return blz_fail(BLZ_EINVAL, "blz_set_rhs_block: b[%lld, %d] is not below p", (long long)r, i);
-			bs[at + i] = b[r * k + i];
-		}
-	}
-	if (c->rhs)
-		hipFree(c->rhs);
-	c->rhs = nullptr;
-	HIPCHK(hipMalloc(&c->rhs, bs.size() * c->cfg.word));
-	if ((rc = put_words(c, c->rhs, bs.data(), (int64_t)bs.size())) != BLZ_OK)
-		return rc;
-	const size_t need = (size_t)border_dot_max_blocks(c->cfg) * kp * BLZ_BORDER_MAXN;
-	if (c->border_partial_words < need) {
-		if (c->border_partial)
-			hipFree(c->border_partial);
-		c->border_partial = nullptr;
-		c->border_partial_words = 0;
-		HIPCHK(hipMalloc(&c->border_partial, need * sizeof(u64)));
-		c->border_partial_words = need;
-	}
-	if (!c->border_rows_dev)
-		HIPCHK(hipMalloc(&c->border_rows_dev, BLZ_MAX_RHS * sizeof(long long)));
-	{
-		long long dev_rows[BLZ_MAX_RHS] = { 0 };
-		for (int i = 0; i < k; i++)
-			dev_rows[i] = rows[(size_t)i];
-		HIPCHK(hipMemcpy(c->border_rows_dev, dev_rows, sizeof dev_rows, hipMemcpyHostToDevice));
-	}
-	c->border_rows = rows;
-	c->border = rows[(size_t)k - 1];
-	c->rhs_k = k;
-	c->rhs_kp = kp;
-	c->fuse_local_off = true;	/* as in blz_set_rhs */
-	if (c->iter_graph) {
-		hipGraphExecDestroy(c->iter_graph);
-		c->iter_graph = nullptr;
-	}
-	return BLZ_OK;
+		return blz_set_rhs(c, b);	/* one column reports as blz_set_rhs */
+	return set_rhs_host(c, "blz_set_rhs_block", k, b);
 }
 
 extern "C" int blz_set_matrix_rhs_block(blz_ctx *c, const blz_coo *M, int right, int k, const uint64_t *b)
@@ -1350,20 +1436,13 @@ extern "C" int blz_set_matrix_rhs_block(blz_ctx *c, const blz_coo *M, int right,
 	int rc = rhs_block_refuse_k(c, "blz_set_matrix_rhs_block", k);
 	if (rc != BLZ_OK || (rc = rhs_refuse_ranks(c, "blz_set_matrix_rhs_block", false)) != BLZ_OK)
 		return rc;
-	blz_coo Mb = *M;	/* the same triplets under a dimension raised by k: k empty rows (x M = b) / columns (M x = b) */
-	if (right)
-		Mb.ncols += k;
-	else
-		Mb.nrows += k;
+	const blz_coo Mb = bordered_coo(M, right, k);
 	if ((rc = blz_set_matrix(c, &Mb, right, 0, 1)) != BLZ_OK)
 		return rc;
 	return blz_set_rhs_block(c, k, b);
 }
 
 /* ---- the border on several ranks ---- */
-
-static inline bool exchanging(const blz_ctx *c);
-static int coll_allreduce_i32(blz_ctx *c, const void *send, void *recv, size_t words, hipStream_t st);
 
 extern "C" int blz_set_rhs_ranks(blz_ctx *c, int k, const uint64_t *b)
 {
@@ -1393,111 +1472,37 @@ extern "C" int blz_set_rhs_ranks(blz_ctx *c, int k, const uint64_t *b)
 		return blz_fail(BLZ_EINVAL, "blz_set_rhs_ranks: unexpected matrix shape");
 	HIPCHK(hipStreamSynchronize(c->stream));
 	HIPCHK(hipStreamSynchronize(c->xstream));
-	const int K = (int)c->csr[0].size(), np = c->cfg.n;
-	const int kp = k == 1 ? 1 : border_kp(k);
-	const int64_t first = c->glob_rows[0] - k, len = c->glob_rows[1];
-	if (!c->border_send) {
-		HIPCHK(hipMalloc(&c->border_send, (size_t)BLZ_MAX_RHS * np * sizeof(u64)));
-		HIPCHK(hipMalloc(&c->border_recv, (size_t)BLZ_MAX_RHS * np * sizeof(u64)));
-		HIPCHK(hipMemset(c->border_send, 0, (size_t)BLZ_MAX_RHS * np * sizeof(u64)));
-		HIPCHK(hipMemset(c->border_recv, 0, (size_t)BLZ_MAX_RHS * np * sizeof(u64)));
+	Border &B = c->bd;
+	if (!B.send) {
+		const size_t bytes = (size_t)BLZ_MAX_RHS * c->cfg.n * sizeof(u64);
+		HIPCHK(hipMalloc(&B.send, bytes));
+		HIPCHK(hipMalloc(&B.recv, bytes));
+		HIPCHK(hipMemset(B.send, 0, bytes));
+		HIPCHK(hipMemset(B.recv, 0, bytes));
 	}
-	/* where the k border rows live, and are the ones this rank owns empty?  The product whose rows live on side 0 says so,
-	 * piece by piece.  A refusal is recorded, not returned: it goes out behind the collective, on every rank. */
-	std::vector<int64_t> gpos((size_t)k), own((size_t)k);
-	int refuse = 0;
+	std::vector<int64_t> gpos, own;
+	BorderWords bs;
 	char why[512] = "";
-	if (!b) {
-		refuse = 1;
+	if (!b)
 		snprintf(why, sizeof why, "blz_set_rhs_ranks: b is NULL");
-	}
-	const int t0 = c->row_side[0] == 0 ? 0 : 1;
-	for (int i = 0; i < k; i++) {
-		const int64_t row = c->perm[0].empty() ? first + i : c->perm[0][(size_t)(first + i)];
-		int owner = 0;
-		int64_t local = 0;
-		const int64_t pos = blz_gathered_position(c->bounds[0].data(), c->nranks, c->stride[0], K, row, &owner, &local);
-		if (pos < 0)
-			return (int)pos;	/* (bounds and strides are every rank's: the same verdict everywhere) */
-		gpos[(size_t)i] = pos;
-		own[(size_t)i] = owner == c->rank ? local : -1;
-		for (int q = 0; q < K && owner == c->rank && !refuse; q++) {
-			const DevCsr &A = c->csr[t0][(size_t)q];
-			u32 rp[2] = { 0, 1 };
-			if (A.rows != c->count[0] || local >= A.rows ||
-			    hipMemcpy(rp, A.row_ptr + local, sizeof rp, hipMemcpyDeviceToHost) != hipSuccess) {
-				refuse = 1;
-				snprintf(why, sizeof why, "blz_set_rhs_ranks: unexpected slab shape");
-			} else if (rp[0] != rp[1]) {
-				refuse = 1;
-				snprintf(why, sizeof why, "blz_set_rhs_ranks: the last %d %s of the matrix must be empty (they stand for the "
-					 "right-hand sides)", k, c->right ? "columns" : "rows");
-			}
-		}
-	}
-	std::vector<uint64_t> bs((size_t)std::max<int64_t>(c->count[1], 1) * kp, 0);
-	if (!refuse && blz_rhs_cut(b, len, k, kp, c->prime, c->perm[1].empty() ? nullptr : c->perm[1].data(), c->first[1], c->count[1],
-				   bs.data()) != BLZ_OK) {
-		refuse = 1;
-		snprintf(why, sizeof why, "blz_set_rhs_ranks: %s", blz_last_error());
-	}
+	if ((rc = border_locate(c, "blz_set_rhs_ranks", k, false, gpos, own, why, sizeof why)) != BLZ_OK)
+		return rc;
+	border_cut(c, "blz_set_rhs_ranks", k, b, c->first[1], c->count[1], bs, why, sizeof why);
+	const int refuse = why[0] != 0;
 	if (exchanging(c)) {	/* all ranks pass or all fail */
 		int sum = 0;
-		HIPCHK(hipMemcpy(c->border_send, &refuse, sizeof refuse, hipMemcpyHostToDevice));
-		if ((rc = coll_allreduce_i32(c, c->border_send, c->border_recv, 1, c->stream)) != BLZ_OK)
+		HIPCHK(hipMemcpy(B.send, &refuse, sizeof refuse, hipMemcpyHostToDevice));
+		if ((rc = coll_allreduce_i32(c, B.send, B.recv, 1, c->stream)) != BLZ_OK)
 			return rc;
 		HIPCHK(hipStreamSynchronize(c->stream));
-		HIPCHK(hipMemcpy(&sum, c->border_recv, sizeof sum, hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(&sum, B.recv, sizeof sum, hipMemcpyDeviceToHost));
 		if (sum && !refuse)
 			return blz_fail(BLZ_EINVAL, "blz_set_rhs_ranks: refused on another rank (%d of %d): the border rows must be empty and "
 					"every word of b below p", sum, c->nranks);
 	}
 	if (refuse)
 		return blz_fail(BLZ_EINVAL, "%s", why);
-	if (c->rhs)
-		hipFree(c->rhs);
-	c->rhs = nullptr;
-	HIPCHK(hipMalloc(&c->rhs, bs.size() * c->cfg.word));
-	if ((rc = put_words(c, c->rhs, bs.data(), (int64_t)bs.size())) != BLZ_OK)
-		return rc;
-	const size_t need = (size_t)border_dot_max_blocks(c->cfg) * kp * BLZ_BORDER_MAXN;
-	if (!c->border_partial || (c->border_partial_words < need && kp > 1)) {
-		if (c->border_partial)
-			hipFree(c->border_partial);
-		c->border_partial = nullptr;
-		c->border_partial_words = 0;
-		HIPCHK(hipMalloc(&c->border_partial, need * sizeof(u64)));
-		c->border_partial_words = kp > 1 ? need : 0;	/* (as the one-rank entry points account for it) */
-	}
-	if (!c->border_rows_dev)
-		HIPCHK(hipMalloc(&c->border_rows_dev, BLZ_MAX_RHS * sizeof(long long)));
-	if (!c->border_own_dev)
-		HIPCHK(hipMalloc(&c->border_own_dev, BLZ_MAX_RHS * sizeof(long long)));
-	{
-		long long dev_rows[BLZ_MAX_RHS] = { 0 }, dev_own[BLZ_MAX_RHS];
-		for (int i = 0; i < BLZ_MAX_RHS; i++)
-			dev_own[i] = -1;
-		for (int i = 0; i < k; i++) {
-			dev_rows[i] = gpos[(size_t)i];
-			dev_own[i] = own[(size_t)i];
-		}
-		HIPCHK(hipMemcpy(c->border_rows_dev, dev_rows, sizeof dev_rows, hipMemcpyHostToDevice));
-		HIPCHK(hipMemcpy(c->border_own_dev, dev_own, sizeof dev_own, hipMemcpyHostToDevice));
-	}
-	c->border_own = own;
-	c->border = gpos[(size_t)k - 1];
-	c->border_rows.clear();
-	if (k > 1)
-		c->border_rows = gpos;
-	c->rhs_k = k;
-	c->rhs_kp = k > 1 ? kp : 0;
-	c->rhs_ranks = true;
-	c->fuse_local_off = true;	/* as in blz_set_rhs */
-	if (c->iter_graph) {
-		hipGraphExecDestroy(c->iter_graph);
-		c->iter_graph = nullptr;
-	}
-	return BLZ_OK;
+	return border_install_host(c, k, gpos, &own, bs);
 }
 
 extern "C" int blz_set_matrix_rhs_ranks(blz_ctx *c, const blz_coo *M, int right, int k, const uint64_t *b, int rank, int nranks)
@@ -1516,11 +1521,7 @@ extern "C" int blz_set_matrix_rhs_ranks(blz_ctx *c, const blz_coo *M, int right,
 	if (c->external_exchange)
 		return blz_fail(BLZ_EINVAL, "blz_set_matrix_rhs_ranks: the context is in external-exchange mode (the all-reduce of the "
 				"border words is the library's own)");
-	blz_coo Mb = *M;	/* the same triplets under a dimension raised by k, as in blz_set_matrix_rhs_block */
-	if (right)
-		Mb.ncols += k;
-	else
-		Mb.nrows += k;
+	const blz_coo Mb = bordered_coo(M, right, k);
 	blz_prepared *P = nullptr;
 	if ((rc = blz_prepare_for(c, &Mb, right, nranks, &P)) != BLZ_OK)
 		return rc;
@@ -2059,57 +2060,46 @@ static inline const u64 *dot_sums(blz_ctx *c) { return exchanging(c) ? c->dot_re
  */
 static int enqueue_border(blz_ctx *c, int transpose, int src, int dst, const DevCtl *ctl, int cls)
 {
-	const size_t row_bytes = (size_t)c->cfg.n * c->cfg.word;
-	if (c->rhs_ranks && exchanging(c)) {
-		/* Several ranks.  T and B are this rank's own rows.  The product that writes side 1 reads the k border rows of its
-		 * operand where the exchange has just put them (all K pieces have landed: the products above waited for them), at
-		 * their positions in the gathered layout -- nothing more is exchanged.  The one that writes side 0 takes the dot over
-		 * its own rows (zeros from a rank without any), all-reduces the k x n words and the owners store their rows.  The
-		 * collective is enqueued whatever the stop flag says, out of a send buffer into a landing buffer of its own (the
-		 * reasoning of allreduce_dots): past the stop the two kernels around it are no-ops and the slab keeps its rows. */
-		const int k = c->rhs_k > 1 ? c->rhs_k : 1;
-		if (c->row_side[transpose] == 1) {
-			Span sp(c, cls);
-			const char *X = (const char *)operand_ptr(c, src);
-			if (k > 1)
-				HIPCHK(launch_border_update_k(c->cfg, slab_ptr(c, dst), c->rhs, X, c->border_rows_dev, k, c->count[1], ctl,
-							      c->stream));
-			else
-				HIPCHK(launch_border_update(c->cfg, slab_ptr(c, dst), c->rhs, X + (size_t)c->border * row_bytes, c->count[1], ctl,
-							    c->stream));
-			return BLZ_OK;
-		}
+	const Border &B = c->bd;
+	const int k = B.k;
+	const size_t last = (size_t)B.rows[(size_t)k - 1] * c->cfg.n * c->cfg.word;	/* k = 1: where the one border row starts */
+	if (c->row_side[transpose] == 1) {
+		/* The product that writes side 1 reads the k border rows of its operand: of the slab on one rank; on several, where
+		 * the exchange has just put them (all K pieces have landed: the products above waited for them), at their positions
+		 * in the gathered layout -- nothing more is exchanged. */
+		Span sp(c, cls);
+		const char *X = (const char *)operand_ptr(c, src);
+		if (k > 1)	/* several right-hand sides: the same pass, fused over the k columns */
+			HIPCHK(launch_border_update_k(c->cfg, slab_ptr(c, dst), B.rhs, X, B.rows_dev, k, c->count[1], ctl, c->stream));
+		else
+			HIPCHK(launch_border_update(c->cfg, slab_ptr(c, dst), B.rhs, X + last, c->count[1], ctl, c->stream));
+		return BLZ_OK;
+	}
+	if (B.distributed && exchanging(c)) {
+		/* Several ranks.  T and B are this rank's own rows.  The product that writes side 0 takes the dot over its own rows
+		 * (zeros from a rank without any), all-reduces the k x n words and the owners store their rows.  The collective is
+		 * enqueued whatever the stop flag says, out of a send buffer into a landing buffer of its own (the reasoning of
+		 * allreduce_dots): past the stop the two kernels around it are no-ops and the slab keeps its rows. */
 		{
 			Span sp(c, cls);
-			HIPCHK(launch_border_dot_send(c->cfg, slab_ptr(c, src), c->rhs, c->count[1], c->border_partial, c->border_send, k, ctl,
-						      c->stream));
+			HIPCHK(launch_border_dot_send(c->cfg, slab_ptr(c, src), B.rhs, c->count[1], B.partial, B.send, k, ctl, c->stream));
 		}
 		{
 			Span sp(c, PK_AR);
-			int rc_ = coll_allreduce_u64(c, c->border_send, c->border_recv, (size_t)k * c->cfg.n, c->stream);
+			int rc_ = coll_allreduce_u64(c, B.send, B.recv, (size_t)k * c->cfg.n, c->stream);
 			if (rc_ != BLZ_OK)
 				return rc_;
 		}
 		Span sp(c, cls);
-		HIPCHK(launch_border_place(c->cfg, c->border_recv, slab_ptr(c, dst), c->border_own_dev, k, ctl, c->stream));
+		HIPCHK(launch_border_place(c->cfg, B.recv, slab_ptr(c, dst), B.own_dev, k, ctl, c->stream));
 		return BLZ_OK;
 	}
 	Span sp(c, cls);
-	if (c->rhs_k > 1) {	/* several right-hand sides: the same two passes, fused over the k columns */
-		if (c->row_side[transpose] == 1)
-			HIPCHK(launch_border_update_k(c->cfg, slab_ptr(c, dst), c->rhs, slab_ptr(c, src), c->border_rows_dev, c->rhs_k,
-						      c->count[1], ctl, c->stream));
-		else
-			HIPCHK(launch_border_dot_k(c->cfg, slab_ptr(c, src), c->rhs, c->count[1], c->border_partial, slab_ptr(c, dst),
-						   c->border_rows_dev, c->rhs_k, ctl, c->stream));
-		return BLZ_OK;
-	}
-	if (c->row_side[transpose] == 1)
-		HIPCHK(launch_border_update(c->cfg, slab_ptr(c, dst), c->rhs, slab_ptr(c, src) + (size_t)c->border * row_bytes, c->count[1],
-					    ctl, c->stream));
+	if (k > 1)
+		HIPCHK(launch_border_dot_k(c->cfg, slab_ptr(c, src), B.rhs, c->count[1], B.partial, slab_ptr(c, dst), B.rows_dev, k, ctl,
+					   c->stream));
 	else
-		HIPCHK(launch_border_dot(c->cfg, slab_ptr(c, src), c->rhs, c->count[1], c->border_partial,
-					 slab_ptr(c, dst) + (size_t)c->border * row_bytes, ctl, c->stream));
+		HIPCHK(launch_border_dot(c->cfg, slab_ptr(c, src), B.rhs, c->count[1], B.partial, slab_ptr(c, dst) + last, ctl, c->stream));
 	return BLZ_OK;
 }
 
@@ -2186,7 +2176,7 @@ static int enqueue_product(blz_ctx *c, int transpose, int src, int dst, bool wit
 		else
 			HIPCHK(launch_spmv(c->cfg, A, X, slab_ptr(c, dst), k > 0, ctl, c->stream));
 	}
-	if (c->rhs)
+	if (c->bd.rhs)
 		return enqueue_border(c, transpose, src, dst, ctl, cls);
 	return BLZ_OK;
 }
@@ -2587,22 +2577,22 @@ static uint64_t host_inverse(uint64_t a, uint64_t p)
 
 /* the k border rows of V on the host, cfg.n words each.  Several ranks: every rank sends the rows it owns (zeros for the
  * others) through the border's all-reduce, so every rank reads the same words; collective. */
-static int border_rows_to_host(blz_ctx *c, int k, std::vector<uint64_t> &W)
+static int border_rows_to_host(blz_ctx *c, std::vector<uint64_t> &W)
 {
+	const Border &B = c->bd;
 	const int np = c->cfg.n;
-	W.assign((size_t)k * np, 0);
-	if (c->rhs_ranks && exchanging(c)) {
-		HIPCHK(launch_border_rows_send(c->cfg, slab_ptr(c, BLZ_V), c->border_own_dev, k, c->border_send, c->stream));
-		int rc = coll_allreduce_u64(c, c->border_send, c->border_recv, (size_t)k * np, c->stream);
+	W.assign((size_t)B.k * np, 0);
+	if (B.distributed && exchanging(c)) {
+		HIPCHK(launch_border_rows_send(c->cfg, slab_ptr(c, BLZ_V), B.own_dev, B.k, B.send, c->stream));
+		int rc = coll_allreduce_u64(c, B.send, B.recv, (size_t)B.k * np, c->stream);
 		if (rc != BLZ_OK)
 			return rc;
 		HIPCHK(hipStreamSynchronize(c->stream));
-		HIPCHK(hipMemcpy(W.data(), c->border_recv, W.size() * sizeof(u64), hipMemcpyDeviceToHost));
+		HIPCHK(hipMemcpy(W.data(), B.recv, W.size() * sizeof(u64), hipMemcpyDeviceToHost));
 		return BLZ_OK;
 	}
-	for (int i = 0; i < k; i++) {
-		const int64_t row = c->rhs_k > 1 ? c->border_rows[(size_t)i] : c->border;
-		int rc = get_words(c, W.data() + (size_t)i * np, slab_ptr(c, BLZ_V) + (size_t)row * np * c->cfg.word, np);
+	for (int i = 0; i < B.k; i++) {
+		int rc = get_words(c, W.data() + (size_t)i * np, slab_ptr(c, BLZ_V) + (size_t)B.rows[(size_t)i] * np * c->cfg.word, np);
 		if (rc != BLZ_OK)
 			return rc;
 	}
@@ -2634,67 +2624,6 @@ static int residual_flag(blz_ctx *c, int *nonzero)
 	return BLZ_OK;
 }
 
-extern "C" int blz_solution(blz_ctx *c, uint64_t *x, int *status)
-{
-	NEED_MATRIX(c);
-	if (!c->rhs || !x || !status)
-		return blz_fail(BLZ_EINVAL, "blz_solution: %s", !c->rhs ? "the context has no right-hand side (blz_set_matrix_rhs)" : "NULL argument");
-	if (c->rhs_k > 1)
-		return blz_fail(BLZ_EINVAL, "blz_solution: the context has %d right-hand sides: use blz_solution_block", c->rhs_k);
-	const int n = c->un;
-	const u64 p = c->prime;
-	int k = 0;
-	int rc = blz_kernel_basis(c, &k, nullptr);
-	if (rc != BLZ_OK)
-		return rc;
-	/* the first basis vector with a non-zero border word: v = (y, w), M' v = 0  <=>  M y + w b = 0 */
-	std::vector<uint64_t> brow;
-	if ((rc = border_rows_to_host(c, 1, brow)) != BLZ_OK)
-		return rc;
-	int j = 0;
-	while (j < k && brow[(size_t)j] == 0)
-		j++;
-	if (j >= k) {
-		*status = 1;
-		return BLZ_OK;
-	}
-	/* column 0 <- -w^-1 * column j (border word p - 1, i.e. -1), the other columns zero: one-column selection matrix */
-	std::vector<uint64_t> Z((size_t)n * n, 0);
-	const uint64_t winv = host_inverse(brow[(size_t)j], p);
-	Z[(size_t)j * n] = winv ? p - winv : 0;
-	if ((rc = block_mul(c, Z)) != BLZ_OK)
-		return rc;
-	/* the check, on the GPU like blz_final_check: the side-1 product of that column with the border applied is
-	 * M y - b and must be zero.  The stop flag is up by now, so the product runs on control words of its own. */
-	{
-		DevCtl *idle = nullptr;
-		HIPCHK(hipMalloc(&idle, sizeof(DevCtl)));
-		hipError_t e = hipMemsetAsync(idle, 0, sizeof(DevCtl), c->stream);
-		rc = e == hipSuccess ? enqueue_product(c, !c->right, BLZ_V, BLZ_TMP, false, nullptr, idle) : BLZ_OK;
-		if (e == hipSuccess)
-			e = hipStreamSynchronize(c->stream);
-		hipFree(idle);
-		HIPCHK(e);
-		if (rc != BLZ_OK)
-			return rc;
-	}
-	int nonzero = 0;
-	if ((rc = residual_flag(c, &nonzero)) != BLZ_OK)
-		return rc;
-	if (nonzero) {
-		*status = 2;
-		return BLZ_OK;
-	}
-	std::vector<uint64_t> v((size_t)c->glob_rows[0] * n);
-	if ((rc = blz_get_block(c, BLZ_V, v.data())) != BLZ_OK)
-		return rc;
-	for (int64_t i = 0; i + 1 < c->glob_rows[0]; i++)	/* the border row is the last one in the original numbering */
-		if (owns_row(c, 0, i))		/* (several ranks: the rows this rank owns, like blz_get_block) */
-			x[i] = v[(size_t)i * n];
-	*status = 0;
-	return BLZ_OK;
-}
-
 /* the side-1 product of V with the border applied, past the stop (on control words of its own), tested for zero on the
  * GPU like blz_final_check: *nonzero = some word of it is not zero */
 static int solution_residual(blz_ctx *c, int *nonzero)
@@ -2720,7 +2649,7 @@ static inline uint64_t host_mulmod(uint64_t a, uint64_t b, uint64_t p) { return 
 static int solution_block_reduce(blz_ctx *c, int *status, bool *verified)
 {
 	*verified = false;
-	const int n = c->un, np = c->cfg.n, k = c->rhs_k > 1 ? c->rhs_k : 1;
+	const int n = c->un, np = c->cfg.n, k = c->bd.k;
 	const u64 p = c->prime;
 	int kb = 0;
 	int rc = blz_kernel_basis(c, &kb, nullptr);
@@ -2730,7 +2659,7 @@ static int solution_block_reduce(blz_ctx *c, int *status, bool *verified)
 	 * combination V c has border part W c, and W c = -e_i makes its upper part a solution of system i */
 	const int cols = kb + k;
 	std::vector<uint64_t> A((size_t)k * cols, 0), brow;
-	if ((rc = border_rows_to_host(c, k, brow)) != BLZ_OK)
+	if ((rc = border_rows_to_host(c, brow)) != BLZ_OK)
 		return rc;
 	for (int i = 0; i < k; i++) {
 		for (int j = 0; j < kb; j++)
@@ -2791,24 +2720,48 @@ static int solution_block_reduce(blz_ctx *c, int *status, bool *verified)
 	return BLZ_OK;
 }
 
+/* x <- the k solution columns of V without the border rows (the last k of the original numbering), the rows this rank owns
+ * (several ranks: like blz_get_block) */
+static int solution_to_host(blz_ctx *c, uint64_t *x)
+{
+	const int n = c->un, k = c->bd.k;
+	std::vector<uint64_t> v((size_t)c->glob_rows[0] * n);
+	int rc = blz_get_block(c, BLZ_V, v.data());
+	if (rc != BLZ_OK)
+		return rc;
+	for (int64_t i = 0; i < c->glob_rows[0] - k; i++)
+		for (int j = 0; j < k && owns_row(c, 0, i); j++)
+			x[i * k + j] = v[(size_t)i * n + j];
+	return BLZ_OK;
+}
+
+/* blz_solution_block on one column: with k = 1 the elimination of [W | -1] picks the first basis vector with a non-zero
+ * border word w and scales it by -w^-1.  Its own argument checks, and x stays untouched unless the system is solved. */
+extern "C" int blz_solution(blz_ctx *c, uint64_t *x, int *status)
+{
+	NEED_MATRIX(c);
+	if (!c->bd.rhs || !x || !status)
+		return blz_fail(BLZ_EINVAL, "blz_solution: %s", !c->bd.rhs ? "the context has no right-hand side (blz_set_matrix_rhs)" : "NULL argument");
+	if (c->bd.k > 1)
+		return blz_fail(BLZ_EINVAL, "blz_solution: the context has %d right-hand sides: use blz_solution_block", c->bd.k);
+	bool verified = false;
+	int rc = solution_block_reduce(c, status, &verified);
+	if (rc != BLZ_OK || !verified || *status != 0)
+		return rc;
+	return solution_to_host(c, x);
+}
+
 extern "C" int blz_solution_block(blz_ctx *c, uint64_t *x, int *status)
 {
 	NEED_MATRIX(c);
-	if (!c->rhs || !x || !status)
+	if (!c->bd.rhs || !x || !status)
 		return blz_fail(BLZ_EINVAL, "blz_solution_block: %s",
-				!c->rhs ? "the context has no right-hand side (blz_set_matrix_rhs_block)" : "NULL argument");
-	const int n = c->un, k = c->rhs_k > 1 ? c->rhs_k : 1;
+				!c->bd.rhs ? "the context has no right-hand side (blz_set_matrix_rhs_block)" : "NULL argument");
 	bool verified = false;
 	int rc = solution_block_reduce(c, status, &verified);
 	if (rc != BLZ_OK || !verified)
 		return rc;
-	std::vector<uint64_t> v((size_t)c->glob_rows[0] * n);
-	if ((rc = blz_get_block(c, BLZ_V, v.data())) != BLZ_OK)
-		return rc;
-	for (int64_t i = 0; i < c->glob_rows[0] - k; i++)	/* the border rows are the last k */
-		for (int j = 0; j < k && owns_row(c, 0, i); j++)	/* (several ranks: the rows this rank owns, like blz_get_block) */
-			x[i * k + j] = v[(size_t)i * n + j];
-	return BLZ_OK;
+	return solution_to_host(c, x);
 }
 
 extern "C" int blz_time_kernel(blz_ctx *c, int which, int reps, float *ms_mean)
@@ -2995,7 +2948,7 @@ extern "C" int blz_set_exchange_mode(blz_ctx *c, int external)
 {
 	if (!c)
 		return blz_fail(BLZ_EINVAL, "blz_set_exchange_mode: NULL context");
-	if (external && c->have_matrix && c->rhs && c->rhs_ranks)
+	if (external && c->have_matrix && c->bd.rhs && c->bd.distributed)
 		return blz_fail(BLZ_EINVAL, "blz_set_exchange_mode: the context carries a right-hand side on several ranks (the all-reduce "
 				"of its border words is the library's own)");
 	if (external && c->device_ranks)
@@ -4412,30 +4365,19 @@ static int devrhs_set(blz_ctx *c, const char *who, int k, const W *b, int64_t ld
 	int rc = devrhs_begin(c, who, sizeof(W), stream);
 	if (rc != BLZ_OK || (rc = rhs_block_refuse_k(c, who, k)) != BLZ_OK)
 		return rc;
-	if (c->csr[0].size() != 1 || c->csr[1].size() != 1 || c->short_side[0] || c->short_side[1] || c->glob_rows[0] < k)
-		return blz_fail(BLZ_EINVAL, "%s: the matrix was not set for a single rank in one piece", who);
-	const int64_t first = c->glob_rows[0] - k, len = c->glob_rows[1];
+	if ((rc = rhs_refuse_pieces(c, who, k)) != BLZ_OK)
+		return rc;
+	const int64_t len = c->glob_rows[1];
 	if ((rc = devio_check_range(c, who, "b", b, len, ldb, nullptr, sizeof(W), k)) != BLZ_OK)
 		return rc;
 	HIPCHK(hipStreamSynchronize(c->stream));
-	const int kp = k > 1 ? border_kp(k) : 0, kw = k > 1 ? kp : 1;
-	std::vector<int64_t> rows((size_t)k);
-	{	/* the k border rows / columns of the matrix itself must be empty: the product whose rows live on side 0 says so */
-		const DevCsr &A = c->csr[c->row_side[0] == 0 ? 0 : 1][0];
-		if (A.rows != c->glob_rows[0])
-			return blz_fail(BLZ_EINVAL, "%s: unexpected slab shape", who);
-		for (int i = 0; i < k; i++) {
-			u32 rp[2] = { 0, 0 };
-			rows[(size_t)i] = c->perm[0].empty() ? first + i : c->perm[0][(size_t)(first + i)];
-			HIPCHK(hipMemcpy(rp, A.row_ptr + rows[(size_t)i], sizeof rp, hipMemcpyDeviceToHost));
-			if (rp[0] != rp[1] && k == 1)
-				return blz_fail(BLZ_EINVAL, "%s: the last %s of the matrix must be empty (it stands for the right-hand side)",
-						who, c->right ? "column" : "row");
-			if (rp[0] != rp[1])
-				return blz_fail(BLZ_EINVAL, "%s: the last %d %s of the matrix must be empty (they stand for the right-hand "
-						"sides)", who, k, c->right ? "columns" : "rows");
-		}
-	}
+	const int kw = border_row_words(k);
+	std::vector<int64_t> rows, own;
+	char why[512] = "";
+	if ((rc = border_locate(c, who, k, k == 1, rows, own, why, sizeof why)) != BLZ_OK)
+		return rc;
+	if (why[0])
+		return blz_fail(BLZ_EINVAL, "%s", why);
 	/* the import goes into a fresh buffer, zero filled like the host's: the border that is resident applies until the count
 	 * has been read as zero */
 	DevmatTmp tmp;
@@ -4454,7 +4396,7 @@ static int devrhs_set(blz_ctx *c, const char *who, int k, const W *b, int64_t ld
 		if (e == hipSuccess && len == 0)
 			e = hipMemsetAsync(fresh, 0, fresh_bytes, c->stream);
 		if (e == hipSuccess)
-			e = launch_rhs_import<W>(c->cfg, fresh, b, ldb, c->inv_dev[1], len, k, kp, c->bad_dev, c->stream);
+			e = launch_rhs_import<W>(c->cfg, fresh, b, ldb, c->inv_dev[1], len, k, kw, c->bad_dev, c->stream);
 		rc = e == hipSuccess ? devio_leave(c, caller) : BLZ_OK;
 		const hipError_t e2 = hipStreamSynchronize(c->stream);
 		HIPCHK(e);
@@ -4465,44 +4407,8 @@ static int devrhs_set(blz_ctx *c, const char *who, int k, const W *b, int64_t ld
 	}
 	if (cnt)
 		return blz_fail(BLZ_EINVAL, "%s: %llu words of b are not below p", who, cnt);
-	/* what the host calls leave behind, in their order: everything that can fail first, then the swap */
-	if (k == 1) {
-		if (!c->border_partial)
-			HIPCHK(hipMalloc(&c->border_partial, (size_t)border_dot_max_blocks(c->cfg) * BLZ_BORDER_MAXN * sizeof(u64)));
-	} else {
-		const size_t need = (size_t)border_dot_max_blocks(c->cfg) * kp * BLZ_BORDER_MAXN;
-		if (c->border_partial_words < need) {
-			if (c->border_partial)
-				hipFree(c->border_partial);
-			c->border_partial = nullptr;
-			c->border_partial_words = 0;
-			HIPCHK(hipMalloc(&c->border_partial, need * sizeof(u64)));
-			c->border_partial_words = need;
-		}
-		if (!c->border_rows_dev)
-			HIPCHK(hipMalloc(&c->border_rows_dev, BLZ_MAX_RHS * sizeof(long long)));
-		long long dev_rows[BLZ_MAX_RHS] = { 0 };
-		for (int i = 0; i < k; i++)
-			dev_rows[i] = rows[(size_t)i];
-		HIPCHK(hipMemcpy(c->border_rows_dev, dev_rows, sizeof dev_rows, hipMemcpyHostToDevice));
-	}
-	if (c->rhs)
-		hipFree(c->rhs);
-	c->rhs = fresh;
-	tmp.keep(fresh);
-	c->border = rows[(size_t)k - 1];
-	c->rhs_k = k;
-	c->rhs_kp = kp;
-	if (k == 1)
-		c->border_rows.clear();
-	else
-		c->border_rows = rows;
-	c->fuse_local_off = true;	/* as in blz_set_rhs */
-	if (c->iter_graph) {
-		hipGraphExecDestroy(c->iter_graph);
-		c->iter_graph = nullptr;
-	}
-	return BLZ_OK;
+	tmp.keep(fresh);	/* (border_install's from here on) */
+	return border_install(c, k, rows, nullptr, fresh);
 }
 
 extern "C" int blz_set_rhs_device(blz_ctx *c, int k, const uint64_t *b, int64_t ldb, void *stream)
@@ -4521,11 +4427,11 @@ static int devrhs_solution(blz_ctx *c, const char *who, W *x, int64_t ldx, int *
 	int rc = devrhs_begin(c, who, sizeof(W), stream);
 	if (rc != BLZ_OK)
 		return rc;
-	if (!c->rhs)
+	if (!c->bd.rhs)
 		return blz_fail(BLZ_EINVAL, "%s: the context has no right-hand side (blz_set_rhs_device)", who);
 	if (!status)
 		return blz_fail(BLZ_EINVAL, "%s: status is NULL", who);
-	const int k = c->rhs_k > 1 ? c->rhs_k : 1;
+	const int k = c->bd.k;
 	const int64_t xrows = c->glob_rows[0] - k;
 	if ((rc = devio_check_range(c, who, "x", x, xrows, ldx, nullptr, sizeof(W), k)) != BLZ_OK)
 		return rc;

@@ -887,26 +887,30 @@ class Context:
         check(lib().blz_solution(self.h, ptr(x), C.byref(status)))
         return int(status.value), (x[:self.rows(V) - 1] if status.value == 0 else None)
 
+    @staticmethod
+    def _rhs_block(b, rows):
+        """b as the block and ranks setters hand it over: contiguous uint64, rows x k"""
+        b = np.ascontiguousarray(b, dtype=np.uint64)
+        assert b.ndim == 2 and b.shape[0] == rows, (b.shape, rows)
+        return b
+
     def set_matrix_rhs_block(self, M, b, right=False):
         """blz_set_matrix_rhs_block(): M X = B (right; B is M.nrows x k) or X M = B (B is M.ncols x k), k right-hand sides
         in one bordered operator; rows(V) then counts the k border rows."""
-        b = np.ascontiguousarray(b, dtype=np.uint64)
-        assert b.ndim == 2 and b.shape[0] == (M.nrows if right else M.ncols), (b.shape, M.nrows, M.ncols, right)
+        b = self._rhs_block(b, M.nrows if right else M.ncols)
         self._hand_over_wide(M)
         check(lib().blz_set_matrix_rhs_block(self.h, C.byref(M.c), C.c_int(int(right)), C.c_int(b.shape[1]), ptr(b.reshape(-1))))
         self.right = bool(right)
 
     def set_rhs_block(self, b):
         """blz_set_rhs_block(): the k borders for a matrix already set with the k extra empty last rows / columns."""
-        b = np.ascontiguousarray(b, dtype=np.uint64)
-        assert b.ndim == 2 and b.shape[0] == self.rows(TMP), (b.shape, self.rows(TMP))
+        b = self._rhs_block(b, self.rows(TMP))
         check(lib().blz_set_rhs_block(self.h, C.c_int(b.shape[1]), ptr(b.reshape(-1))))
 
     def set_matrix_rhs_ranks(self, M, b, right=False, rank=0, nranks=1):
         """blz_set_matrix_rhs_ranks(): the bordered operator of set_matrix_rhs_block row-partitioned over nranks ranks (attach
         the communicator first); b is the WHOLE block (M.nrows x k resp. M.ncols x k) on every rank.  Collective."""
-        b = np.ascontiguousarray(b, dtype=np.uint64)
-        assert b.ndim == 2 and b.shape[0] == (M.nrows if right else M.ncols), (b.shape, M.nrows, M.ncols, right)
+        b = self._rhs_block(b, M.nrows if right else M.ncols)
         check(lib().blz_set_matrix_rhs_ranks(self.h, C.byref(M.c), C.c_int(int(right)), C.c_int(b.shape[1]), ptr(b.reshape(-1)),
                                              C.c_int(rank), C.c_int(nranks)))
         self.right = bool(right)
@@ -914,8 +918,7 @@ class Context:
     def set_rhs_ranks(self, b):
         """blz_set_rhs_ranks(): the k borders for a matrix this rank has set with the k extra empty last rows / columns; b is
         the whole rows(TMP) x k block on every rank.  Collective."""
-        b = np.ascontiguousarray(b, dtype=np.uint64)
-        assert b.ndim == 2 and b.shape[0] == self.rows(TMP), (b.shape, self.rows(TMP))
+        b = self._rhs_block(b, self.rows(TMP))
         check(lib().blz_set_rhs_ranks(self.h, C.c_int(b.shape[1]), ptr(b.reshape(-1))))
 
     @property

@@ -870,7 +870,8 @@ int blz_kernel_basis(blz_ctx *ctx, int *k, uint64_t *z);
  * p - 1 (V keeps it in column 0, the other columns zero), recomputes the product of that column with the border applied
  * into TMP and checks on the GPU that it is zero (M x - b), then writes x (blz_rows(ctx, BLZ_V) - 1 words, original
  * numbering, the border row left out).  *status: 0 = solved and verified; 1 = no kernel vector with a non-zero border
- * word (an inconsistent system, or an unlucky start), x untouched; 2 = the verification failed (a bug), x untouched. */
+ * word (an inconsistent system, or an unlucky start), x untouched; 2 = the verification failed (a bug), x untouched.
+ * It is blz_solution_block on one right-hand side: the same status and the same V afterwards (zero where status is 1). */
 int blz_solution(blz_ctx *ctx, uint64_t *x, int *status);
 
 /* The solutions of a context with k = blz_rhs_count(ctx) right-hand sides (k == 1 included), in the same state.  Runs
