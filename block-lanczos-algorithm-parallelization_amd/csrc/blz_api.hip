@@ -237,6 +237,9 @@ struct blz_ctx {
 	bool reorder = true;		/* BLZ_NO_REORDER=1 keeps the file's numbering */
 	bool pack = true;		/* BLZ_NO_PACK=1 keeps col_idx and val as two arrays */
 	bool fuse_dot = true;		/* BLZ_NO_FUSE=1 keeps block_dot as its own kernel (A/B measurements) */
+	bool selfdot = true;		/* BLZ_NO_SELFDOT=1: the iteration never takes the self-dot path (selfdot_path; A/B measurements) */
+	u64 *partial_self = nullptr;	/* partial rows of v^T Av out of the first product on that path: max_self_blocks x n^2 words */
+	int max_self_blocks = 0;
 	bool fuse_local_off = false;	/* this matrix: the second product runs the staged form and block_dot its own kernel (gathers that hit) */
 	int un = 0;			/* the caller's block width; cfg.n is the width in HBM (below) */
 	bool use_graph = false;		/* BLZ_GRAPH=1: single-GPU iterations are replayed from a captured hipGraph */
@@ -493,6 +496,8 @@ extern "C" int blz_create(blz_ctx **out, int device, uint64_t prime, int n)
 	c->reorder = !(nr && nr[0] == '1');
 	const char *nf = getenv("BLZ_NO_FUSE");
 	c->fuse_dot = !(nf && nf[0] == '1');
+	const char *nsf = getenv("BLZ_NO_SELFDOT");
+	c->selfdot = !(nsf && nsf[0] == '1');
 	const char *ug = getenv("BLZ_GRAPH");
 	c->use_graph = ug && ug[0] == '1';
 	const char *xp = getenv("BLZ_EXPLICIT_P");
@@ -520,6 +525,10 @@ extern "C" int blz_create(blz_ctx **out, int device, uint64_t prime, int n)
 	 * outlier launches; the stand-alone kernel keeps the grid it was tuned with */
 	c->max_dot_blocks = c->cfg.num_cu * (np_ <= 8 ? 16 : 8);
 	HIPCHK(hipMalloc(&c->partial, (size_t)c->max_dot_blocks * 2 * np_ * np_ * sizeof(u64)));
+	if (c->selfdot && np_ <= 8) {	/* one row per workgroup of the first product: at most 8 per CU unless the experiment knob asks for more */
+		c->max_self_blocks = c->cfg.num_cu * std::max(8, c->cfg.spmv_blocks_per_cu) + 8;
+		HIPCHK(hipMalloc(&c->partial_self, (size_t)c->max_self_blocks * np_ * np_ * sizeof(u64)));
+	}
 	HIPCHK(hipMalloc(&c->ctl, sizeof(DevCtl)));
 	HIPCHK(hipHostMalloc((void **)&c->ctl_pinned, sizeof(DevCtl), hipHostMallocMapped));
 	HIPCHK(hipHostGetDevicePointer((void **)&c->ctl_pinned_dev, c->ctl_pinned, 0));
@@ -597,6 +606,7 @@ extern "C" void blz_destroy(blz_ctx *c)
 	if (c->cfg.ev_fork) hipEventDestroy(c->cfg.ev_fork);
 	if (c->cfg.ev_join) hipEventDestroy(c->cfg.ev_join);
 	if (c->partial) hipFree(c->partial);
+	if (c->partial_self) hipFree(c->partial_self);
 	if (c->ctl) hipFree(c->ctl);
 	if (c->ctl_pinned) hipHostFree(c->ctl_pinned);
 	if (c->ev0) hipEventDestroy(c->ev0);
@@ -1585,6 +1595,21 @@ static inline bool iteration_fuses(const blz_ctx *c)
 	return c->fuse_dot && !c->fuse_local_off && spmv_dot_supported(c->cfg) && c->count[0] > 0 && !c->short_side[c->right];
 }
 
+/* Does the next blz_iterate take the self-dot path?  Both inner products are then products of a block with itself --
+ * v^T Av = tmp^T tmp out of the first product, v^T A^2 v = Av^T Av out of the second -- and v is not read again.  One kernel
+ * form (the streaming one, no outlier rows, whole rows per lane group) on one kind of context (one rank, no collectives, no
+ * border, one piece per slab, no captured graph); every other case is enqueued as before. */
+static inline bool selfdot_path(const blz_ctx *c)
+{
+	if (!c->selfdot || !c->partial_self || !c->have_matrix || !iteration_fuses(c) || exchanging(c) || c->nranks != 1 || c->bd.rhs
+	    || c->use_graph || c->short_side[0] || c->short_side[1] || c->csr[0].size() != 1 || c->csr[1].size() != 1)
+		return false;
+	return spmv_self_ok(c->cfg, c->csr[!c->right][0], false, c->max_self_blocks)
+	       && spmv_self_ok(c->cfg, c->csr[c->right][0], true, c->max_dot_blocks);
+}
+
+extern "C" int blz_selfdot_active(const blz_ctx *c) { return c && selfdot_path(c) ? 1 : 0; }
+
 static void plan_launch(const SpmvGrids &g, blz_plan_launch *o)
 {
 	o->form = g.form == SPMV_FORM_PANEL ? BLZ_FORM_PANEL : (g.form == SPMV_FORM_STAGED ? BLZ_FORM_STAGED : BLZ_FORM_SPMV);
@@ -2293,8 +2318,26 @@ extern "C" int blz_orthogonalize(blz_ctx *c)
 static int enqueue_iteration(blz_ctx *c)
 {
 	int rc;
-	if ((rc = enqueue_product(c, !c->right, BLZ_V, BLZ_TMP, false, nullptr)) != BLZ_OK) return rc;	/* :635 */
-	if (iteration_fuses(c)) {
+	if (selfdot_path(c)) {
+		/* :635, :636 and :640 in two kernels: each product leaves the inner product of its own output with itself */
+		int nb1 = 0, nb2 = 0;
+		{
+			Span sp(c, PK_SPMV1);
+			HIPCHK(launch_spmv_self(c->cfg, c->csr[!c->right][0], operand_ptr(c, BLZ_V), slab_ptr(c, BLZ_TMP), false,
+						c->partial_self, c->max_self_blocks, &nb1, c->ctl, c->stream));
+		}
+		{
+			Span sp(c, PK_SPMV2);
+			HIPCHK(launch_spmv_self(c->cfg, c->csr[c->right][0], operand_ptr(c, BLZ_TMP), slab_ptr(c, BLZ_AV), true, c->partial,
+						c->max_dot_blocks, &nb2, c->ctl, c->stream));
+		}
+		{
+			Span sp(c, PK_DOT);
+			HIPCHK(launch_dot_finalize_pair(c->cfg, c->partial_self, nb1, c->partial, nb2, c->small, c->ctl, c->stream));
+		}
+	} else if ((rc = enqueue_product(c, !c->right, BLZ_V, BLZ_TMP, false, nullptr)) != BLZ_OK) {	/* :635 */
+		return rc;
+	} else if (iteration_fuses(c)) {
 		int nb = 0;							/* :636 + :640 in one kernel */
 		if ((rc = enqueue_product(c, c->right, BLZ_TMP, BLZ_AV, true, &nb)) != BLZ_OK) return rc;
 		{

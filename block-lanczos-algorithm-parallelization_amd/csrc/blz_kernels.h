@@ -142,6 +142,19 @@ hipError_t launch_block_dot(const KernelCfg &c, const void *V, const void *AV, i
 hipError_t launch_dot_finalize(const KernelCfg &c, const u64 *partial, int nblocks, u64 *out, const DevCtl *ctl,
 			       hipStream_t s);
 
+/* The self forms of the two streaming products of an iteration: Y = A*X and, as the epilogue, partial[b] = this
+ * workgroup's share of Y^T Y (n * n words per row, *nblocks rows).  second = false: k_spmv's grid; true: k_spmv_dot's
+ * (and no operand V is read).  spmv_self_ok: the slab takes the streaming form, has no outlier rows, the first product
+ * does not split rows, and the grid fits max_blocks rows -- launch_spmv_self fails otherwise. */
+bool spmv_self_ok(const KernelCfg &c, const DevCsr &A, bool second, int max_blocks);
+hipError_t launch_spmv_self(const KernelCfg &c, const DevCsr &A, const void *X, void *Y, bool second, u64 *partial,
+			    int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s);
+/* out = [sum of pa's rows | sum of pb's rows] (rows of n * n words); _half: one half of `out` alone, the other untouched */
+hipError_t launch_dot_finalize_pair(const KernelCfg &c, const u64 *pa, int na, const u64 *pb, int nb, u64 *out, const DevCtl *ctl,
+				    hipStream_t s);
+hipError_t launch_dot_finalize_half(const KernelCfg &c, const u64 *partial, int nblocks, u64 *out, int half, const DevCtl *ctl,
+				    hipStream_t s);
+
 /* small: [vtAv | vtAAv | winv | d | c | vtAvd], n*n words each (d: n words, padded to n*n).
  * Reads vtAv/vtAAv (reduced mod p first: they may be sums over ranks), writes the rest and
  * updates ctl.  sequential/lanczos_modp.c:342-438 and :460-475. */

@@ -342,61 +342,12 @@ static void launch_heavy(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, 
 	launch_heavy_as<W, G, MERS, DOT, VM_U32>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
 }
 
-template <typename W, int G, int MERS, bool TAILB, int VM = VM_U32>
+/* the streaming product (defined next to k_spmv_dot, further down: its SELF form shares DotState with it) */
+template <typename W, int G, int MERS, bool TAILB, int VM = VM_U32, bool SELF = false>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__restrict__ va,
        const u32 *__restrict__ vh, const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, long long rows, int n, int split_log2,
-       int accum, u32 heavy, ModP m, XcdRows xr, const DevCtl *__restrict__ ctl)
-{
-	if (ctl->stop)
-		return;
-	__shared__ u32 spal_store[VM == VM_WIDE ? 2 * BLOCK : BLOCK];	/* wide: the 256 low limbs, then the 256 high limbs */
-	const u32 *spal = pal ? spal_store : nullptr;
-	if (pal) {
-		spal_store[threadIdx.x] = pal[threadIdx.x];
-		if (VM == VM_WIDE)
-			spal_store[BLOCK + threadIdx.x] = pal[BLOCK + threadIdx.x];
-	}
-	__syncthreads();
-	const int lane = threadIdx.x & (G - 1);
-	const int xl = lane < n ? lane : 0;
-	/* 2^split_log2 adjacent groups of one wavefront share a row (few, long rows: keeps every CU busy and
-	 * shortens the dependent chain); their 128-bit partial sums are added across lanes before the reduction */
-	const long long gid = ((long long)blockIdx.x * BLOCK + threadIdx.x) / G;
-	const long long g0 = gid >> split_log2;
-	const u32 part = (u32)gid & ((1u << split_log2) - 1u);
-	long long ng = ((long long)gridDim.x * (BLOCK / G)) >> split_log2;
-	long long r = g0;
-	if (xr.begin[0] >= 0) {
-		/* per-XCD row ranges (matrices whose neighbouring rows share columns; split_log2 == 0, grid a multiple of 8):
-		 * blocks b and b + 8 share an XCD, so each L2 serves one contiguous eighth of the rows */
-		const int xcd = blockIdx.x & 7;
-		r = xr.begin[xcd] + ((long long)(blockIdx.x >> 3) * BLOCK + threadIdx.x) / G;
-		rows = xr.begin[xcd + 1];
-		ng = (long long)(gridDim.x >> 3) * (BLOCK / G);
-	}
-	for (; r < rows; r += ng) {
-		u32 k = rp[r], e = rp[r + 1];
-		if (e - k > heavy)	/* left to k_spmv_heavy */
-			continue;
-		if (split_log2) {
-			const u32 len = e - k, per = (len + (1u << split_log2) - 1u) >> split_log2;
-			const u32 lo = k + part * per;
-			k = lo < e ? lo : e;
-			e = (lo + per) < e ? (lo + per) : e;
-		}
-		Acc acc;
-		acc_zero(acc);
-		spmv_accumulate<W, TAILB, VM, MERS>(acc, k, e, ci, va, spal, X, n, xl, m, vh);
-		for (int off = G; off < (G << split_log2); off <<= 1)
-			acc_add_acc(acc, shfl_xor64(acc.lo, off), shfl_xor64(acc.hi, off));
-		if (lane < n && part == 0) {
-			if (accum)		/* column-chunked product: this launch adds to what earlier pieces left in Y */
-				acc_add(acc, Y[(size_t)r * n + lane]);
-			Y[(size_t)r * n + lane] = (W)acc_reduce<MERS>(acc, m);
-		}
-	}
-}
+       int accum, u32 heavy, ModP m, XcdRows xr, const DevCtl *__restrict__ ctl, u64 *__restrict__ partial = nullptr);
 
 static int spmv_split_log2(const KernelCfg &c, int64_t rows, int64_t nnz)
 {
@@ -772,11 +723,16 @@ k_block_dot(const W *__restrict__ V, const W *__restrict__ AV, long long rows, l
  * value in both positions for 0 < t < NT/2 (the totals of the two positions are equal, so the sum over the partial rows
  * is the matrix the reference computes entry by entry); t = NT/2 is computed from both sides, each lane writes its own.
  * 10 MACs per lane and row instead of 13 at n = 8, and three accumulators less in the register-bound fused kernel.
+ * SELF: the product of ONE block with itself, y^T y, and nothing else: the H accumulators of a2, no a1 (N1 = 0), rows
+ * fed by row_self(), and a partial row of NT * NT words only (finish mirrors it as it mirrors a2 otherwise).  Inside the
+ * iteration both inner products are of this kind -- v^T Av = tmp^T tmp out of the first product, v^T A^2 v = Av^T Av out
+ * of the second -- and y^T y is symmetric row by row, so nothing here leans on a total.
  */
-template <typename A, int MERS, int NT, int BS = BLOCK, bool SYM1 = false>
+template <typename A, int MERS, int NT, int BS = BLOCK, bool SYM1 = false, bool SELF = false>
 struct DotState {
-	static constexpr int H = NT / 2 + 1, N1 = SYM1 ? H : NT, SLOTS = N1 + H, WAVES = BS / 64;
-	A a1[N1], a2[H];
+	static constexpr int H = NT / 2 + 1, N1 = SELF ? 0 : (SYM1 ? H : NT), SLOTS = N1 + H, WAVES = BS / 64;
+	static constexpr int WORDS = SELF ? NT * NT : 2 * NT * NT;	/* of a partial row */
+	A a1[N1 ? N1 : 1], a2[H];
 	u32 cnt;
 
 	__device__ __forceinline__ void init()
@@ -825,6 +781,23 @@ struct DotState {
 		}
 	}
 
+	/* SELF: one block row of y, yi = y[r,i]; same rotations, same chunk */
+	__device__ __forceinline__ void row_self(u64 yi, int i, int gbase, const ModP &m)
+	{
+		static_assert(NT <= 8, "the self mode rides on the streaming products: n <= 8");
+#pragma unroll
+		for (int q = 0; q < H; q++) {
+			const u64 yq = q == 0 ? yi : bperm_word<std::is_same<A, AccS>::value>(yi, (gbase + ((i + q) & (NT - 1))) * 4);
+			acc_mac64(a2[q], yi, yq);
+		}
+		if (++cnt == m.chunk) {
+			cnt = 0;
+#pragma unroll
+			for (int q = 0; q < H; q++)
+				acc_set(a2[q], acc_reduce<MERS>(a2[q], m));
+		}
+	}
+
 	/* wave: sum the 64/NT groups; block: sum the waves through LDS; one partial row per block.
 	 * Must be reached by every thread of the block. */
 	__device__ __forceinline__ void finish(u64 (*red)[SLOTS][NT], u64 *__restrict__ partial, const ModP &m, int slot)
@@ -832,7 +805,7 @@ struct DotState {
 		const int t = threadIdx.x, lane = t & 63, i = t & (NT - 1);
 #pragma unroll
 		for (int q = 0; q < SLOTS; q++) {
-			u64 x = q < N1 ? acc_reduce<MERS>(a1[q < N1 ? q : 0], m) : acc_reduce<MERS>(a2[q < N1 ? 0 : q - N1], m);
+			u64 x = q < N1 ? acc_reduce<MERS>(a1[q < N1 ? q : 0], m) : acc_reduce<MERS>(a2[q < N1 ? 0 : q - N1], m);	/* (SELF: N1 = 0) */
 #pragma unroll
 			for (int off = NT; off < 64; off <<= 1)
 				x = addmod(x, shfl_xor64(x, off), m.p);
@@ -846,8 +819,12 @@ struct DotState {
 #pragma unroll
 			for (int w = 0; w < WAVES; w++)
 				x = addmod(x, red[w][q][ii], m.p);
-			u64 *out = partial + (size_t)slot * 2 * NT * NT;
-			if (q < N1) {
+			u64 *out = partial + (size_t)slot * WORDS;
+			if (SELF) {
+				const int jj = (ii + q) & (NT - 1);
+				out[ii * NT + jj] = x;
+				out[jj * NT + ii] = x;
+			} else if (q < N1) {
 				const int jj = (ii + q) & (NT - 1);
 				out[ii * NT + jj] = x;
 				if (SYM1 && q > 0 && 2 * q < NT)	/* (jj, ii) is computed by no lane: same total */
@@ -952,6 +929,85 @@ k_block_dot_64(const W *__restrict__ V, const W *__restrict__ AV, long long rows
 	}
 }
 
+/* SELF (n = G in {1,2,4,8}, split_log2 == 0, a slab without outlier rows -- the host checks, spmv_self_ok): the lane that has
+ * produced Y[r,i] also feeds Y^T Y (DotState's self mode), one partial row of n * n words per workgroup in `partial`.  Inside
+ * the iteration Y = tmp = B^T v and Av = B tmp, so that sum is v^T Av. */
+template <typename W, int G, int MERS, bool TAILB, int VM, bool SELF>
+__global__ void __launch_bounds__(BLOCK)
+k_spmv(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__restrict__ va,
+       const u32 *__restrict__ vh, const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, long long rows, int n, int split_log2,
+       int accum, u32 heavy, ModP m, XcdRows xr, const DevCtl *__restrict__ ctl, u64 *__restrict__ partial)
+{
+	if (ctl->stop)
+		return;
+	using DS = DotState<typename std::conditional<sizeof(W) == 4, AccS, Acc>::type, MERS, SELF ? G : 1, BLOCK, true, true>;
+	__shared__ u64 red[SELF ? DS::WAVES : 1][DS::SLOTS][SELF ? G : 1];
+	__shared__ u32 spal_store[VM == VM_WIDE ? 2 * BLOCK : BLOCK];	/* wide: the 256 low limbs, then the 256 high limbs */
+	const u32 *spal = pal ? spal_store : nullptr;
+	if (pal) {
+		spal_store[threadIdx.x] = pal[threadIdx.x];
+		if (VM == VM_WIDE)
+			spal_store[BLOCK + threadIdx.x] = pal[BLOCK + threadIdx.x];
+	}
+	__syncthreads();
+	const int lane = threadIdx.x & (G - 1);
+	const int xl = lane < n ? lane : 0;
+	/* 2^split_log2 adjacent groups of one wavefront share a row (few, long rows: keeps every CU busy and
+	 * shortens the dependent chain); their 128-bit partial sums are added across lanes before the reduction */
+	const long long gid = ((long long)blockIdx.x * BLOCK + threadIdx.x) / G;
+	const long long g0 = gid >> split_log2;
+	const u32 part = (u32)gid & ((1u << split_log2) - 1u);
+	long long ng = ((long long)gridDim.x * (BLOCK / G)) >> split_log2;
+	long long r = g0;
+	if (xr.begin[0] >= 0) {
+		/* per-XCD row ranges (matrices whose neighbouring rows share columns; split_log2 == 0, grid a multiple of 8):
+		 * blocks b and b + 8 share an XCD, so each L2 serves one contiguous eighth of the rows */
+		const int xcd = blockIdx.x & 7;
+		r = xr.begin[xcd] + ((long long)(blockIdx.x >> 3) * BLOCK + threadIdx.x) / G;
+		rows = xr.begin[xcd + 1];
+		ng = (long long)(gridDim.x >> 3) * (BLOCK / G);
+	}
+	if constexpr (SELF) {
+		const int gbase = (threadIdx.x & 63) - lane;
+		DS ds;
+		ds.init();
+		for (; r < rows; r += ng) {
+			const u32 k = rp[r], e = rp[r + 1];
+			Acc acc;
+			acc_zero(acc);
+			spmv_accumulate<W, TAILB, VM, MERS>(acc, k, e, ci, va, spal, X, G, lane, m, vh);
+			if (accum)
+				acc_add(acc, Y[(size_t)r * G + lane]);
+			const u64 y = acc_reduce<MERS>(acc, m);
+			Y[(size_t)r * G + lane] = (W)y;
+			ds.row_self(y, lane, gbase, m);
+		}
+		ds.finish(red, partial, m, (int)blockIdx.x);
+		return;
+	}
+	for (; r < rows; r += ng) {
+		u32 k = rp[r], e = rp[r + 1];
+		if (e - k > heavy)	/* left to k_spmv_heavy */
+			continue;
+		if (split_log2) {
+			const u32 len = e - k, per = (len + (1u << split_log2) - 1u) >> split_log2;
+			const u32 lo = k + part * per;
+			k = lo < e ? lo : e;
+			e = (lo + per) < e ? (lo + per) : e;
+		}
+		Acc acc;
+		acc_zero(acc);
+		spmv_accumulate<W, TAILB, VM, MERS>(acc, k, e, ci, va, spal, X, n, xl, m, vh);
+		for (int off = G; off < (G << split_log2); off <<= 1)
+			acc_add_acc(acc, shfl_xor64(acc.lo, off), shfl_xor64(acc.hi, off));
+		if (lane < n && part == 0) {
+			if (accum)		/* column-chunked product: this launch adds to what earlier pieces left in Y */
+				acc_add(acc, Y[(size_t)r * n + lane]);
+			Y[(size_t)r * n + lane] = (W)acc_reduce<MERS>(acc, m);
+		}
+	}
+}
+
 /*
  * Second SpMV of an iteration (Av = M tmp, sequential/lanczos_modp.c:636) with block_dot_products (:640) as its
  * epilogue: the lane that has just produced Av[r,i] loads v[r,i] and feeds both products.  The SpMV is bound by
@@ -960,7 +1016,10 @@ k_block_dot_64(const W *__restrict__ V, const W *__restrict__ AV, long long rows
  * per lane cost more occupancy than the saved pass is worth (measured: 15.8 ms fused against 12.4 + 2.3 ms apart on
  * the config-5 shape), so that width runs k_spmv and k_block_dot_fast.
  */
-template <typename W, int MERS, int NT, bool TAILB, int VM = VM_U32>
+/* SELF: inside the iteration v^T Av has come out of the first product already (k_spmv's SELF form), so this one
+ * accumulates Av^T Av only -- five MACs per lane and row at n = 8 instead of ten, a partial row of n * n words -- and does
+ * not touch Vd. */
+template <typename W, int MERS, int NT, bool TAILB, int VM = VM_U32, bool SELF = false>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_dot(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__restrict__ va,
 	   const u32 *__restrict__ vh, const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, const W *__restrict__ Vd,
@@ -969,7 +1028,7 @@ k_spmv_dot(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__
 {
 	if (ctl->stop)
 		return;
-	using DS = DotState<typename std::conditional<sizeof(W) == 4, AccS, Acc>::type, MERS, NT, BLOCK, true>;
+	using DS = DotState<typename std::conditional<sizeof(W) == 4, AccS, Acc>::type, MERS, NT, BLOCK, true, SELF>;
 	__shared__ u64 red[DS::WAVES][DS::SLOTS][NT];
 	__shared__ u32 spal_store[VM == VM_WIDE ? 2 * BLOCK : BLOCK];	/* wide: the 256 low limbs, then the 256 high limbs */
 	const u32 *spal = pal ? spal_store : nullptr;
@@ -994,7 +1053,9 @@ k_spmv_dot(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__
 		const u32 k = rp[r], e = rp[r + 1];
 		if (e - k > heavy)	/* row and its share of the inner products: k_spmv_heavy */
 			continue;
-		const u64 vi = Vd[(size_t)r * NT + lane];
+		u64 vi = 0;
+		if constexpr (!SELF)
+			vi = Vd[(size_t)r * NT + lane];
 		Acc acc;
 		acc_zero(acc);
 		spmv_accumulate<W, TAILB, VM, MERS>(acc, k, e, ci, va, spal, X, NT, lane, m, vh);
@@ -1002,7 +1063,10 @@ k_spmv_dot(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__
 			acc_add(acc, Y[(size_t)r * NT + lane]);
 		const u64 y = acc_reduce<MERS>(acc, m);
 		Y[(size_t)r * NT + lane] = (W)y;
-		ds.row(vi, y, lane, gbase, m);
+		if constexpr (SELF)
+			ds.row_self(y, lane, gbase, m);
+		else
+			ds.row(vi, y, lane, gbase, m);
 	}
 	ds.finish(red, partial, m, (int)blockIdx.x);
 }
@@ -1209,6 +1273,86 @@ static hipError_t spmv_dot_dispatch(const KernelCfg &c, const DevCsr &A, const W
 bool spmv_dot_supported(const KernelCfg &c)
 {
 	return c.n == 1 || c.n == 2 || c.n == 4 || c.n == 8;
+}
+
+/* The self forms of the two streaming products (k_spmv / k_spmv_dot with SELF): same grids, same row walk, same value
+ * modes as the plain launches; partial rows of n * n words, one per workgroup. */
+bool spmv_self_ok(const KernelCfg &c, const DevCsr &A, bool second, int max_blocks)
+{
+	if (!spmv_dot_supported(c) || A.rows <= 0 || A.n_heavy || A.n_medium || A.n_multi || spmv_form(c, A, second) != SPMV_FORM_STREAM)
+		return false;
+	const SpmvGrids g = second ? stream_dot_grids(c, A, max_blocks) : stream_grids(c, A);
+	return g.ok && g.split_log2 == 0 && g.blocks >= 1 && g.blocks <= max_blocks && !g.hb && !g.cb && !g.mb;
+}
+
+template <typename W, int MERS>
+static hipError_t spmv_self_dispatch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, bool second, u64 *partial,
+				     int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s)
+{
+	if (!spmv_self_ok(c, A, second, max_blocks))
+		return hipErrorInvalidValue;
+	const SpmvGrids g = second ? stream_dot_grids(c, A, max_blocks) : stream_grids(c, A);
+	const long long blocks = g.blocks;
+	XcdRows xr;
+	xr.begin[0] = -1;
+	if (g.xcd)
+		for (int x = 0; x < 9; x++)
+			xr.begin[x] = A.xr_rows[x];
+	*nblocks = (int)blocks;
+	const bool sgn = sizeof(W) == 8 && A.sgn, wide = sizeof(W) == 8 && A.wide;
+#define SPMV_SELF_GO(NN, TT, SS)                                                                                     \
+	do {                                                                                                         \
+		if (second)                                                                                          \
+			hipLaunchKernelGGL((k_spmv_dot<W, MERS, NN, TT, SS, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s,  \
+					   A.row_ptr, A.col_idx, A.val, A.val_hi, A.palette, X, Y, (const W *)nullptr,     \
+					   (long long)A.rows, 0, A.heavy_thr, c.m, partial, xr, ctl);                      \
+		else                                                                                                 \
+			hipLaunchKernelGGL((k_spmv<W, NN, MERS, TT, SS, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s,      \
+					   A.row_ptr, A.col_idx, A.val, A.val_hi, A.palette, X, Y, (long long)A.rows, NN, 0, 0, \
+					   A.heavy_thr, c.m, xr, ctl, partial);                                            \
+	} while (0)
+#define SPMV_SELF(NN)                                                                                               \
+	case NN:                                                                                                    \
+		if (wide) {                                                                                         \
+			if constexpr (sizeof(W) == 8) {                                                             \
+				if (A.tail_batch)                                                                   \
+					SPMV_SELF_GO(NN, true, VM_WIDE);                                            \
+				else                                                                                \
+					SPMV_SELF_GO(NN, false, VM_WIDE);                                           \
+			}                                                                                           \
+		} else if (sgn) {                                                                                   \
+			if constexpr (sizeof(W) == 8) {                                                             \
+				if (A.tail_batch)                                                                   \
+					SPMV_SELF_GO(NN, true, VM_SIGNED);                                          \
+				else                                                                                \
+					SPMV_SELF_GO(NN, false, VM_SIGNED);                                         \
+			}                                                                                           \
+		} else if (A.tail_batch)                                                                            \
+			SPMV_SELF_GO(NN, true, VM_U32);                                                             \
+		else                                                                                                \
+			SPMV_SELF_GO(NN, false, VM_U32);                                                            \
+		break;
+	switch (c.n) {
+		SPMV_SELF(1)
+		SPMV_SELF(2)
+		SPMV_SELF(4)
+		SPMV_SELF(8)
+	default:
+		return hipErrorInvalidValue;
+	}
+#undef SPMV_SELF
+#undef SPMV_SELF_GO
+	return hipGetLastError();
+}
+
+hipError_t launch_spmv_self(const KernelCfg &c, const DevCsr &A, const void *X, void *Y, bool second, u64 *partial,
+			    int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s)
+{
+	if (c.word == 4)
+		return c.mers == 31 ? spmv_self_dispatch<u32, 31>(c, A, (const u32 *)X, (u32 *)Y, second, partial, max_blocks, nblocks, ctl, s)
+				    : spmv_self_dispatch<u32, 0>(c, A, (const u32 *)X, (u32 *)Y, second, partial, max_blocks, nblocks, ctl, s);
+	return c.mers == 61 ? spmv_self_dispatch<u64, 61>(c, A, (const u64 *)X, (u64 *)Y, second, partial, max_blocks, nblocks, ctl, s)
+			    : spmv_self_dispatch<u64, 0>(c, A, (const u64 *)X, (u64 *)Y, second, partial, max_blocks, nblocks, ctl, s);
 }
 
 hipError_t launch_spmv_dot(const KernelCfg &c, const DevCsr &A, const void *X, void *Y, const void *Vd, int accum,
@@ -2101,14 +2245,26 @@ hipError_t launch_block_dot(const KernelCfg &c, const void *V, const void *AV, i
 #define FIN_THREADS 1024
 __global__ void __launch_bounds__(FIN_THREADS)
 k_dot_finalize(const u64 *__restrict__ partial, int nblocks, int words, int cw_log2, u64 p, u64 *__restrict__ out,
-	       const DevCtl *__restrict__ ctl)
+	       const DevCtl *__restrict__ ctl, const u64 *__restrict__ partial_b = nullptr, int nblocks_b = 0)
 {
 	if (ctl->stop)
 		return;
 	__shared__ u64 part[FIN_THREADS / 64][8];
 	const int CW = 1 << cw_log2, RL = 64 >> cw_log2;
 	const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, wl = lane & (CW - 1), rl = lane >> cw_log2;
-	const int e = blockIdx.x * CW + wl, step = (FIN_THREADS / 64) * RL;
+	const int eo = blockIdx.x * CW + wl, step = (FIN_THREADS / 64) * RL;
+	int e = eo;
+	if (partial_b) {
+		/* the two halves of the output come from two sets of partial rows of words / 2 words each (the self forms of the
+		 * two products): the first from `partial`, the second from `partial_b`.  (One half alone, the other left as it is:
+		 * a launch over that half's words, launch_dot_finalize_half.) */
+		words >>= 1;
+		if (e >= words) {
+			e -= words;
+			partial = partial_b;
+			nblocks = nblocks_b;
+		}
+	}
 	u64 s = 0;
 	int b = wave * RL + rl;
 	for (; b + 7 * step < nblocks; b += 8 * step) {	/* eight independent loads in flight, then the adds */
@@ -2132,7 +2288,7 @@ k_dot_finalize(const u64 *__restrict__ partial, int nblocks, int words, int cw_l
 #pragma unroll
 		for (int w = 0; w < FIN_THREADS / 64; w++)
 			t = addmod(t, part[w][threadIdx.x], p);
-		out[e] = t;
+		out[eo] = t;
 	}
 }
 
@@ -2144,7 +2300,33 @@ hipError_t launch_dot_finalize(const KernelCfg &c, const u64 *partial, int nbloc
 	while ((words & ((1 << cw_log2) - 1)) != 0)
 		cw_log2--;
 	hipLaunchKernelGGL(k_dot_finalize, dim3(words >> cw_log2), dim3(FIN_THREADS), 0, s, partial, nblocks, words, cw_log2, c.m.p, out,
-			   ctl);
+			   ctl, (const u64 *)nullptr, 0);
+	return hipGetLastError();
+}
+
+/* out[0, n*n) from the rows of `pa`, out[n*n, 2n*n) from the rows of `pb`: rows of n * n words (the self forms) */
+hipError_t launch_dot_finalize_pair(const KernelCfg &c, const u64 *pa, int na, const u64 *pb, int nb, u64 *out, const DevCtl *ctl,
+				    hipStream_t s)
+{
+	const int words = 2 * c.n * c.n;
+	int cw_log2 = 3;
+	while ((words & ((1 << cw_log2) - 1)) != 0)
+		cw_log2--;
+	hipLaunchKernelGGL(k_dot_finalize, dim3(words >> cw_log2), dim3(FIN_THREADS), 0, s, pa, na, words, cw_log2, c.m.p, out, ctl, pb,
+			   nb);
+	return hipGetLastError();
+}
+
+/* one half alone: out[half * n*n, (half + 1) * n*n) from rows of n * n words; the other half of `out` is not touched */
+hipError_t launch_dot_finalize_half(const KernelCfg &c, const u64 *partial, int nblocks, u64 *out, int half, const DevCtl *ctl,
+				    hipStream_t s)
+{
+	const int words = c.n * c.n;
+	int cw_log2 = 3;
+	while ((words & ((1 << cw_log2) - 1)) != 0)
+		cw_log2--;
+	hipLaunchKernelGGL(k_dot_finalize, dim3(words >> cw_log2), dim3(FIN_THREADS), 0, s, partial, nblocks, words, cw_log2, c.m.p,
+			   out + (size_t)half * words, ctl, (const u64 *)nullptr, 0);
 	return hipGetLastError();
 }
 

@@ -1418,6 +1418,11 @@ class Context:
         """blz_p_implicit(): 1 while the iteration keeps p as X * E, 0 when the P block holds p itself (test hook)."""
         return int(lib().blz_p_implicit(self.h))
 
+    @property
+    def selfdot_active(self):
+        """blz_selfdot_active(): 1 when the next iterate() takes both inner products from the products' own outputs."""
+        return int(lib().blz_selfdot_active(self.h))
+
     def set_iterations(self, its):
         check(lib().blz_set_iterations(self.h, C.c_int64(its)))
 

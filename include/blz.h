@@ -842,6 +842,13 @@ int64_t blz_iterations(const blz_ctx *ctx);
  * P block holds p itself.  Every call that looks at P (blz_get_block, blz_snapshot_begin, blz_orthogonalize, ...) makes
  * it explicit first; blz_set_block(P) makes it explicit. */
 int blz_p_implicit(const blz_ctx *ctx);
+/* Read-only: 1 when the next blz_iterate takes the self-dot path -- both inner products as products of a block with itself
+ * (v^T Av = tmp^T tmp in the first product's kernel, v^T A^2 v = Av^T Av in the second's), v not read again -- and 0 when it
+ * enqueues the step the other way.  The path needs: the fused second product (n in {1,2,4,8}, not BLZ_NO_FUSE=1), one rank
+ * without collectives, no right-hand side, one piece per slab, both slabs in the streaming form without outlier rows, whole
+ * rows per lane group in the first product, no BLZ_GRAPH=1, and not BLZ_NO_SELFDOT=1 (read when the context is created).
+ * The results are the same words either way. */
+int blz_selfdot_active(const blz_ctx *ctx);
 int blz_set_iterations(blz_ctx *ctx, int64_t iterations);	/* --load-checkpoint */
 
 /* final_check(), :560-582, on V and on TMP (= M^T v of the last iteration). */
