@@ -255,17 +255,10 @@ hipError_t launch_border_update(const KernelCfg &c, void *T, const void *B, cons
 		return hipErrorInvalidValue;
 	if (rows <= 0)
 		return hipSuccess;
-	if (c.word == 4) {
-		if (c.mers == 31)
-			border_update_go<u32, 31>(c, (u32 *)T, (const u32 *)B, (const u32 *)vb, rows, ctl, s);
-		else
-			border_update_go<u32, 0>(c, (u32 *)T, (const u32 *)B, (const u32 *)vb, rows, ctl, s);
-	} else {
-		if (c.mers == 61)
-			border_update_go<u64, 61>(c, (u64 *)T, (const u64 *)B, (const u64 *)vb, rows, ctl, s);
-		else
-			border_update_go<u64, 0>(c, (u64 *)T, (const u64 *)B, (const u64 *)vb, rows, ctl, s);
-	}
+	with_word_reducer(c, [&](auto wt, auto mers) {
+		using W = typename decltype(wt)::type;
+		border_update_go<W, decltype(mers)::value>(c, (W *)T, (const W *)B, (const W *)vb, rows, ctl, s);
+	});
 	return hipGetLastError();
 }
 
@@ -279,25 +272,13 @@ static hipError_t border_dot_go(const KernelCfg &c, const void *T, const void *B
 	long long blocks = (rows + (long long)gpb * 4 - 1) / ((long long)gpb * 4);
 	blocks = blocks < 1 ? 1 : (blocks > border_dot_max_blocks(c) ? border_dot_max_blocks(c) : blocks);
 	const dim3 grid((unsigned)blocks), blk(BLOCK);
-	if (c.word == 4) {
-		if (c.mers == 31)
-			hipLaunchKernelGGL((k_border_dot<u32, 31>), grid, blk, 0, s, (const u32 *)T, (const u32 *)B, (long long)rows, n, G, c.m,
-					   partial, ctl);
-		else
-			hipLaunchKernelGGL((k_border_dot<u32, 0>), grid, blk, 0, s, (const u32 *)T, (const u32 *)B, (long long)rows, n, G, c.m,
-					   partial, ctl);
+	with_word_reducer(c, [&](auto wt, auto mers) {
+		using W = typename decltype(wt)::type;
+		hipLaunchKernelGGL((k_border_dot<W, decltype(mers)::value>), grid, blk, 0, s, (const W *)T, (const W *)B, (long long)rows, n, G,
+				   c.m, partial, ctl);
 		if (!send)
-			hipLaunchKernelGGL((k_border_finalize<u32>), dim3(1), blk, 0, s, partial, (int)blocks, n, G, c.m.p, (u32 *)out_row, ctl);
-	} else {
-		if (c.mers == 61)
-			hipLaunchKernelGGL((k_border_dot<u64, 61>), grid, blk, 0, s, (const u64 *)T, (const u64 *)B, (long long)rows, n, G, c.m,
-					   partial, ctl);
-		else
-			hipLaunchKernelGGL((k_border_dot<u64, 0>), grid, blk, 0, s, (const u64 *)T, (const u64 *)B, (long long)rows, n, G, c.m,
-					   partial, ctl);
-		if (!send)
-			hipLaunchKernelGGL((k_border_finalize<u64>), dim3(1), blk, 0, s, partial, (int)blocks, n, G, c.m.p, (u64 *)out_row, ctl);
-	}
+			hipLaunchKernelGGL((k_border_finalize<W>), dim3(1), blk, 0, s, partial, (int)blocks, n, G, c.m.p, (W *)out_row, ctl);
+	});
 	if (send)
 		hipLaunchKernelGGL(k_border_finalize_send, dim3(1), blk, 0, s, partial, (int)blocks, n, G, 1, c.m.p, send, ctl);
 	return hipGetLastError();
@@ -511,22 +492,14 @@ template <typename W, int MERS>
 static hipError_t border_k_kp(const KernelCfg &c, bool update, void *T, const void *B, void *S, const long long *brow, int k,
 			      long long rows, u64 *partial, u64 *send, const DevCtl *ctl, hipStream_t s)
 {
-#define BORDER_K_CASE(KP) \
-	case KP: \
-		if (update) \
-			border_update_k_go<W, MERS, KP>(c, (W *)T, (const W *)B, (const W *)S, brow, k, rows, ctl, s); \
-		else \
-			border_dot_k_go<W, MERS, KP>(c, (const W *)T, (const W *)B, rows, partial, (W *)S, brow, k, send, ctl, s); \
-		break
-	switch (border_kp(k)) {
-	BORDER_K_CASE(2);
-	BORDER_K_CASE(4);
-	BORDER_K_CASE(8);
-	BORDER_K_CASE(16);
-	default: return hipErrorInvalidValue;
-	}
-#undef BORDER_K_CASE
-	return hipGetLastError();
+	const bool known = with_lane_group<2, 4, 8, 16>(border_kp(k), [&](auto kt) {
+		constexpr int KP = decltype(kt)::value;
+		if (update)
+			border_update_k_go<W, MERS, KP>(c, (W *)T, (const W *)B, (const W *)S, brow, k, rows, ctl, s);
+		else
+			border_dot_k_go<W, MERS, KP>(c, (const W *)T, (const W *)B, rows, partial, (W *)S, brow, k, send, ctl, s);
+	});
+	return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 static hipError_t border_k(const KernelCfg &c, bool update, void *T, const void *B, void *S, const long long *brow, int k,
@@ -536,11 +509,9 @@ static hipError_t border_k(const KernelCfg &c, bool update, void *T, const void 
 		return hipErrorInvalidValue;
 	if (update && rows <= 0)
 		return hipSuccess;
-	if (c.word == 4)
-		return c.mers == 31 ? border_k_kp<u32, 31>(c, update, T, B, S, brow, k, rows, partial, send, ctl, s)
-				    : border_k_kp<u32, 0>(c, update, T, B, S, brow, k, rows, partial, send, ctl, s);
-	return c.mers == 61 ? border_k_kp<u64, 61>(c, update, T, B, S, brow, k, rows, partial, send, ctl, s)
-			    : border_k_kp<u64, 0>(c, update, T, B, S, brow, k, rows, partial, send, ctl, s);
+	return with_word_reducer(c, [&](auto wt, auto mers) {
+		return border_k_kp<typename decltype(wt)::type, decltype(mers)::value>(c, update, T, B, S, brow, k, rows, partial, send, ctl, s);
+	});
 }
 
 hipError_t launch_border_update_k(const KernelCfg &c, void *T, const void *B, const void *V, const long long *brow, int k,

@@ -3,6 +3,7 @@
 #define BLZ_KERNELS_H
 
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "modp.h"
 
 /* Outlier rows of a slab (more than heavy_thr entries), cut into segments of at most HEAVY_SEG entries. */
@@ -234,5 +235,63 @@ __host__ __device__ constexpr size_t small_Emat(int n) { return (size_t)7 * n * 
 __host__ __device__ constexpr size_t small_skip_p(int n) { return (size_t)8 * n * n; }		/* this step writes no p' */
 __host__ __device__ constexpr size_t small_materialize(int n) { return (size_t)8 * n * n + 1; }	/* this step needs X <- X * Emat first */
 __host__ __device__ constexpr size_t small_words(int n) { return (size_t)8 * n * n + 8; }
+
+/* ------------------------------------------------------------------ choosing a kernel instance (host side)
+ * Every launch asks the same few questions of the context and the slab.  Each helper answers one of them and calls the
+ * generic lambda f with the answer as tag values, so the launch at the call site is ordinary C++ with
+ * decltype(tag)::value as template arguments.  A combination that has no kernel is never offered: the classes that exist
+ * for 64-bit words only sit behind `if constexpr (sizeof(W) == 8)` here, and a call site guards what is its own (the
+ * widths of a form) on the tags in the same way. */
+#ifdef __cplusplus
+template <typename T> struct TypeTag { using type = T; };
+template <int V> using IntTag = std::integral_constant<int, V>;
+template <bool V> using BoolTag = std::integral_constant<bool, V>;
+/* the helpers melt into the launcher that calls them: the choice compiles to the branches a hand-written ladder has */
+#define DISPATCH_INLINE static inline __attribute__((always_inline))
+
+/* word width and reducer class: f(TypeTag<W>, IntTag<MERS>) for <u32, 31>, <u32, 0>, <u64, 61>, <u64, 0>; returns f's result */
+template <typename F> DISPATCH_INLINE auto with_word_reducer(const KernelCfg &c, F &&f)
+{
+	if (c.word == 4)
+		return c.mers == 31 ? f(TypeTag<u32>{}, IntTag<31>{}) : f(TypeTag<u32>{}, IntTag<0>{});
+	return c.mers == 61 ? f(TypeTag<u64>{}, IntTag<61>{}) : f(TypeTag<u64>{}, IntTag<0>{});
+}
+
+/* lane group or block width: f(IntTag<G>) for the member of Gs equal to G; false when there is none (f was not called) */
+template <int... Gs, typename F> DISPATCH_INLINE bool with_lane_group(int G, F &&f)
+{
+	return ((G == Gs ? (f(IntTag<Gs>{}), true) : false) || ...);
+}
+
+/* value class of a slab in the streaming kernels: f(IntTag<VM>, BoolTag<TAILB>) */
+template <typename W, typename F> DISPATCH_INLINE void with_value_mode(const DevCsr &A, F &&f)
+{
+	auto tail = [&](auto vm) { A.tail_batch ? f(vm, BoolTag<true>{}) : f(vm, BoolTag<false>{}); };
+	if constexpr (sizeof(W) == 8) {		/* DevCsr::wide and DevCsr::sgn are never set on a slab of 4-byte words, and never both */
+		if (A.wide)
+			return tail(IntTag<VM_WIDE>{});
+		if (A.sgn)
+			return tail(IntTag<VM_SIGNED>{});
+	}
+	tail(IntTag<VM_U32>{});
+}
+
+/* value stream of a slab in the staged and panel kernels: f(IntTag<VALS>, BoolTag<SGN>) */
+enum { V_ONES = 0, V_PACKED = 1, V_ARRAY = 2 };
+template <typename W, typename F> DISPATCH_INLINE void with_stream_values(const DevCsr &A, F &&f)
+{
+	const int vals = A.palette ? V_PACKED : (A.val ? V_ARRAY : V_ONES);
+	if constexpr (sizeof(W) == 8) {
+		if (A.sgn && vals != V_ONES)
+			return vals == V_PACKED ? f(IntTag<V_PACKED>{}, BoolTag<true>{}) : f(IntTag<V_ARRAY>{}, BoolTag<true>{});
+	}
+	if (vals == V_PACKED)
+		f(IntTag<V_PACKED>{}, BoolTag<false>{});
+	else if (vals == V_ARRAY)
+		f(IntTag<V_ARRAY>{}, BoolTag<false>{});
+	else
+		f(IntTag<V_ONES>{}, BoolTag<false>{});
+}
+#endif
 
 #endif

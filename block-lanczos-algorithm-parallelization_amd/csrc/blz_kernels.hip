@@ -329,17 +329,9 @@ template <typename W, int G, int MERS, bool DOT>
 static void launch_heavy(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum, u64 *partial,
 			 int slot0, long long hb, const DevCtl *ctl, hipStream_t main_stream)
 {
-	if constexpr (sizeof(W) == 8) {
-		if (A.wide) {
-			launch_heavy_as<W, G, MERS, DOT, VM_WIDE>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
-			return;
-		}
-		if (A.sgn) {
-			launch_heavy_as<W, G, MERS, DOT, VM_SIGNED>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
-			return;
-		}
-	}
-	launch_heavy_as<W, G, MERS, DOT, VM_U32>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
+	with_value_mode<W>(A, [&](auto vm, auto) {	/* (the outlier kernels have no tail batch) */
+		launch_heavy_as<W, G, MERS, DOT, decltype(vm)::value>(c, A, X, Y, Vd, accum, partial, slot0, hb, ctl, main_stream);
+	});
 }
 
 /* the streaming product (defined next to k_spmv_dot, further down: its SELF form shares DotState with it) */
@@ -349,11 +341,27 @@ k_spmv(const u32 *__restrict__ rp, const int *__restrict__ ci, const u32 *__rest
        const u32 *__restrict__ vh, const u32 *__restrict__ pal, const W *__restrict__ X, W *__restrict__ Y, long long rows, int n, int split_log2,
        int accum, u32 heavy, ModP m, XcdRows xr, const DevCtl *__restrict__ ctl, u64 *__restrict__ partial = nullptr);
 
-static int spmv_split_log2(const KernelCfg &c, int64_t rows, int64_t nnz)
+/* lanes per row: the block width rounded up to a power of two */
+static inline int lane_group(const KernelCfg &c)
 {
 	int G = 1;
 	while (G < c.n)
 		G <<= 1;
+	return G;
+}
+
+/* the lane groups a product has kernels for: the fused forms exist for 1, 2, 4 and 8 lanes only */
+template <bool DOT, typename F> DISPATCH_INLINE bool with_product_lanes(int G, F &&f)
+{
+	if constexpr (DOT)
+		return with_lane_group<1, 2, 4, 8>(G, f);
+	else
+		return with_lane_group<1, 2, 4, 8, 16, 32, 64>(G, f);
+}
+
+static int spmv_split_log2(const KernelCfg &c, int64_t rows, int64_t nnz)
+{
+	const int G = lane_group(c);
 	const long long groups_per_block = BLOCK / G;
 	const double avg = rows ? (double)nnz / (double)rows : 0.0;
 	int split_log2 = 0;
@@ -376,12 +384,15 @@ u32 spmv_heavy_threshold(const KernelCfg &c, int64_t rows, int64_t nnz)
  * What the dispatch functions below launch for a slab, computed in one place: they call these, and so does the
  * read-only plan hook (spmv_grids), so a test that reads the plan reads the launch. */
 
-static inline int lane_group(const KernelCfg &c)
+/* the row ranges k_spmv / k_spmv_dot walk: the slab's per-XCD ranges where the grid was sized for them, else none */
+static inline XcdRows xcd_rows(const DevCsr &A, bool xcd)
 {
-	int G = 1;
-	while (G < c.n)
-		G <<= 1;
-	return G;
+	XcdRows xr;
+	xr.begin[0] = -1;
+	if (xcd)
+		for (int x = 0; x < 9; x++)
+			xr.begin[x] = A.xr_rows[x];
+	return xr;
 }
 
 /* the outlier launches of a fused product: one partial row per workgroup of each */
@@ -566,68 +577,28 @@ static hipError_t spmv_dispatch(const KernelCfg &c, const DevCsr &A, const W *X,
 		return panel_dispatch<W, MERS, false>(c, A, X, Y, (const W *)nullptr, accum, (u64 *)nullptr, 0, (int *)nullptr, ctl, s);
 	if (form == SPMV_FORM_STAGED)
 		return staged_dispatch<W, MERS, false>(c, A, X, Y, (const W *)nullptr, accum, (u64 *)nullptr, 0, (int *)nullptr, ctl, s);
-	const int G = lane_group(c);
 	const SpmvGrids g = stream_grids(c, A);
-	const long long blocks = g.blocks;
-	const int split_log2 = g.split_log2;
-	XcdRows xr;
-	xr.begin[0] = -1;
-	if (g.xcd)
-		for (int x = 0; x < 9; x++)
-			xr.begin[x] = A.xr_rows[x];
-	const bool sgn = sizeof(W) == 8 && A.sgn, wide = sizeof(W) == 8 && A.wide;
-#define SPMV_GO(GG, TT, SS)                                                                                     \
-	hipLaunchKernelGGL((k_spmv<W, GG, MERS, TT, SS>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, A.row_ptr,          \
-			   A.col_idx, A.val, A.val_hi, A.palette, X, Y, (long long)A.rows, c.n, split_log2, accum,                  \
-			   A.heavy_thr, c.m, xr, ctl)
-#define SPMV_CASE(GG)                                                                                           \
-	case GG:                                                                                                  \
-		if (wide) {                                                                                       \
-			if constexpr (sizeof(W) == 8) {                                                           \
-				if (A.tail_batch)                                                                 \
-					SPMV_GO(GG, true, VM_WIDE);                                               \
-				else                                                                              \
-					SPMV_GO(GG, false, VM_WIDE);                                              \
-			}                                                                                         \
-		} else if (sgn) {                                                                                 \
-			if constexpr (sizeof(W) == 8) {                                                           \
-				if (A.tail_batch)                                                                 \
-					SPMV_GO(GG, true, VM_SIGNED);                                             \
-				else                                                                              \
-					SPMV_GO(GG, false, VM_SIGNED);                                            \
-			}                                                                                         \
-		} else if (A.tail_batch)                                                                          \
-			SPMV_GO(GG, true, VM_U32);                                                                \
-		else                                                                                              \
-			SPMV_GO(GG, false, VM_U32);                                                               \
-		if (A.n_heavy || A.n_medium)                                                                      \
-			launch_heavy<W, GG, MERS, false>(c, A, X, Y, (const W *)nullptr, accum, (u64 *)nullptr, 0,   \
-							 g.hb, ctl, s);                                               \
-		break;
-	switch (G) {
-		SPMV_CASE(1)
-		SPMV_CASE(2)
-		SPMV_CASE(4)
-		SPMV_CASE(8)
-		SPMV_CASE(16)
-		SPMV_CASE(32)
-		SPMV_CASE(64)
-	default:
-		return hipErrorInvalidValue;
-	}
-#undef SPMV_CASE
-#undef SPMV_GO
-	return hipGetLastError();
+	const XcdRows xr = xcd_rows(A, g.xcd);
+	const bool known = with_lane_group<1, 2, 4, 8, 16, 32, 64>(lane_group(c), [&](auto gt) {
+		constexpr int G = decltype(gt)::value;
+		with_value_mode<W>(A, [&](auto vm, auto tailb) {
+			hipLaunchKernelGGL((k_spmv<W, G, MERS, decltype(tailb)::value, decltype(vm)::value>), dim3((unsigned)g.blocks),
+					   dim3(BLOCK), 0, s, A.row_ptr, A.col_idx, A.val, A.val_hi, A.palette, X, Y, (long long)A.rows, c.n,
+					   g.split_log2, accum, A.heavy_thr, c.m, xr, ctl);
+		});
+		if (A.n_heavy || A.n_medium)
+			launch_heavy<W, G, MERS, false>(c, A, X, Y, (const W *)nullptr, accum, (u64 *)nullptr, 0, g.hb, ctl, s);
+	});
+	return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_spmv(const KernelCfg &c, const DevCsr &A, const void *X, void *Y, int accum, const DevCtl *ctl,
 		       hipStream_t s)
 {
-	if (c.word == 4)
-		return c.mers == 31 ? spmv_dispatch<u32, 31>(c, A, (const u32 *)X, (u32 *)Y, accum, ctl, s)
-				    : spmv_dispatch<u32, 0>(c, A, (const u32 *)X, (u32 *)Y, accum, ctl, s);
-	return c.mers == 61 ? spmv_dispatch<u64, 61>(c, A, (const u64 *)X, (u64 *)Y, accum, ctl, s)
-			    : spmv_dispatch<u64, 0>(c, A, (const u64 *)X, (u64 *)Y, accum, ctl, s);
+	return with_word_reducer(c, [&](auto wt, auto mers) {
+		using W = typename decltype(wt)::type;
+		return spmv_dispatch<W, decltype(mers)::value>(c, A, (const W *)X, (W *)Y, accum, ctl, s);
+	});
 }
 
 /* --------------------------------------------------------------------- block_dot_products */
@@ -1224,50 +1195,19 @@ static hipError_t spmv_dot_dispatch(const KernelCfg &c, const DevCsr &A, const W
 		return staged_dispatch<W, MERS, true>(c, A, X, Y, Vd, accum, partial, max_blocks, nblocks, ctl, s);
 	const SpmvGrids g = stream_dot_grids(c, A, max_blocks);
 	const long long blocks = g.blocks, hb = g.hb, cb = g.cb, mb = g.mb;
-	XcdRows xr;
-	xr.begin[0] = -1;
-	if (g.xcd)
-		for (int x = 0; x < 9; x++)
-			xr.begin[x] = A.xr_rows[x];
+	const XcdRows xr = xcd_rows(A, g.xcd);
 	*nblocks = (int)(blocks + hb + cb + mb);
-	const bool sgn = sizeof(W) == 8 && A.sgn, wide = sizeof(W) == 8 && A.wide;
-#define SPMV_DOT_GO(NN, TT, SS)                                                                                      \
-	hipLaunchKernelGGL((k_spmv_dot<W, MERS, NN, TT, SS>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, A.row_ptr, A.col_idx, \
-			   A.val, A.val_hi, A.palette, X, Y, Vd, (long long)A.rows, accum, A.heavy_thr, c.m, partial, xr, ctl)
-#define SPMV_DOT(NN)                                                                                                \
-	case NN:                                                                                                    \
-		if (wide) {                                                                                         \
-			if constexpr (sizeof(W) == 8) {                                                             \
-				if (A.tail_batch)                                                                   \
-					SPMV_DOT_GO(NN, true, VM_WIDE);                                             \
-				else                                                                                \
-					SPMV_DOT_GO(NN, false, VM_WIDE);                                            \
-			}                                                                                           \
-		} else if (sgn) {                                                                                   \
-			if constexpr (sizeof(W) == 8) {                                                             \
-				if (A.tail_batch)                                                                   \
-					SPMV_DOT_GO(NN, true, VM_SIGNED);                                           \
-				else                                                                                \
-					SPMV_DOT_GO(NN, false, VM_SIGNED);                                          \
-			}                                                                                           \
-		} else if (A.tail_batch)                                                                            \
-			SPMV_DOT_GO(NN, true, VM_U32);                                                              \
-		else                                                                                                \
-			SPMV_DOT_GO(NN, false, VM_U32);                                                             \
-		if (hb || mb)                                                                                       \
-			launch_heavy<W, NN, MERS, true>(c, A, X, Y, Vd, accum, partial, (int)blocks, hb, ctl, s);      \
-		break;
-	switch (c.n) {
-		SPMV_DOT(1)
-		SPMV_DOT(2)
-		SPMV_DOT(4)
-		SPMV_DOT(8)
-	default:
-		return hipErrorInvalidValue;
-	}
-#undef SPMV_DOT
-#undef SPMV_DOT_GO
-	return hipGetLastError();
+	const bool known = with_lane_group<1, 2, 4, 8>(c.n, [&](auto nt) {
+		constexpr int N = decltype(nt)::value;
+		with_value_mode<W>(A, [&](auto vm, auto tailb) {
+			hipLaunchKernelGGL((k_spmv_dot<W, MERS, N, decltype(tailb)::value, decltype(vm)::value>), dim3((unsigned)blocks),
+					   dim3(BLOCK), 0, s, A.row_ptr, A.col_idx, A.val, A.val_hi, A.palette, X, Y, Vd, (long long)A.rows,
+					   accum, A.heavy_thr, c.m, partial, xr, ctl);
+		});
+		if (hb || mb)
+			launch_heavy<W, N, MERS, true>(c, A, X, Y, Vd, accum, partial, (int)blocks, hb, ctl, s);
+	});
+	return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 bool spmv_dot_supported(const KernelCfg &c)
@@ -1293,76 +1233,43 @@ static hipError_t spmv_self_dispatch(const KernelCfg &c, const DevCsr &A, const 
 		return hipErrorInvalidValue;
 	const SpmvGrids g = second ? stream_dot_grids(c, A, max_blocks) : stream_grids(c, A);
 	const long long blocks = g.blocks;
-	XcdRows xr;
-	xr.begin[0] = -1;
-	if (g.xcd)
-		for (int x = 0; x < 9; x++)
-			xr.begin[x] = A.xr_rows[x];
+	const XcdRows xr = xcd_rows(A, g.xcd);
 	*nblocks = (int)blocks;
-	const bool sgn = sizeof(W) == 8 && A.sgn, wide = sizeof(W) == 8 && A.wide;
-#define SPMV_SELF_GO(NN, TT, SS)                                                                                     \
-	do {                                                                                                         \
-		if (second)                                                                                          \
-			hipLaunchKernelGGL((k_spmv_dot<W, MERS, NN, TT, SS, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s,  \
-					   A.row_ptr, A.col_idx, A.val, A.val_hi, A.palette, X, Y, (const W *)nullptr,     \
-					   (long long)A.rows, 0, A.heavy_thr, c.m, partial, xr, ctl);                      \
-		else                                                                                                 \
-			hipLaunchKernelGGL((k_spmv<W, NN, MERS, TT, SS, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s,      \
-					   A.row_ptr, A.col_idx, A.val, A.val_hi, A.palette, X, Y, (long long)A.rows, NN, 0, 0, \
-					   A.heavy_thr, c.m, xr, ctl, partial);                                            \
-	} while (0)
-#define SPMV_SELF(NN)                                                                                               \
-	case NN:                                                                                                    \
-		if (wide) {                                                                                         \
-			if constexpr (sizeof(W) == 8) {                                                             \
-				if (A.tail_batch)                                                                   \
-					SPMV_SELF_GO(NN, true, VM_WIDE);                                            \
-				else                                                                                \
-					SPMV_SELF_GO(NN, false, VM_WIDE);                                           \
-			}                                                                                           \
-		} else if (sgn) {                                                                                   \
-			if constexpr (sizeof(W) == 8) {                                                             \
-				if (A.tail_batch)                                                                   \
-					SPMV_SELF_GO(NN, true, VM_SIGNED);                                          \
-				else                                                                                \
-					SPMV_SELF_GO(NN, false, VM_SIGNED);                                         \
-			}                                                                                           \
-		} else if (A.tail_batch)                                                                            \
-			SPMV_SELF_GO(NN, true, VM_U32);                                                             \
-		else                                                                                                \
-			SPMV_SELF_GO(NN, false, VM_U32);                                                            \
-		break;
-	switch (c.n) {
-		SPMV_SELF(1)
-		SPMV_SELF(2)
-		SPMV_SELF(4)
-		SPMV_SELF(8)
-	default:
-		return hipErrorInvalidValue;
-	}
-#undef SPMV_SELF
-#undef SPMV_SELF_GO
-	return hipGetLastError();
+	const bool known = with_lane_group<1, 2, 4, 8>(c.n, [&](auto nt) {
+		constexpr int N = decltype(nt)::value;
+		with_value_mode<W>(A, [&](auto vm, auto tailb) {
+			constexpr int VM = decltype(vm)::value;
+			constexpr bool TAILB = decltype(tailb)::value;
+			if (second)
+				hipLaunchKernelGGL((k_spmv_dot<W, MERS, N, TAILB, VM, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s,
+						   A.row_ptr, A.col_idx, A.val, A.val_hi, A.palette, X, Y, (const W *)nullptr, (long long)A.rows,
+						   0, A.heavy_thr, c.m, partial, xr, ctl);
+			else
+				hipLaunchKernelGGL((k_spmv<W, N, MERS, TAILB, VM, true>), dim3((unsigned)blocks), dim3(BLOCK), 0, s,
+						   A.row_ptr, A.col_idx, A.val, A.val_hi, A.palette, X, Y, (long long)A.rows, N, 0, 0,
+						   A.heavy_thr, c.m, xr, ctl, partial);
+		});
+	});
+	return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 hipError_t launch_spmv_self(const KernelCfg &c, const DevCsr &A, const void *X, void *Y, bool second, u64 *partial,
 			    int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s)
 {
-	if (c.word == 4)
-		return c.mers == 31 ? spmv_self_dispatch<u32, 31>(c, A, (const u32 *)X, (u32 *)Y, second, partial, max_blocks, nblocks, ctl, s)
-				    : spmv_self_dispatch<u32, 0>(c, A, (const u32 *)X, (u32 *)Y, second, partial, max_blocks, nblocks, ctl, s);
-	return c.mers == 61 ? spmv_self_dispatch<u64, 61>(c, A, (const u64 *)X, (u64 *)Y, second, partial, max_blocks, nblocks, ctl, s)
-			    : spmv_self_dispatch<u64, 0>(c, A, (const u64 *)X, (u64 *)Y, second, partial, max_blocks, nblocks, ctl, s);
+	return with_word_reducer(c, [&](auto wt, auto mers) {
+		using W = typename decltype(wt)::type;
+		return spmv_self_dispatch<W, decltype(mers)::value>(c, A, (const W *)X, (W *)Y, second, partial, max_blocks, nblocks, ctl, s);
+	});
 }
 
 hipError_t launch_spmv_dot(const KernelCfg &c, const DevCsr &A, const void *X, void *Y, const void *Vd, int accum,
 			   u64 *partial, int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s)
 {
-	if (c.word == 4)
-		return c.mers == 31 ? spmv_dot_dispatch<u32, 31>(c, A, (const u32 *)X, (u32 *)Y, (const u32 *)Vd, accum, partial, max_blocks, nblocks, ctl, s)
-				    : spmv_dot_dispatch<u32, 0>(c, A, (const u32 *)X, (u32 *)Y, (const u32 *)Vd, accum, partial, max_blocks, nblocks, ctl, s);
-	return c.mers == 61 ? spmv_dot_dispatch<u64, 61>(c, A, (const u64 *)X, (u64 *)Y, (const u64 *)Vd, accum, partial, max_blocks, nblocks, ctl, s)
-			    : spmv_dot_dispatch<u64, 0>(c, A, (const u64 *)X, (u64 *)Y, (const u64 *)Vd, accum, partial, max_blocks, nblocks, ctl, s);
+	return with_word_reducer(c, [&](auto wt, auto mers) {
+		using W = typename decltype(wt)::type;
+		return spmv_dot_dispatch<W, decltype(mers)::value>(c, A, (const W *)X, (W *)Y, (const W *)Vd, accum, partial, max_blocks,
+								   nblocks, ctl, s);
+	});
 }
 
 /* ------------------------------------------------------- SpMV, matrix stream staged through LDS (round 2) */
@@ -1387,7 +1294,6 @@ hipError_t launch_spmv_dot(const KernelCfg &c, const DevCsr &A, const void *X, v
  * A row whose entries do not all fit the staged window (tiles of unusually long rows) takes the k_spmv path from
  * global memory; rows above the outlier threshold are left to k_spmv_wave / k_spmv_heavy as before.
  */
-enum { V_ONES = 0, V_PACKED = 1, V_ARRAY = 2 };
 
 struct XcdTiles {
 	long long begin[9];
@@ -1857,95 +1763,55 @@ static void staged_launch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y,
 	xt.interleave = A.st_interleave;
 	const size_t lds = (size_t)(BLOCK / 64) * 2 * A.st_ns * A.st_capw * sizeof(u32);
 	const bool deep = staged_gathers(c, A, G, DOT, sizeof(W) == 8) == 8;	/* gathers in flight per lane: 8 or 4 */
-#define STAGED_GO(UU, DD)                                                                                              \
-	hipLaunchKernelGGL((k_spmv_staged<W, G, MERS, DOT, VALS, UU, DD, 1, SGN>), dim3((unsigned)blocks), dim3(BLOCK), lds, s, A.row_ptr, \
-			   (const u32 *)A.col_idx, A.val, A.palette, X, Y, Vd, (long long)A.rows, c.n, A.st_tr, A.st_capw, accum, \
-			   A.heavy_thr, c.m, partial, xt, ctl)
+	auto go = [&](auto u, auto dyn) {
+		hipLaunchKernelGGL((k_spmv_staged<W, G, MERS, DOT, VALS, decltype(u)::value, decltype(dyn)::value, 1, SGN>),
+				   dim3((unsigned)blocks), dim3(BLOCK), lds, s, A.row_ptr, (const u32 *)A.col_idx, A.val, A.palette, X, Y, Vd,
+				   (long long)A.rows, c.n, A.st_tr, A.st_capw, accum, A.heavy_thr, c.m, partial, xt, ctl);
+	};
+	constexpr IntTag<8> u8{};
+	constexpr IntTag<4> u4{};
+	constexpr BoolTag<true> dynamic{};
+	constexpr BoolTag<false> lockstep{};
 	if constexpr ((G == 16 || G == 8) && !DOT && sizeof(W) == 8) {
 		if (A.st_pair) {	/* G / 2 lanes of two words per row */
-#define STAGED_PAIR(UU)                                                                                                 \
-	hipLaunchKernelGGL((k_spmv_staged<W, G / 2, MERS, false, VALS, UU, false, 2, SGN>), dim3((unsigned)blocks), dim3(BLOCK), lds, s, \
-			   A.row_ptr, (const u32 *)A.col_idx, A.val, A.palette, X, Y, Vd, (long long)A.rows, c.n, A.st_tr, A.st_capw, \
-			   accum, A.heavy_thr, c.m, partial, xt, ctl)
-			if (deep)
-				STAGED_PAIR(8);
-			else
-				STAGED_PAIR(4);
-#undef STAGED_PAIR
+			auto pair = [&](auto u) {
+				hipLaunchKernelGGL((k_spmv_staged<W, G / 2, MERS, false, VALS, decltype(u)::value, false, 2, SGN>),
+						   dim3((unsigned)blocks), dim3(BLOCK), lds, s, A.row_ptr, (const u32 *)A.col_idx, A.val, A.palette, X,
+						   Y, Vd, (long long)A.rows, c.n, A.st_tr, A.st_capw, accum, A.heavy_thr, c.m, partial, xt, ctl);
+			};
+			deep ? pair(u8) : pair(u4);
 			return;
 		}
 	}
 	if constexpr (G >= 8 && !DOT) {
 		if (A.st_dyn) {
-			if constexpr (G < 64) {
-				if (deep)
-					STAGED_GO(8, true);
-				else
-					STAGED_GO(4, true);
-			}
-		} else if (deep)
-			STAGED_GO(8, false);
-		else
-			STAGED_GO(4, false);
+			if constexpr (G < 64)
+				deep ? go(u8, dynamic) : go(u4, dynamic);
+		} else
+			deep ? go(u8, lockstep) : go(u4, lockstep);
 	} else {
-		STAGED_GO(4, false);
+		go(u4, lockstep);
 	}
-#undef STAGED_GO
 }
 
 template <typename W, int MERS, bool DOT>
 static hipError_t staged_dispatch(const KernelCfg &c, const DevCsr &A, const W *X, W *Y, const W *Vd, int accum,
 				  u64 *partial, int max_blocks, int *nblocks, const DevCtl *ctl, hipStream_t s)
 {
-	const int G = lane_group(c);
 	const SpmvGrids g = staged_grids(c, A, DOT, max_blocks);
 	const long long blocks = g.blocks, hb = g.hb;
 	if (DOT)
 		*nblocks = (int)(blocks + hb + g.cb + g.mb);
-	const int vals = A.palette ? V_PACKED : (A.val ? V_ARRAY : V_ONES);
-	const bool sgn = sizeof(W) == 8 && A.sgn && vals != V_ONES;
-#define STAGED_G(GG)                                                                                              \
-	case GG:                                                                                                  \
-		if (sgn) {                                                                                        \
-			if constexpr (sizeof(W) == 8) {                                                           \
-				if (vals == V_PACKED)                                                             \
-					staged_launch<W, MERS, DOT, GG, V_PACKED, true>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
-				else                                                                              \
-					staged_launch<W, MERS, DOT, GG, V_ARRAY, true>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
-			}                                                                                         \
-		} else if (vals == V_PACKED)                                                                      \
-			staged_launch<W, MERS, DOT, GG, V_PACKED>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
-		else if (vals == V_ARRAY)                                                                         \
-			staged_launch<W, MERS, DOT, GG, V_ARRAY>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s);  \
-		else                                                                                              \
-			staged_launch<W, MERS, DOT, GG, V_ONES>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s);   \
-		if (A.n_heavy || A.n_medium)                                                                      \
-			launch_heavy<W, GG, MERS, DOT>(c, A, X, Y, Vd, accum, partial, (int)blocks, hb, ctl, s);      \
-		break;
-	if constexpr (DOT) {
-		switch (G) {
-			STAGED_G(1)
-			STAGED_G(2)
-			STAGED_G(4)
-			STAGED_G(8)
-		default:
-			return hipErrorInvalidValue;
-		}
-	} else {
-		switch (G) {
-			STAGED_G(1)
-			STAGED_G(2)
-			STAGED_G(4)
-			STAGED_G(8)
-			STAGED_G(16)
-			STAGED_G(32)
-			STAGED_G(64)
-		default:
-			return hipErrorInvalidValue;
-		}
-	}
-#undef STAGED_G
-	return hipGetLastError();
+	auto launch = [&](auto gt) {
+		constexpr int G = decltype(gt)::value;
+		with_stream_values<W>(A, [&](auto vals, auto sgn) {
+			staged_launch<W, MERS, DOT, G, decltype(vals)::value, decltype(sgn)::value>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s);
+		});
+		if (A.n_heavy || A.n_medium)
+			launch_heavy<W, G, MERS, DOT>(c, A, X, Y, Vd, accum, partial, (int)blocks, hb, ctl, s);
+	};
+	const bool known = with_product_lanes<DOT>(lane_group(c), launch);
+	return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 /* ------------------------------------------ SpMV with a panel of dense block rows resident in LDS (round 2) */
@@ -2126,50 +1992,15 @@ static hipError_t panel_dispatch(const KernelCfg &c, const DevCsr &A, const W *X
 			return hipErrorInvalidValue;
 		*nblocks = (int)(blocks + hb + g.cb + g.mb);
 	}
-	const int vals = A.palette ? V_PACKED : (A.val ? V_ARRAY : V_ONES);
-	const bool sgn = sizeof(W) == 8 && A.sgn && vals != V_ONES;
-#define PANEL_G(GG)                                                                                              \
-	case GG:                                                                                                 \
-		if (sgn) {                                                                                       \
-			if constexpr (sizeof(W) == 8) {                                                          \
-				if (vals == V_PACKED)                                                            \
-					panel_launch<W, MERS, DOT, GG, V_PACKED, true>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
-				else                                                                             \
-					panel_launch<W, MERS, DOT, GG, V_ARRAY, true>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
-			}                                                                                        \
-		} else if (vals == V_PACKED)                                                                     \
-			panel_launch<W, MERS, DOT, GG, V_PACKED>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s); \
-		else if (vals == V_ARRAY)                                                                        \
-			panel_launch<W, MERS, DOT, GG, V_ARRAY>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s);  \
-		else                                                                                             \
-			panel_launch<W, MERS, DOT, GG, V_ONES>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s);   \
-		if (A.n_heavy || A.n_medium)                                                                     \
-			launch_heavy<W, GG, MERS, DOT>(c, A, X, Y, Vd, accum, partial, (int)blocks, hb, ctl, s);     \
-		break;
-	if constexpr (DOT) {
-		switch (G) {
-			PANEL_G(1)
-			PANEL_G(2)
-			PANEL_G(4)
-			PANEL_G(8)
-		default:
-			return hipErrorInvalidValue;
-		}
-	} else {
-		switch (G) {
-			PANEL_G(1)
-			PANEL_G(2)
-			PANEL_G(4)
-			PANEL_G(8)
-			PANEL_G(16)
-			PANEL_G(32)
-			PANEL_G(64)
-		default:
-			return hipErrorInvalidValue;
-		}
-	}
-#undef PANEL_G
-	return hipGetLastError();
+	const bool known = with_product_lanes<DOT>(G, [&](auto gt) {
+		constexpr int GG = decltype(gt)::value;
+		with_stream_values<W>(A, [&](auto vals, auto sgn) {
+			panel_launch<W, MERS, DOT, GG, decltype(vals)::value, decltype(sgn)::value>(c, A, X, Y, Vd, accum, partial, blocks, ctl, s);
+		});
+		if (A.n_heavy || A.n_medium)
+			launch_heavy<W, GG, MERS, DOT>(c, A, X, Y, Vd, accum, partial, (int)blocks, hb, ctl, s);
+	});
+	return known ? hipGetLastError() : hipErrorInvalidValue;
 }
 
 template <typename W, int MERS>
@@ -2191,20 +2022,10 @@ static hipError_t dot_dispatch(const KernelCfg &c, const W *V, const W *AV, int6
 		long long blocks = (rows + gpb * 8 - 1) / (gpb * 8);	/* >= 8 rows per group */
 		blocks = blocks < 1 ? 1 : (blocks > max_blocks ? max_blocks : blocks);
 		*nblocks = (int)blocks;
-#define DOT_FAST(NN)                                                                                              \
-	case NN:                                                                                                  \
-		hipLaunchKernelGGL((k_block_dot_fast<W, MERS, NN>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, V, AV, \
-				   (long long)rows, c.m, partial, ctl);                                            \
-		break;
-		switch (n) {
-			DOT_FAST(1)
-			DOT_FAST(2)
-			DOT_FAST(4)
-			DOT_FAST(8)
-			DOT_FAST(16)
-			DOT_FAST(32)
-		}
-#undef DOT_FAST
+		with_lane_group<1, 2, 4, 8, 16, 32>(n, [&](auto nt) {
+			hipLaunchKernelGGL((k_block_dot_fast<W, MERS, decltype(nt)::value>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, V, AV,
+					   (long long)rows, c.m, partial, ctl);
+		});
 		return hipGetLastError();
 	}
 	long long blocks = (rows + 255) / 256;
@@ -2228,11 +2049,10 @@ hipError_t launch_block_dot(const KernelCfg &c, const void *V, const void *AV, i
 {
 	if (block_dot_mfma_supported(c) && rows >= 4096)	/* below that one VALU workgroup is quicker than the fold set-up */
 		return launch_block_dot_mfma(c, V, AV, rows, partial, max_blocks, nblocks, ctl, s);
-	if (c.word == 4)
-		return c.mers == 31 ? dot_dispatch<u32, 31>(c, (const u32 *)V, (const u32 *)AV, rows, partial, max_blocks, nblocks, ctl, s)
-				    : dot_dispatch<u32, 0>(c, (const u32 *)V, (const u32 *)AV, rows, partial, max_blocks, nblocks, ctl, s);
-	return c.mers == 61 ? dot_dispatch<u64, 61>(c, (const u64 *)V, (const u64 *)AV, rows, partial, max_blocks, nblocks, ctl, s)
-			    : dot_dispatch<u64, 0>(c, (const u64 *)V, (const u64 *)AV, rows, partial, max_blocks, nblocks, ctl, s);
+	return with_word_reducer(c, [&](auto wt, auto mers) {
+		using W = typename decltype(wt)::type;
+		return dot_dispatch<W, decltype(mers)::value>(c, (const W *)V, (const W *)AV, rows, partial, max_blocks, nblocks, ctl, s);
+	});
 }
 
 /*
@@ -3287,25 +3107,13 @@ static hipError_t ortho_dispatch(const KernelCfg &c, W *V, const W *AV, W *P, in
 			blocks = fit;
 		if (blocks > cap)
 			blocks = cap;
-#define ORTHO_FAST(NN)                                                                                               \
-	case NN:                                                                                                     \
-		hipLaunchKernelGGL((k_orthogonalize_fast<W, MERS, NN>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, V, AV, P, \
-				   (long long)rows, c.m, small, ctl);                                                 \
-		break;
-		switch (n) {
-			ORTHO_FAST(1)
-			ORTHO_FAST(2)
-			ORTHO_FAST(4)
-			ORTHO_FAST(8)
-			ORTHO_FAST(16)
-		}
-#undef ORTHO_FAST
+		with_lane_group<1, 2, 4, 8, 16>(n, [&](auto nt) {
+			hipLaunchKernelGGL((k_orthogonalize_fast<W, MERS, decltype(nt)::value>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, V,
+					   AV, P, (long long)rows, c.m, small, ctl);
+		});
 		return hipGetLastError();
 	}
-	int G = 1;
-	while (G < n)
-		G <<= 1;
-	const int gpb = BLOCK / G;
+	const int G = lane_group(c), gpb = BLOCK / G;
 	const size_t lds = ((size_t)3 * n * n + (size_t)2 * gpb * n) * sizeof(u64);
 	if (lds > 48 * 1024)
 		hipFuncSetAttribute((const void *)k_orthogonalize<W, MERS>, hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -3336,11 +3144,10 @@ hipError_t launch_orthogonalize(const KernelCfg &c, void *V, const void *AV, voi
 {
 	if (ortho_uses_mfma(c, rows))
 		return launch_orthogonalize_mfma(c, V, AV, P, rows, small, ctl, s, img_ready);
-	if (c.word == 4)
-		return c.mers == 31 ? ortho_dispatch<u32, 31>(c, (u32 *)V, (const u32 *)AV, (u32 *)P, rows, small, ctl, s)
-				    : ortho_dispatch<u32, 0>(c, (u32 *)V, (const u32 *)AV, (u32 *)P, rows, small, ctl, s);
-	return c.mers == 61 ? ortho_dispatch<u64, 61>(c, (u64 *)V, (const u64 *)AV, (u64 *)P, rows, small, ctl, s)
-			    : ortho_dispatch<u64, 0>(c, (u64 *)V, (const u64 *)AV, (u64 *)P, rows, small, ctl, s);
+	return with_word_reducer(c, [&](auto wt, auto mers) {
+		using W = typename decltype(wt)::type;
+		return ortho_dispatch<W, decltype(mers)::value>(c, (W *)V, (const W *)AV, (W *)P, rows, small, ctl, s);
+	});
 }
 
 /* ---------------------------------------------------------------------------- utilities */
@@ -3461,12 +3268,10 @@ hipError_t launch_any_nonzero(const KernelCfg &c, const void *X, int64_t words, 
 	long long blocks = (words + BLOCK - 1) / BLOCK;
 	if (blocks > (long long)c.num_cu * 8)
 		blocks = (long long)c.num_cu * 8;
-	if (c.word == 4)
-		hipLaunchKernelGGL((k_any_nonzero<u32>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, (const u32 *)X,
-				   (long long)words, flag);
-	else
-		hipLaunchKernelGGL((k_any_nonzero<u64>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, (const u64 *)X,
-				   (long long)words, flag);
+	with_word_reducer(c, [&](auto wt, auto) {
+		using W = typename decltype(wt)::type;
+		hipLaunchKernelGGL((k_any_nonzero<W>), dim3((unsigned)blocks), dim3(BLOCK), 0, s, (const W *)X, (long long)words, flag);
+	});
 	return hipGetLastError();
 }
 
@@ -3667,12 +3472,9 @@ hipError_t launch_rref_partial(const KernelCfg &c, const void *X, int64_t rows, 
 	if (n < 1 || n > RREF_MAXN)
 		return hipErrorInvalidValue;
 	const int b = rref_partial_blocks(c, rows, n);
-	if (c.word == 4)
-		(c.mers == 31 ? rref_launch<u32, 31, false> : rref_launch<u32, 0, false>)(b, X, rows, nullptr, ld, n, c.m, ctl, stack,
-											   nullptr, s);
-	else
-		(c.mers == 61 ? rref_launch<u64, 61, false> : rref_launch<u64, 0, false>)(b, X, rows, nullptr, ld, n, c.m, ctl, stack,
-											   nullptr, s);
+	with_word_reducer(c, [&](auto wt, auto mers) {
+		rref_launch<typename decltype(wt)::type, decltype(mers)::value, false>(b, X, rows, nullptr, ld, n, c.m, ctl, stack, nullptr, s);
+	});
 	return hipGetLastError();
 }
 
@@ -3681,6 +3483,7 @@ hipError_t launch_rref_merge(const KernelCfg &c, const u64 *stack, int64_t rows,
 {
 	if (n < 1 || n > RREF_MAXN)
 		return hipErrorInvalidValue;
+	/* (its own choice, not with_word_reducer: the stacked rows are u64 words at every reducer class, 31 included) */
 	auto f = c.mers == 61 ? rref_launch<u64, 61, true> : c.mers == 31 ? rref_launch<u64, 31, true> : rref_launch<u64, 0, true>;
 	f(1, stack, rows, rows_dev, n, n, c.m, nullptr, E, info, s);
 	return hipGetLastError();
@@ -3737,16 +3540,9 @@ hipError_t launch_block_mul_gated(const KernelCfg &c, void *X, int64_t rows, int
 	const int64_t groups = (rows + 64 / G - 1) / (64 / G);
 	const int64_t blocks = std::max<int64_t>(1, std::min<int64_t>((groups + 3) / 4, (int64_t)c.num_cu * 8));
 	const dim3 grid((unsigned)blocks), blk(BLOCK);
-	if (c.word == 4) {
-		if (c.mers == 31)
-			hipLaunchKernelGGL((k_block_mul<u32, 31>), grid, blk, 0, s, (u32 *)X, (long long)rows, ld, n, G, Z, c.m, ctl, gate);
-		else
-			hipLaunchKernelGGL((k_block_mul<u32, 0>), grid, blk, 0, s, (u32 *)X, (long long)rows, ld, n, G, Z, c.m, ctl, gate);
-	} else {
-		if (c.mers == 61)
-			hipLaunchKernelGGL((k_block_mul<u64, 61>), grid, blk, 0, s, (u64 *)X, (long long)rows, ld, n, G, Z, c.m, ctl, gate);
-		else
-			hipLaunchKernelGGL((k_block_mul<u64, 0>), grid, blk, 0, s, (u64 *)X, (long long)rows, ld, n, G, Z, c.m, ctl, gate);
-	}
+	with_word_reducer(c, [&](auto wt, auto mers) {
+		using W = typename decltype(wt)::type;
+		hipLaunchKernelGGL((k_block_mul<W, decltype(mers)::value>), grid, blk, 0, s, (W *)X, (long long)rows, ld, n, G, Z, c.m, ctl, gate);
+	});
 	return hipGetLastError();
 }
