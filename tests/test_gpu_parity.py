@@ -611,8 +611,10 @@ def test_block_update_on_the_matrix_cores_against_oracle(monkeypatch, n, rows):
 def test_inner_products_on_the_matrix_cores_against_oracle(monkeypatch, n, rows):
     """block_dot_products for p = 2^61-1 at n = 8 / 16 on v_mfma_i32_16x16x64_i8 (rows as the K dimension, both operands
     biased, the bias terms turned into column sums, i32 accumulators folded mod p every 64 tiles): random blocks and the
-    extreme block (all words p-1), row counts around the 64-row tile and past the first fold, against the oracle;
-    BLZ_NO_MFMA=1 gives the same words."""
+    extreme block (all words p-1), row counts around the 64-row tile and up to 600 000, against the oracle; BLZ_NO_MFMA=1
+    gives the same words.  600 000 rows do NOT reach the fold: launch_block_dot_mfma starts up to 2 * num_cu workgroups of
+    4 wavefronts, so on 256 compute units a wavefront takes 4 to 5 tiles of 64 rows there and flushes once, at the end.
+    test_gpu_mfma_digits.py::test_inner_products_past_the_fold gives every wavefront 65 tiles."""
     p = P61
     rng = np.random.default_rng(rows + n)
     M = blz.Matrix(rows, 8, rng.integers(0, rows, 64), rng.integers(0, 8, 64), np.ones(64, dtype=np.uint32))
