@@ -43,6 +43,7 @@
 #include "blz_devrank.h"
 #include "blz_devw32.h"
 #include "blz_devmat.h"
+#include "blz_devorder.h"
 #include "blz_devrhs.h"
 
 #define HIPCHK(expr)                                                                                     \
@@ -299,6 +300,8 @@ struct blz_ctx {
 	u64 *devrank_send = nullptr, *devrank_recv = nullptr;
 	/* the resident matrix was built on the device (blz_set_matrix_device / blz_set_matrix_upload) */
 	bool device_built = false;
+	/* ... and renumbered there first (blz_set_matrix_device_ordered with order 1) */
+	bool device_order = false;
 };
 
 enum { APPLY_SLAB = 4 };
@@ -1015,6 +1018,7 @@ static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool
 	HIPCHK(hipSetDevice(c->device));
 	matrix_reset(c, right, rank, nranks);
 	c->device_built = false;
+	c->device_order = false;
 	/* side 0 = rows of v: rows of M for a left kernel, columns of M for a right kernel
 	 * (sequential/lanczos_modp.c:592-593). */
 	c->glob_rows[0] = right ? P->ncols : P->nrows;
@@ -3579,8 +3583,14 @@ static int devmat_refuse_ptr(const blz_ctx *c, const char *who, const char *arg,
 
 /* The build itself.  i, j, x have passed devmat_refuse_ptr (or are the library's own copies).  Until the counts of the check
  * pass and the two row_ptr arrays have been read the context is untouched; from there on a failure leaves it without a matrix. */
+/* what an ordered build installs after matrix_reset: perm[0] / inv[0] of M's rows, perm[1] / inv[1] of its columns (all
+ * empty: the identity, the order of a matrix without entries) */
+struct DevmatNumbering {
+	std::vector<int32_t> perm[2], inv[2];
+};
+
 static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
-			int idx_bytes, const void *x, int val_bytes, int right)
+			int idx_bytes, const void *x, int val_bytes, int right, DevmatNumbering *numbering)
 {
 	DevmatTmp tmp;
 	hipStream_t st = c->stream;
@@ -3633,6 +3643,7 @@ static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncol
 	matrix_reset(c, right ? 1 : 0, 0, 1);
 	c->have_matrix = false;
 	c->device_built = false;
+	c->device_order = false;
 	c->values_wide = wide;
 	c->glob_rows[0] = right ? ncols : nrows;
 	c->glob_rows[1] = right ? nrows : ncols;
@@ -3645,6 +3656,14 @@ static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncol
 		c->stride[sd] = c->glob_rows[sd];
 		c->first[sd] = 0;
 		c->count[sd] = c->glob_rows[sd];
+	}
+	if (numbering) {
+		/* i, j are in the new numbering already; M's rows live on side `right`, its columns on the other (set_matrix_prepared) */
+		const int rs = right ? 1 : 0;
+		for (int q = 0; q < 2; q++) {
+			c->perm[q ? 1 - rs : rs] = std::move(numbering->perm[q]);
+			c->inv[q ? 1 - rs : rs] = std::move(numbering->inv[q]);
+		}
 	}
 	c->hot_share[0] = c->hot_share[1] = 0.0;
 	c->locality[0] = c->locality[1] = 1.0;
@@ -3748,15 +3767,134 @@ static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncol
 	}
 	const int rc = matrix_blocks(c, 1, 1);
 	c->device_built = rc == BLZ_OK;
+	c->device_order = c->device_built && numbering != nullptr;
 	return rc;
 }
 
-extern "C" int blz_set_matrix_device(blz_ctx *c, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
-				     int idx_bytes, const void *x, int val_bytes, int right, void *stream)
+static int devmat_build_plain(blz_ctx *c, const char *who, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
+			      int idx_bytes, const void *x, int val_bytes, int right)
 {
-	const char *who = "blz_set_matrix_device";
+	return devmat_build(c, who, nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right, nullptr);
+}
+
+/* BLZ_DEVMAT_TRACE=1: the passes of the renumbering, one line on stderr in front of the build's own */
+struct DevorderTrace {
+	enum { BEGIN = 0, MIN0, SORT0, MIN1, SORT1, RELABEL, MARKS };
+	bool on = false;
+	hipStream_t st = nullptr;
+	hipEvent_t ev[MARKS] = {};
+	bool set[MARKS] = {};
+	explicit DevorderTrace(hipStream_t s) : st(s)
+	{
+		const char *e = getenv("BLZ_DEVMAT_TRACE");
+		on = e && e[0] == '1';
+	}
+	void mark(int k)
+	{
+		if (on && !set[k] && hipEventCreate(&ev[k]) == hipSuccess) {
+			(void)hipEventRecord(ev[k], st);
+			set[k] = true;
+		}
+	}
+	float ms(int a, int b)
+	{
+		float t = 0.0f;
+		if (!set[a] || !set[b] || hipEventElapsedTime(&t, ev[a], ev[b]) != hipSuccess)
+			return 0.0f;
+		return t;
+	}
+	void report()	/* (the stream has been synchronised) */
+	{
+		if (on && set[RELABEL])
+			fprintf(stderr, "blz device order: row keys %.3f ms, row sort %.3f ms, column keys %.3f ms, column sort %.3f ms, "
+				"relabel %.3f ms\n", ms(BEGIN, MIN0), ms(MIN0, SORT0), ms(SORT0, MIN1), ms(MIN1, SORT1), ms(SORT1, RELABEL));
+	}
+	~DevorderTrace()
+	{
+		for (int k = 0; k < MARKS; k++)
+			if (set[k])
+				hipEventDestroy(ev[k]);
+	}
+};
+
+/* The ordered build: blz_reorder's numbering made on the device (csrc/blz_devorder.hip), the triplets
+ * relabelled into int32 copies, then devmat_build on those.  Nothing here touches the context: the resident matrix goes only
+ * when devmat_build has read the counts of its check pass as zero.  The caller's arrays are only read. */
+static int devmat_build_ordered(blz_ctx *c, const char *who, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
+				int idx_bytes, const void *x, int val_bytes, int right)
+{
+	if (nnz == 0) {		/* nothing to order by: the identity, as blz_prepare leaves a matrix without entries */
+		DevmatNumbering identity;
+		return devmat_build(c, who, nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right, &identity);
+	}
+	DevmatTmp tmp;
+	hipStream_t st = c->stream;
+	DevorderTrace trace(st);
+	const int64_t longer = std::max(nrows, ncols), dims[2] = { nrows, ncols };
+	int32_t *key = nullptr, *perm[2] = { nullptr, nullptr }, *bkey[2], *bitem[2], *ni = nullptr, *nj = nullptr;
+	u32 *counters = nullptr, *sums = nullptr;
+	HIPCHK(tmp.alloc((void **)&key, (size_t)longer * sizeof(int32_t)));
+	for (int q = 0; q < 2; q++) {
+		HIPCHK(tmp.alloc((void **)&perm[q], (size_t)dims[q] * sizeof(int32_t)));
+		HIPCHK(tmp.alloc((void **)&bkey[q], (size_t)longer * sizeof(int32_t)));
+		HIPCHK(tmp.alloc((void **)&bitem[q], (size_t)longer * sizeof(int32_t)));
+	}
+	HIPCHK(tmp.alloc((void **)&counters, (size_t)devorder_sort_counters(longer) * sizeof(u32)));
+	HIPCHK(tmp.alloc((void **)&sums, (size_t)devmat_scan_tiles(devorder_sort_counters(longer)) * sizeof(u32)));
+	HIPCHK(tmp.alloc((void **)&ni, (size_t)nnz * sizeof(int32_t)));
+	HIPCHK(tmp.alloc((void **)&nj, (size_t)nnz * sizeof(int32_t)));
+	trace.mark(DevorderTrace::BEGIN);
+	/* rows by smallest column (rows without entries: ncols, last), then columns by smallest NEW row */
+	for (int q = 0; q < 2; q++) {
+		HIPCHK(launch_devorder_fill(c->cfg, key, dims[q], (int32_t)dims[1 - q], st));
+		HIPCHK(launch_devorder_min(c->cfg, idx_bytes, i, j, nnz, nrows, ncols, q ? perm[0] : nullptr, key, q, st));
+		trace.mark(q ? DevorderTrace::MIN1 : DevorderTrace::MIN0);
+		HIPCHK(launch_devorder_sort(c->cfg, key, dims[q], dims[1 - q], perm[q], bkey, bitem, counters, sums, st));
+		trace.mark(q ? DevorderTrace::SORT1 : DevorderTrace::SORT0);
+	}
+	HIPCHK(launch_devorder_relabel(c->cfg, idx_bytes, i, j, nnz, nrows, ncols, perm[0], perm[1], ni, nj, st));
+	trace.mark(DevorderTrace::RELABEL);
+	HIPCHK(hipStreamSynchronize(st));
+	trace.report();
+	/* the numbering on the host, once: the host blocks, the right-hand sides and the checkpoints go through it */
+	DevmatNumbering num;
+	for (int q = 0; q < 2; q++) {
+		num.perm[q].resize((size_t)dims[q]);
+		num.inv[q].assign((size_t)dims[q], (int32_t)-1);
+		if (dims[q] > 0)
+			HIPCHK(hipMemcpy(num.perm[q].data(), perm[q], (size_t)dims[q] * sizeof(int32_t), hipMemcpyDeviceToHost));
+		for (int64_t r = 0; r < dims[q]; r++) {
+			const int64_t to = num.perm[q][(size_t)r];
+			if (to < 0 || to >= dims[q] || num.inv[q][(size_t)to] >= 0)
+				return blz_fail(BLZ_EHIP, "%s: the device sort of the %s did not return a permutation (at %lld)", who,
+						q ? "columns" : "rows", (long long)r);
+			num.inv[q][(size_t)to] = (int32_t)r;
+		}
+	}
+	/* the transients of the sort go before the build allocates the two CSRs */
+	for (void *p : { (void *)key, (void *)perm[0], (void *)perm[1], (void *)bkey[0], (void *)bkey[1], (void *)bitem[0],
+			 (void *)bitem[1], (void *)counters, (void *)sums }) {
+		tmp.keep(p);
+		hipFree(p);
+	}
+	return devmat_build(c, who, nrows, ncols, nnz, ni, nj, 4, x, val_bytes, right, &num);
+}
+
+static int devmat_refuse_order(const char *who, int order)
+{
+	if (order != 0 && order != 1)
+		return blz_fail(BLZ_EINVAL, "%s: order = %d is neither 0 (the caller's numbering) nor 1 (rows by smallest column, columns "
+				"by smallest new row)", who, order);
+	return BLZ_OK;
+}
+
+static int devmat_set_device(blz_ctx *c, const char *who, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
+			     int idx_bytes, const void *x, int val_bytes, int right, int order, void *stream)
+{
 	int rc = devmat_refuse(c, who, nrows, ncols, nnz, idx_bytes, x, val_bytes);
 	if (rc != BLZ_OK)
+		return rc;
+	if ((rc = devmat_refuse_order(who, order)) != BLZ_OK)
 		return rc;
 	if ((rc = devio_refuse_capture(who, (hipStream_t)stream)) != BLZ_OK)
 		return rc;
@@ -3767,12 +3905,24 @@ extern "C" int blz_set_matrix_device(blz_ctx *c, int64_t nrows, int64_t ncols, i
 		return rc;
 	if ((rc = devio_wait_caller(c, (hipStream_t)stream)) != BLZ_OK)
 		return rc;
-	return devmat_build(c, who, nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right);
+	return (order ? devmat_build_ordered : devmat_build_plain)(c, who, nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right);
 }
 
-extern "C" int blz_set_matrix_upload(blz_ctx *c, const blz_coo *M, int right)
+extern "C" int blz_set_matrix_device(blz_ctx *c, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
+				     int idx_bytes, const void *x, int val_bytes, int right, void *stream)
 {
-	const char *who = "blz_set_matrix_upload";
+	return devmat_set_device(c, "blz_set_matrix_device", nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right, 0, stream);
+}
+
+extern "C" int blz_set_matrix_device_ordered(blz_ctx *c, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
+					     int idx_bytes, const void *x, int val_bytes, int right, int order, void *stream)
+{
+	return devmat_set_device(c, "blz_set_matrix_device_ordered", nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right, order,
+				 stream);
+}
+
+static int devmat_set_upload(blz_ctx *c, const char *who, const blz_coo *M, int right, int order)
+{
 	if (!c || !M)
 		return blz_fail(BLZ_EINVAL, "%s: NULL argument", who);
 	if (M->nnz >= (int64_t)UINT32_MAX)
@@ -3781,6 +3931,8 @@ extern "C" int blz_set_matrix_upload(blz_ctx *c, const blz_coo *M, int right)
 		return blz_fail(BLZ_EINVAL, "%s: the triplets of M are NULL", who);
 	int rc = devmat_refuse(c, who, M->nrows, M->ncols, M->nnz, 4, M->x, 4);
 	if (rc != BLZ_OK)
+		return rc;
+	if ((rc = devmat_refuse_order(who, order)) != BLZ_OK)
 		return rc;
 	HIPCHK(hipSetDevice(c->device));
 	DevmatTmp tmp;		/* the triplets on the device, for the length of the call */
@@ -3792,10 +3944,42 @@ extern "C" int blz_set_matrix_upload(blz_ctx *c, const blz_coo *M, int right)
 		if (bytes)
 			HIPCHK(hipMemcpy(dev[q], host[q], bytes, hipMemcpyHostToDevice));
 	}
-	return devmat_build(c, who, M->nrows, M->ncols, M->nnz, dev[0], dev[1], 4, dev[2], 4, right);
+	return (order ? devmat_build_ordered : devmat_build_plain)(c, who, M->nrows, M->ncols, M->nnz, dev[0], dev[1], 4, dev[2], 4, right);
+}
+
+extern "C" int blz_set_matrix_upload(blz_ctx *c, const blz_coo *M, int right)
+{
+	return devmat_set_upload(c, "blz_set_matrix_upload", M, right, 0);
+}
+
+extern "C" int blz_set_matrix_upload_ordered(blz_ctx *c, const blz_coo *M, int right, int order)
+{
+	return devmat_set_upload(c, "blz_set_matrix_upload_ordered", M, right, order);
 }
 
 extern "C" int blz_matrix_device_built(const blz_ctx *c) { return c && c->have_matrix && c->device_built ? 1 : 0; }
+
+extern "C" int blz_matrix_device_order(const blz_ctx *c)
+{
+	return c && c->have_matrix && c->device_built && c->device_order ? 1 : 0;
+}
+
+extern "C" int blz_numbering(const blz_ctx *c, int block, int32_t *perm)
+{
+	if (!c || !perm || block < 0 || block > 3)
+		return blz_fail(BLZ_EINVAL, "blz_numbering: no context, no array or block %d", block);
+	if (c->have_matrix && c->nranks > 1)
+		return blz_fail(BLZ_EINVAL, "blz_numbering: the context holds one rank of %d", c->nranks);
+	const int sd = side_of(block);
+	const int64_t rows = c->glob_rows[sd];
+	if (!c->have_matrix || c->perm[sd].empty()) {
+		for (int64_t r = 0; r < rows; r++)
+			perm[r] = (int32_t)r;
+		return 0;
+	}
+	memcpy(perm, c->perm[sd].data(), (size_t)rows * sizeof(int32_t));
+	return 1;
+}
 
 /* The calls below are written once for both word widths of a caller's block: W is uint64_t for blz_..._device and uint32_t
  * for blz_..._device32, `who` the name the caller used.  The widths differ in what devio_begin refuses,

@@ -29,7 +29,7 @@
 static long n = 1;
 static uint64_t prime;
 static char *matrix_filename, *kernel_filename, *rhs_filename;
-static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis, rhs_gpus_given, values_signed, values_wide, device_build;
+static bool right_kernel, checkpoints, load_checkpoint, verify, use_cache, basis, rhs_gpus_given, values_signed, values_wide, device_build, device_reorder;
 static int stop_after = -1, checkpoint_timer = 60, device, gpus = 1, rhs_gpus;
 
 static double wtime(void)
@@ -94,6 +94,9 @@ static void usage(char **argv)
 	printf("                            host renumbering and no host CSR build; the file's numbering is kept, the output is\n");
 	printf("                            the same, byte for byte.  One GPU only: not with --gpus above 1, --rhs, --rhs-gpus,\n");
 	printf("                            --cache, --signed or --wide\n");
+	printf("--device-reorder            with --device-build: renumber the rows and columns on the GPU before the build\n");
+	printf("                            (blz_set_matrix_upload_ordered: rows by smallest column, columns by smallest new row);\n");
+	printf("                            the output is the same, byte for byte.  Only together with --device-build\n");
 	printf("--device D                  first HIP device to run on [default 0]\n");
 	printf("--gpus G                    row-partition the matrix over G GPUs of this node (devices D..D+G-1), RCCL\n");
 	printf("                            all-gather of the block before each product [default 1]\n");
@@ -105,6 +108,7 @@ static void usage(char **argv)
 	printf("kernel basis of the bordered matrix, which --rhs computes itself; it is one vector per system, not a kernel block)\n");
 	printf("The --rhs-gpus argument needs --rhs and excludes --gpus above 1\n");
 	printf("The --device-build argument excludes --gpus above 1, --rhs, --rhs-gpus, --cache, --signed and --wide\n");
+	printf("The --device-reorder argument needs --device-build\n");
 	exit(0);
 }
 
@@ -120,6 +124,7 @@ static void process_command_line_options(int argc, char **argv)
 		{"cache", no_argument, NULL, 'C'}, {"basis", no_argument, NULL, 'B'}, {"rhs", required_argument, NULL, 'R'},
 		{"rhs-gpus", required_argument, NULL, 'G'}, {"signed", no_argument, NULL, 'S'},
 		{"wide", no_argument, NULL, 'W'}, {"device-build", no_argument, NULL, 'D'},
+		{"device-reorder", no_argument, NULL, 'O'},
 		{"help", no_argument, NULL, 'h'}, {NULL, 0, NULL, 0}
 	};
 	int ch;
@@ -150,6 +155,7 @@ static void process_command_line_options(int argc, char **argv)
 		case 'S': values_signed = true; break;
 		case 'W': values_wide = true; break;
 		case 'D': device_build = true; break;
+		case 'O': device_reorder = true; break;
 		case 'h': usage(argv); break;
 		default: errx(1, "Unknown option\n");
 		}
@@ -167,6 +173,8 @@ static void process_command_line_options(int argc, char **argv)
 	if (values_wide && (use_cache || gpus > 1 || rhs_gpus_given || values_signed))
 		usage(argv);
 	if (device_build && (gpus > 1 || rhs_filename != NULL || rhs_gpus_given || use_cache || values_signed || values_wide))
+		usage(argv);
+	if (device_reorder && !device_build)
 		usage(argv);
 	if (prime >= (1ull << 62))
 		errx(1, "p is capped at 2**62 - 1.");
@@ -518,8 +526,9 @@ int main(int argc, char **argv)
 	}
 	if (device_build) {
 		/* both CSRs are built on the GPU from the file's triplets; the file's numbering is the solver's (one GPU, no cache) */
-		CHECK(blz_set_matrix_upload(ctx, &M, right_kernel));
-		fprintf(stderr, "  - Device build of CSR(M), CSR(M^T) (upload, check, scan, scatter; numbering kept): %.2fs\n", wtime() - t_prep);
+		CHECK(blz_set_matrix_upload_ordered(ctx, &M, right_kernel, device_reorder ? 1 : 0));
+		fprintf(stderr, "  - Device build of CSR(M), CSR(M^T) (upload, %scheck, scan, scatter; numbering %s): %.2fs\n",
+			device_reorder ? "renumbering, " : "", device_reorder ? "made on the GPU" : "kept", wtime() - t_prep);
 	} else if (x_hi) {
 		/* the one-call form carries the high limbs through the renumbering and the CSR builds (one GPU, no cache) */
 		CHECK(blz_set_values_wide(ctx, x_hi, M.nnz));

@@ -823,18 +823,23 @@ class Context:
             ncols = int(j.max()) + 1 if ncols is None else ncols
         return nrows, ncols
 
-    def set_matrix_device(self, i, j, x=None, nrows=None, ncols=None, right=False, stream=None):
+    def set_matrix_device(self, i, j, x=None, nrows=None, ncols=None, right=False, stream=None, reorder=False):
         """blz_set_matrix_device(): M from triplets on the GPU (device_triplets() says what i, j, x may be); both CSRs are
         built there and the caller's numbering is kept.  nrows / ncols default to 1 + the largest index (a device
-        reduction; an empty matrix needs them given).  Ordered on `stream` (default: torch's current stream); synchronises."""
+        reduction; an empty matrix needs them given).  Ordered on `stream` (default: torch's current stream); synchronises.
+        reorder=True: blz_set_matrix_device_ordered() with order 1 -- rows and columns are renumbered on the GPU first
+        (blz_reorder's order); nothing of the numbering shows."""
         pi, pj, ib, px, vb, nnz = device_triplets(i, j, x, self.device)
         nrows, ncols = self._matrix_dims(i, j, nrows, ncols, "set_matrix_device")
-        check(lib().blz_set_matrix_device(self.h, C.c_int64(nrows), C.c_int64(ncols), C.c_int64(nnz), C.c_void_p(pi),
-                                          C.c_void_p(pj), C.c_int(ib), C.c_void_p(px), C.c_int(vb), C.c_int(int(bool(right))),
-                                          C.c_void_p(self._stream(stream))))
+        args = (self.h, C.c_int64(nrows), C.c_int64(ncols), C.c_int64(nnz), C.c_void_p(pi), C.c_void_p(pj), C.c_int(ib),
+                C.c_void_p(px), C.c_int(vb), C.c_int(int(bool(right))))
+        if reorder:
+            check(lib().blz_set_matrix_device_ordered(*args, C.c_int(int(reorder)), C.c_void_p(self._stream(stream))))
+        else:
+            check(lib().blz_set_matrix_device(*args, C.c_void_p(self._stream(stream))))
         self.right = bool(right)
 
-    def set_matrix_sparse(self, t, right=False, stream=None):
+    def set_matrix_sparse(self, t, right=False, stream=None, reorder=False):
         """set_matrix_device() of a 2-D torch sparse COO tensor: rows 0 and 1 of its _indices() and its _values(), dimensions
         from t.shape.  The tensor need not be coalesced: duplicates add up."""
         if len(tuple(t.shape)) != 2:
@@ -843,17 +848,34 @@ class Context:
         if not idx.is_contiguous():
             idx = idx.contiguous()
         self.set_matrix_device(idx[0], idx[1], val.contiguous(), nrows=int(t.shape[0]), ncols=int(t.shape[1]), right=right,
-                               stream=stream)
+                               stream=stream, reorder=reorder)
 
-    def set_matrix_upload(self, M, right=False):
-        """blz_set_matrix_upload(): the host triplets of M through the device build (numbering kept, as set_matrix_device)."""
+    def set_matrix_upload(self, M, right=False, reorder=False):
+        """blz_set_matrix_upload(): the host triplets of M through the device build (numbering kept, as set_matrix_device;
+        reorder=True: blz_set_matrix_upload_ordered() with order 1)."""
         if getattr(M, "x_hi", None) is not None:
             raise ValueError("set_matrix_upload: wide entries go through set_matrix_device as 8-byte values")
-        check(lib().blz_set_matrix_upload(self.h, C.byref(M.c), C.c_int(int(bool(right)))))
+        if reorder:
+            check(lib().blz_set_matrix_upload_ordered(self.h, C.byref(M.c), C.c_int(int(bool(right))), C.c_int(int(reorder))))
+        else:
+            check(lib().blz_set_matrix_upload(self.h, C.byref(M.c), C.c_int(int(bool(right)))))
         self.right = bool(right)
 
     def matrix_device_built(self):
         return bool(lib().blz_matrix_device_built(self.h))
+
+    def matrix_device_order(self):
+        """blz_matrix_device_order(): 1 when the resident matrix was renumbered and built on the device, else 0"""
+        return int(lib().blz_matrix_device_order(self.h))
+
+    def numbering(self, block):
+        """blz_numbering() (a test hook): (resident, perm) -- perm[r] = the solver's index of original row r of the block's
+        side, an int32 array of rows(block) words; resident False: the identity"""
+        perm = np.zeros(max(self.rows(block), 0), dtype=np.int32)
+        rc = lib().blz_numbering(self.h, C.c_int(block), perm.ctypes.data_as(C.POINTER(C.c_int32)))
+        if rc < 0:
+            check(rc)
+        return bool(rc), perm
 
     def set_matrix_prepared(self, P, rank=0):
         check(lib().blz_set_matrix_prepared(self.h, P.h, C.c_int(rank)))
@@ -979,12 +1001,12 @@ class Context:
         """blz_solution_device32(): solution_device() into a tensor of 32-bit words (a new torch.uint32 one when not given)."""
         return self._solution_device(device_rhs32, "uint32", lib().blz_solution_device32, out, stream)
 
-    def set_matrix_rhs_device(self, i, j, x, b, nrows=None, ncols=None, right=False, stream=None):
+    def set_matrix_rhs_device(self, i, j, x, b, nrows=None, ncols=None, right=False, stream=None, reorder=False):
         """set_matrix_device() with the dimension raised by k, then set_rhs_device(): M x = b (right; b has nrows rows) or
         x M = b (b has ncols rows) from triplets and right-hand sides that all live on the GPU."""
         nrows, ncols = self._matrix_dims(i, j, nrows, ncols, "set_matrix_rhs_device")
         k = device_rhs(b, self.n, nrows if right else ncols, self.device)[2]
-        self.set_matrix_device(i, j, x, nrows + (0 if right else k), ncols + (k if right else 0), right, stream)
+        self.set_matrix_device(i, j, x, nrows + (0 if right else k), ncols + (k if right else 0), right, stream, reorder)
         self.set_rhs_device(b, stream)
 
     def rows(self, block):
@@ -1512,11 +1534,11 @@ def solve_rhs(M, b, prime, n, right=False, batch=16, device=0, signed=False, wid
         return dict(status=status, x=x, iterations=ctx.iterations, final_check=fc)
 
 
-def solve_rhs_device(t_or_triplets, b, prime, n, right=False, batch=16, device=0):
+def solve_rhs_device(t_or_triplets, b, prime, n, right=False, batch=16, device=0, reorder=False):
     """M X = B (right) / X M = B with nothing tall on the host: M a 2-D torch sparse COO tensor or a tuple (i, j, x[, nrows,
     ncols]) of device triplets (Context.set_matrix_device), b a (rows,) or (rows, k) tensor on the same GPU (device_rhs()).
     Returns dict(status, x, iterations, final_check): status the list of k statuses of solution_block(), x a (length, k)
-    torch.uint64 tensor on the GPU."""
+    torch.uint64 tensor on the GPU.  reorder=True: the matrix is renumbered on the GPU before the build (the result is the same)."""
     with Context(prime, n, device) as ctx:
         if isinstance(t_or_triplets, (tuple, list)):
             i, j, x, *dims = t_or_triplets
@@ -1527,7 +1549,7 @@ def solve_rhs_device(t_or_triplets, b, prime, n, right=False, batch=16, device=0
                 raise ValueError(f"solve_rhs_device: {len(tuple(t.shape))} dimensions, a matrix has 2")
             idx = t._indices().contiguous()
             i, j, x, nrows, ncols = idx[0], idx[1], t._values().contiguous(), int(t.shape[0]), int(t.shape[1])
-        ctx.set_matrix_rhs_device(i, j, x, b, nrows, ncols, right)
+        ctx.set_matrix_rhs_device(i, j, x, b, nrows, ncols, right, reorder=reorder)
         ctx.init_v()
         while not ctx.iterate(batch)[1]:
             pass
@@ -1537,7 +1559,7 @@ def solve_rhs_device(t_or_triplets, b, prime, n, right=False, batch=16, device=0
 
 
 def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0, basis=False, signed=False, wide=False,
-          device_build=False):
+          device_build=False, device_reorder=False):
     """block_lanczos(), sequential/lanczos_modp.c:585-669, on one GPU.  Returns dict(v, tmp, iterations).
     basis=True (not with stop_after): also reduce the final block to independent kernel vectors (blz_kernel_basis) --
     adds basis (rows x k array), k and z to the result; v, tmp and p stay those of the plain solve.
@@ -1545,16 +1567,19 @@ def solve(M, prime, n, right=False, stop_after=-1, batch=16, device=0, basis=Fal
     wide: the wide value mode comes from the matrix (M.x_hi, handed over by set_matrix); the argument only says so at the
     call site and changes nothing -- a matrix whose residues all fit 32 bits has x_hi None and is an ordinary one.
     device_build=True: the matrix is set with set_matrix_upload (both CSRs built on the GPU, the file's numbering kept; not
-    with signed or wide entries); every block of the result is the same, word for word."""
+    with signed or wide entries); every block of the result is the same, word for word.
+    device_reorder=True (with device_build): set_matrix_upload(reorder=True), the numbering made on the GPU; the same result."""
     if basis and stop_after > 0:
         raise ValueError("basis=True needs a run to the end (stop_after < 0)")
+    if device_reorder and not device_build:
+        raise ValueError("device_reorder=True needs device_build=True")
     if device_build and (signed or getattr(M, "x_hi", None) is not None):
         raise ValueError("device_build=True takes neither signed nor wide entries")
     with Context(prime, n, device) as ctx:
         if signed:
             ctx.set_values_signed()
         if device_build:
-            ctx.set_matrix_upload(M, right)
+            ctx.set_matrix_upload(M, right, reorder=device_reorder)
         else:
             ctx.set_matrix(M, right)
         ctx.init_v()

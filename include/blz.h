@@ -389,6 +389,29 @@ int blz_set_matrix_device(blz_ctx *ctx, int64_t nrows, int64_t ncols, int64_t nn
 int blz_set_matrix_upload(blz_ctx *ctx, const blz_coo *M, int right);
 int blz_matrix_device_built(const blz_ctx *ctx);
 
+/* Ordered device matrix: the device build with the rows and columns renumbered on the GPU first
+ * (csrc/blz_devorder.hip).  order == 0 is blz_set_matrix_device / blz_set_matrix_upload in every respect; order == 1 means what
+ * blz_set_matrix means on a context created under BLZ_REORDER_PLAIN=1 BLZ_NO_PANEL=1: the numbering is blz_reorder(M)'s, word
+ * for word -- rows sorted stably by their smallest column (rows without entries take the key ncols and come last, ties stay
+ * in ascending original index), then columns sorted the same way by their smallest NEW row -- with no hot rows and no
+ * panel; blz_locality reports 1.0 / kind 0.  The key is a minimum and the sort is stable, so the numbering has one answer
+ * whatever the schedule.  The argument decides: BLZ_NO_REORDER is not consulted.  Any other order is BLZ_EINVAL.
+ * Refusals are those of the unordered calls, all before anything is enqueued; entries that are invalid give the unordered
+ * call's message with its counts, and the resident matrix stays in place and still applies.  No index is used as an address
+ * before it has been compared with its bound, in the minimum passes and the relabel pass included.
+ * Afterwards the context carries the numbering as a host-renumbered one does: host blocks, device blocks, checkpoints,
+ * blz_owner_of_row, blz_set_rhs*, blz_set_rhs_device and blz_solution_device speak the ORIGINAL numbering, and nothing of it
+ * shows.  A matrix without entries keeps the identity.  Transient device memory: 8 bytes per entry (the relabelled
+ * triplets, for the length of the build) and 32 bytes per row or column of the longer side (keys, the two permutations, the
+ * sort's buffers and counters, freed before the CSRs are allocated); the two permutations are copied to the host once.
+ * The caller's arrays are never written.  One rank; no prepared object, no cache.
+ *   blz_matrix_device_order  1 when the resident matrix was built on the device with order 1, 0 otherwise (a host-built
+ *                            matrix or no matrix included) */
+int blz_set_matrix_device_ordered(blz_ctx *ctx, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
+				  int idx_bytes, const void *x, int val_bytes, int right, int order, void *stream);
+int blz_set_matrix_upload_ordered(blz_ctx *ctx, const blz_coo *M, int right, int order);
+int blz_matrix_device_order(const blz_ctx *ctx);
+
 /* Device right-hand sides: the two ends of M x = b / x M = b on memory of the context's GPU, so that a
  * solve whose matrix came from blz_set_matrix_device needs nothing tall on the host.  The 64 / 32-bit twins follow the device
  * blocks' pattern (the ...32 forms: contexts of 4-byte words, blz_word_bytes(ctx) == 4, p < 2^32).  A plain single rank.
@@ -535,6 +558,11 @@ typedef struct blz_plan {
 	blz_plan_launch plain, dot;
 } blz_plan;
 int blz_slab_plan(const blz_ctx *c, int transpose, int piece, blz_plan *out);
+
+/* The solver's numbering of one side (tests): perm[r] = the new index of original row r of `block`'s side, blz_rows(ctx, block)
+ * words.  Returns 1 when a numbering is resident and 0 when it is the identity (perm is then 0, 1, 2, ...); a negative error
+ * code for a bad argument or a context that holds one rank of several.  Host-built and device-built matrices alike. */
+int blz_numbering(const blz_ctx *c, int block, int32_t *perm);
 
 /* Short-side exchange: 1 when product `transpose` (0: M * x, 1: M^T * x) runs in its short-side form on this context
  * -- several ranks, 64-bit words, operand side at least 8 times longer than the output side (BLZ_SHORT_SIDE=0/1
