@@ -671,6 +671,35 @@ extern "C" int blz_values_signed(const blz_ctx *c) { return c && c->values_signe
 
 static int plan_csr(blz_ctx *c, const u32 *row_ptr, DevCsr &D, int64_t hot_rows, bool dot_slab);
 
+/* product t's (last) launch carries the inner products where that form exists: product `right` is the second one of the iteration */
+static inline bool carries_dots(const blz_ctx *c, int t) { return t == c->right && c->fuse_dot && spmv_dot_supported(c->cfg); }
+
+/* a wide slab sums a row's products unreduced (csrc/modp.h): what both paths refuse before they build one */
+static int wide_refuse_long_row(const u32 *row_ptr, int64_t rows)
+{
+	for (int64_t r = 0; r < rows; r++)
+		if (row_ptr[r + 1] - row_ptr[r] > (1u << 30))
+			return blz_fail(BLZ_EINVAL, "a row of a wide slab has more than 2^30 entries: its unreduced sum is not bounded "
+					"(csrc/modp.h)");
+	return BLZ_OK;
+}
+
+/* The stream arrays of a slab of nnz entries: col_idx always, val and val_hi on request.  The streaming kernels read up to
+ * BLZ_STREAM_PAD elements past the end of each, so each has nnz + BLZ_STREAM_PAD elements and its pad is zeroed, on `st`.
+ * Every matrix-setting call ends in matrix_blocks, which synchronises c->stream: named here, the pad is zero before the call
+ * returns to its caller. */
+static int alloc_stream_arrays(DevCsr &D, int64_t nnz, bool val, bool val_hi, hipStream_t st)
+{
+	void **const arr[3] = { (void **)&D.col_idx, val ? (void **)&D.val : nullptr, val_hi ? (void **)&D.val_hi : nullptr };
+	for (void **a : arr) {
+		if (!a)
+			continue;
+		HIPCHK(hipMalloc(a, (size_t)(nnz + BLZ_STREAM_PAD) * sizeof(u32)));
+		HIPCHK(hipMemsetAsync((u32 *)*a + nnz, 0, BLZ_STREAM_PAD * sizeof(u32), st));
+	}
+	return BLZ_OK;
+}
+
 /* hi0: wide value mode, the high limbs of H0.val (host) */
 static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows = 0, bool dot_slab = false, double locality = 1.0,
 		      const u32 *hi0 = nullptr)
@@ -706,10 +735,9 @@ static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows
 				hi = hi0;
 	}
 	if (hi) {
-		for (int64_t r = 0; r < H0.rows; r++)
-			if (H0.row_ptr[r + 1] - H0.row_ptr[r] > (1u << 30))
-				return blz_fail(BLZ_EINVAL, "a row of a wide slab has more than 2^30 entries: its unreduced sum is not bounded "
-						"(csrc/modp.h)");
+		const int rcw = wide_refuse_long_row(H0.row_ptr, H0.rows);
+		if (rcw != BLZ_OK)
+			return rcw;
 	}
 	D.wide = hi != nullptr;
 	D.locality = locality;
@@ -718,15 +746,14 @@ static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows
 	D.nnz = H.nnz;
 	HIPCHK(hipMalloc(&D.row_ptr, (size_t)(H.rows + 1) * sizeof(u32)));
 	HIPCHK(hipMemcpy(D.row_ptr, H.row_ptr, (size_t)(H.rows + 1) * sizeof(u32), hipMemcpyHostToDevice));
-	HIPCHK(hipMalloc(&D.col_idx, (size_t)(H.nnz + BLZ_STREAM_PAD) * sizeof(int)));
-	HIPCHK(hipMemset(D.col_idx + H.nnz, 0, BLZ_STREAM_PAD * sizeof(int)));
 	/* Packed stream: when the slab has at most 256 distinct values and fewer than 2^24 columns, each entry
 	 * travels as ONE u32 (column | palette index << 24) instead of two; the SpMV is bound by the number of
 	 * fabric requests, and this halves those of the matrix stream.  BLZ_NO_PACK=1 keeps the plain arrays. */
 	bool packed = false;
+	std::vector<u32> pal, pk;
 	if (H.val && c->pack && H.cols < (1 << 24)) {
-		std::vector<u32> pal, pal_hi;	/* (wide: 256 low limbs, then 256 high limbs) */
-		std::vector<u32> pk((size_t)H.nnz);
+		std::vector<u32> pal_hi;	/* (wide: 256 low limbs, then 256 high limbs) */
+		pk.resize((size_t)H.nnz);
 		std::vector<int> slot(4096, -1);	/* open-addressing hash: value -> palette index */
 		packed = true;
 		for (int64_t k = 0; k < H.nnz && packed; k++) {
@@ -752,23 +779,22 @@ static int upload_csr(blz_ctx *c, const blz_csr &H0, DevCsr &D, int64_t hot_rows
 				pal_hi.resize(256, 0);
 				pal.insert(pal.end(), pal_hi.begin(), pal_hi.end());
 			}
-			HIPCHK(hipMalloc(&D.palette, pal.size() * sizeof(u32)));
-			HIPCHK(hipMemcpy(D.palette, pal.data(), pal.size() * sizeof(u32), hipMemcpyHostToDevice));
-			HIPCHK(hipMemcpy(D.col_idx, pk.data(), (size_t)H.nnz * sizeof(u32), hipMemcpyHostToDevice));
 		}
 	}
-	if (!packed) {
+	/* (a packed slab has no value array: its values are in the palette) */
+	const int rca = alloc_stream_arrays(D, H.nnz, !packed && H.val, !packed && hi, c->stream);
+	if (rca != BLZ_OK)
+		return rca;
+	if (packed) {
+		HIPCHK(hipMalloc(&D.palette, pal.size() * sizeof(u32)));
+		HIPCHK(hipMemcpy(D.palette, pal.data(), pal.size() * sizeof(u32), hipMemcpyHostToDevice));
+		HIPCHK(hipMemcpy(D.col_idx, pk.data(), (size_t)H.nnz * sizeof(u32), hipMemcpyHostToDevice));
+	} else {
 		HIPCHK(hipMemcpy(D.col_idx, H.col_idx, (size_t)H.nnz * sizeof(int), hipMemcpyHostToDevice));
-		if (H.val) {
-			HIPCHK(hipMalloc(&D.val, (size_t)(H.nnz + BLZ_STREAM_PAD) * sizeof(u32)));
-			HIPCHK(hipMemset(D.val + H.nnz, 0, BLZ_STREAM_PAD * sizeof(u32)));
+		if (H.val)
 			HIPCHK(hipMemcpy(D.val, H.val, (size_t)H.nnz * sizeof(u32), hipMemcpyHostToDevice));
-			if (hi) {
-				HIPCHK(hipMalloc(&D.val_hi, (size_t)(H.nnz + BLZ_STREAM_PAD) * sizeof(u32)));
-				HIPCHK(hipMemset(D.val_hi + H.nnz, 0, BLZ_STREAM_PAD * sizeof(u32)));
-				HIPCHK(hipMemcpy(D.val_hi, hi, (size_t)H.nnz * sizeof(u32), hipMemcpyHostToDevice));
-			}
-		}
+		if (hi)
+			HIPCHK(hipMemcpy(D.val_hi, hi, (size_t)H.nnz * sizeof(u32), hipMemcpyHostToDevice));
 	}
 	return plan_csr(c, H.row_ptr, D, hot_rows, dot_slab);
 }
@@ -910,7 +936,7 @@ extern "C" uint64_t blz_prepare_key(const blz_ctx *c, uint64_t content_hash, int
 }
 
 /* What every matrix-setting call drops of the matrix before it: the captured iteration, the scratch of the device blocks,
- * the border.  (The host path and the device build share this and matrix_blocks below.) */
+ * the border.  (The first step of matrix_begin.) */
 static void matrix_reset(blz_ctx *c, int right, int rank, int nranks)
 {
 	if (c->iter_graph) {
@@ -923,6 +949,60 @@ static void matrix_reset(blz_ctx *c, int right, int rank, int nranks)
 	c->nranks = nranks;
 	c->fuse_local_off = false;
 	border_release(c, false);	/* a border belongs to the matrix it was set for */
+}
+
+/* what a matrix-setting call knows of its matrix before a slab of it exists */
+struct MatrixShape {
+	int right, rank, nranks, K;		/* K: pieces per product */
+	int64_t nrows, ncols;			/* of M */
+	const int64_t *bounds[2];		/* per SIDE (0: rows of v, 1: rows of tmp): nranks + 1 row bounds; NULL: one rank, the whole side */
+	int64_t stride[2];			/* per side: rows of a padded slab (read with bounds only) */
+	std::vector<int32_t> perm[2];		/* new index of every row / column of M; empty: the identity */
+	double share[2], locality[2];		/* what the renumbering found, per product (t = 0: M * x gathers by column; t = 1: M^T * x by row) */
+	int order_kind;
+};
+
+/* The first step of every matrix-setting call, the refusals behind it: the matrix that was resident goes, and the context
+ * takes the geometry of the new one.  From here to the end of matrix_blocks the context has no matrix: a call that fails on
+ * the way leaves it so.  csr[t] are K empty slabs, csr_short[t] is empty and no product is in its short-side form. */
+static void matrix_begin(blz_ctx *c, MatrixShape &S)
+{
+	matrix_reset(c, S.right, S.rank, S.nranks);
+	c->have_matrix = false;
+	c->device_built = false;
+	c->device_order = false;
+	/* side 0 = rows of v: rows of M for a left kernel, columns of M for a right kernel
+	 * (sequential/lanczos_modp.c:592-593). */
+	const int rs = S.right ? 1 : 0, cs = 1 - rs;	/* side of M's rows / columns */
+	c->glob_rows[rs] = S.nrows;
+	c->glob_rows[cs] = S.ncols;
+	c->row_side[0] = rs;		/* rows of M   */
+	c->row_side[1] = cs;		/* rows of M^T */
+	for (int sd = 0; sd < 2; sd++) {
+		if (S.bounds[sd]) {
+			c->bounds[sd].assign(S.bounds[sd], S.bounds[sd] + S.nranks + 1);
+			c->stride[sd] = S.stride[sd];
+		} else {
+			c->bounds[sd].assign({ (int64_t)0, c->glob_rows[sd] });
+			c->stride[sd] = c->glob_rows[sd];
+		}
+		c->first[sd] = c->bounds[sd][S.rank];
+		c->count[sd] = c->bounds[sd][S.rank + 1] - c->bounds[sd][S.rank];
+		c->perm[sd] = std::move(S.perm[sd == rs ? 0 : 1]);
+		c->inv[sd].assign(c->perm[sd].size(), 0);
+		for (size_t r = 0; r < c->perm[sd].size(); r++)
+			c->inv[sd][(size_t)c->perm[sd][r]] = (int32_t)r;
+	}
+	for (int t = 0; t < 2; t++) {
+		c->hot_share[t] = S.share[t];
+		c->locality[t] = S.locality[t];
+		for (auto &A : c->csr[t])
+			free_csr(A);
+		c->csr[t].assign((size_t)S.K, DevCsr{});
+		free_csr(c->csr_short[t]);
+		c->short_side[t] = false;
+	}
+	c->order_kind = S.order_kind;
 }
 
 /* The last step of every matrix-setting call, once csr[] and stride[] are what the new matrix wants: the four blocks
@@ -1016,50 +1096,18 @@ static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool
 		return blz_fail(BLZ_EINVAL, "blz_set_matrix_prepared: rank %d of %d, but the context is rank %d of %d in its loopback communicator",
 				rank, nranks, c->loop_rank, c->loop->nranks);
 	HIPCHK(hipSetDevice(c->device));
-	matrix_reset(c, right, rank, nranks);
-	c->device_built = false;
-	c->device_order = false;
-	/* side 0 = rows of v: rows of M for a left kernel, columns of M for a right kernel
-	 * (sequential/lanczos_modp.c:592-593). */
-	c->glob_rows[0] = right ? P->ncols : P->nrows;
-	c->glob_rows[1] = right ? P->nrows : P->ncols;
-	c->row_side[0] = right ? 1 : 0;		/* rows of M   */
-	c->row_side[1] = right ? 0 : 1;		/* rows of M^T */
-	const int rs = right ? 1 : 0, cs = 1 - rs;	/* side of M's rows / columns */
-	for (int sd = 0; sd < 2; sd++) {
-		c->perm[sd].clear();
-		c->inv[sd].clear();
-		c->bounds[sd].assign(P->bounds[sd], P->bounds[sd] + nranks + 1);
-		c->stride[sd] = P->stride[sd];
-		c->first[sd] = c->bounds[sd][rank];
-		c->count[sd] = c->bounds[sd][rank + 1] - c->bounds[sd][rank];
-	}
+	MatrixShape S = { right, rank, nranks, K, P->nrows, P->ncols, { P->bounds[0], P->bounds[1] }, { P->stride[0], P->stride[1] }, {},
+			  { P->share[0], P->share[1] }, { P->locality[0], P->locality[1] }, P->order_kind };
 	if (P->has_perm) {
-		c->perm[rs].assign(P->perm[0], P->perm[0] + P->nrows);
-		c->perm[cs].assign(P->perm[1], P->perm[1] + P->ncols);
-		for (int sd = 0; sd < 2; sd++) {
-			c->inv[sd].resize(c->perm[sd].size());
-			for (size_t r = 0; r < c->perm[sd].size(); r++)
-				c->inv[sd][(size_t)c->perm[sd][r]] = (int32_t)r;
-		}
+		S.perm[0].assign(P->perm[0], P->perm[0] + P->nrows);
+		S.perm[1].assign(P->perm[1], P->perm[1] + P->ncols);
 	}
-	/* what the renumbering found, per product (t = 0: M * x gathers by column; t = 1: M^T * x gathers by row) */
-	c->hot_share[0] = P->share[0];
-	c->hot_share[1] = P->share[1];
-	c->locality[0] = P->locality[0];
-	c->locality[1] = P->locality[1];
-	c->order_kind = P->order_kind;
-	for (int t = 0; t < 2; t++) {
-		for (auto &A : c->csr[t])
-			free_csr(A);
-		c->csr[t].assign((size_t)K, DevCsr{});
-	}
+	matrix_begin(c, S);
 	int rc = BLZ_OK;
 	/* Short-side form of a product whose operand side is at least 8 times longer than its output side (64-bit words:
 	 * the partial sums travel as u64).  BLZ_SHORT_SIDE=0 / 1 forces it off / on (tests, A/B). */
 	size_t part_need = 0, rs_need = 0;
 	for (int t = 0; t < 2; t++) {
-		free_csr(c->csr_short[t]);
 		const int rs_t = c->row_side[t], cs_t = 1 - rs_t;
 		bool on = (nranks > 1 || c->force_comm) && c->cfg.word == 8 && c->glob_rows[cs_t] >= 8 * c->glob_rows[rs_t];
 		if (const char *e = getenv("BLZ_SHORT_SIDE"))
@@ -1083,8 +1131,7 @@ static int set_matrix_prepared(blz_ctx *c, const blz_prepared *P, int rank, bool
 		}
 		blz_csr slab;
 		memset(&slab, 0, sizeof slab);
-		/* product `right` is the second one of the iteration: its (last) launch carries the inner products where that form exists */
-		const bool dot_slab = t == right && c->fuse_dot && spmv_dot_supported(c->cfg);
+		const bool dot_slab = carries_dots(c, t);
 		const bool whole = nranks == 1;		/* one rank: the slab IS the prepared CSR, no copy */
 		if (whole)
 			slab = P->full[t];
@@ -1148,15 +1195,17 @@ extern "C" int blz_set_matrix(blz_ctx *c, const blz_coo *M, int right, int rank,
 		return blz_fail(BLZ_EINVAL, "blz_set_matrix: rank %d of %d", rank, nranks);
 	blz_prepared *P = nullptr;
 	int rc;
-	if (c->wide_hi) {
-		/* Wide value mode: the pending high limbs belong to this matrix and are consumed here, whatever comes of the call
-		 * (a call that fails leaves the context out of the mode: no matrix of it is resident or pending).
-		 * The whole preparation runs on the entry NUMBERS in place of the values; one gather at the end fills both limbs. */
-		const u32 *hi = c->wide_hi;
+	/* Wide value mode: the pending high limbs belong to this matrix and are consumed here, whatever comes of the call
+	 * (a call that fails leaves the context out of the mode: no matrix of it is resident or pending).  An ordinary matrix:
+	 * the mode describes the matrix that is resident or about to be set. */
+	const u32 *hi = c->wide_hi;
+	c->wide_hi = nullptr;
+	c->values_wide = false;
+	blz_coo Mp = *M;	/* what the preparation runs on */
+	std::vector<u32> number;
+	if (hi) {
 		const int64_t hn = c->wide_nnz;
-		c->wide_hi = nullptr;
 		c->wide_nnz = 0;
-		c->values_wide = false;
 		if ((rc = wide_refuse_ranks(c, "blz_set_matrix", nranks)) != BLZ_OK)
 			return rc;
 		if (hn != M->nnz)
@@ -1170,35 +1219,24 @@ extern "C" int blz_set_matrix(blz_ctx *c, const blz_coo *M, int right, int rank,
 		bool any_hi = false;
 		for (int64_t k = 0; k < M->nnz && !any_hi; k++)
 			any_hi = hi[k] != 0;
-		if (!any_hi) {
-			/* every high limb is zero: the ordinary path, value-dependent choices (a matrix of ones is a pattern) included --
-			 * the plans and the words are those of a context that was never given a high array */
-			if ((rc = blz_prepare_for(c, M, right, nranks, &P)) != BLZ_OK)
-				return rc;
-			rc = blz_set_matrix_prepared(c, P, rank);
-			blz_prepared_free(P);
-			c->values_wide = rc == BLZ_OK;
-			return rc;
+		/* Every high limb zero: the ordinary path, value-dependent choices (a matrix of ones is a pattern) included -- the
+		 * plans and the words are those of a context that was never given a high array.  Otherwise the whole preparation
+		 * runs on the entry NUMBERS in place of the values; one gather at the end fills both limbs. */
+		if (any_hi) {
+			number.resize((size_t)M->nnz);
+			for (int64_t k = 0; k < M->nnz; k++)
+				number[(size_t)k] = (u32)k;
+			Mp.x = number.data();
 		}
-		std::vector<u32> number((size_t)std::max<int64_t>(M->nnz, 1));
-		for (int64_t k = 0; k < M->nnz; k++)
-			number[(size_t)k] = (u32)k;
-		blz_coo Mn = *M;
-		Mn.x = number.data();
-		if ((rc = blz_prepare_for(c, &Mn, right, nranks, &P)) != BLZ_OK)
-			return rc;
-		if ((rc = blz_prepared_fill_wide(P, M->x, hi)) == BLZ_OK)
-			rc = blz_set_matrix_prepared(c, P, rank);
-		blz_prepared_free(P);
-		c->values_wide = rc == BLZ_OK;
-		return rc;
 	}
-	c->values_wide = false;		/* (an ordinary matrix: the mode describes the matrix that is resident or about to be set) */
-	rc = blz_prepare_for(c, M, right, nranks, &P);
-	if (rc != BLZ_OK)
+	if ((rc = blz_prepare_for(c, &Mp, right, nranks, &P)) != BLZ_OK)
 		return rc;
-	rc = blz_set_matrix_prepared(c, P, rank);
+	if (!number.empty())
+		rc = blz_prepared_fill_wide(P, M->x, hi);
+	if (rc == BLZ_OK)
+		rc = blz_set_matrix_prepared(c, P, rank);
 	blz_prepared_free(P);
+	c->values_wide = hi && rc == BLZ_OK;
 	return rc;
 }
 
@@ -3478,7 +3516,10 @@ static hipError_t devio_export(blz_ctx *c, W *blk, int64_t ld, int slab, int sd)
 		return launch_w32_export(c->cfg, blk, ld, c->slab[slab], devio_inv(c, sd), c->count[sd], c->un, c->stream);
 }
 
-/* ---- device matrix: M from triplets on the GPU, both CSRs built there (kernels: blz_devmat.hip) ---- */
+/* ---- device matrix: M from triplets on the GPU, both CSRs built there (kernels: blz_devmat.hip).
+ * A build and a host upload (set_matrix_prepared) differ only in how the slabs are filled.  Both refuse first, then go
+ * matrix_begin (the old matrix goes, the geometry and the numbering of the new one are installed), their slabs through
+ * alloc_stream_arrays, plan_csr and slab_whole_choices, and matrix_blocks, which alone makes the matrix resident. ---- */
 
 /* device memory of one build: whatever is still listed when the build leaves, by whichever exit, is freed */
 struct DevmatTmp {
@@ -3506,14 +3547,15 @@ struct DevmatTmp {
 	}
 };
 
-/* BLZ_DEVMAT_TRACE=1: HIP events around the kernels of a build, one line on stderr (tools/device_matrix_cost.py reads it) */
-struct DevmatTrace {
-	enum { COUNT0 = 0, COUNT1, SCAN1, SCATTER0, SCATTER1, PALETTE1, PACK1, MARKS };
+/* BLZ_DEVMAT_TRACE=1: HIP events between the stages of a build or of an ordering.  Each of the two has its own marks and
+ * prints its own line on stderr once its stream has been synchronised (tools/device_matrix_cost.py reads both). */
+struct StageTrace {
+	enum { MAX_MARKS = 8 };
 	bool on = false;
 	hipStream_t st = nullptr;
-	hipEvent_t ev[MARKS] = {};
-	bool set[MARKS] = {};
-	explicit DevmatTrace(hipStream_t s) : st(s)
+	hipEvent_t ev[MAX_MARKS] = {};
+	bool set[MAX_MARKS] = {};
+	explicit StageTrace(hipStream_t s) : st(s)
 	{
 		const char *e = getenv("BLZ_DEVMAT_TRACE");
 		on = e && e[0] == '1';
@@ -3525,6 +3567,7 @@ struct DevmatTrace {
 			set[k] = true;
 		}
 	}
+	bool reached(int k) const { return on && set[k]; }
 	float ms(int a, int b)
 	{
 		float t = 0.0f;
@@ -3532,12 +3575,9 @@ struct DevmatTrace {
 			return 0.0f;
 		return t;
 	}
-	~DevmatTrace()
+	~StageTrace()
 	{
-		if (on && set[SCATTER1] && hipStreamSynchronize(st) == hipSuccess)
-			fprintf(stderr, "blz device build: check+count %.3f ms, scan %.3f ms, scatter %.3f ms, palette %.3f ms, pack %.3f ms\n",
-				ms(COUNT0, COUNT1), ms(COUNT1, SCAN1), ms(SCATTER0, SCATTER1), ms(SCATTER1, PALETTE1), ms(PALETTE1, PACK1));
-		for (int k = 0; k < MARKS; k++)
+		for (int k = 0; k < MAX_MARKS; k++)
 			if (set[k])
 				hipEventDestroy(ev[k]);
 	}
@@ -3582,19 +3622,26 @@ static int devmat_refuse_ptr(const blz_ctx *c, const char *who, const char *arg,
 }
 
 /* The build itself.  i, j, x have passed devmat_refuse_ptr (or are the library's own copies).  Until the counts of the check
- * pass and the two row_ptr arrays have been read the context is untouched; from there on a failure leaves it without a matrix. */
-/* what an ordered build installs after matrix_reset: perm[0] / inv[0] of M's rows, perm[1] / inv[1] of its columns (all
- * empty: the identity, the order of a matrix without entries) */
-struct DevmatNumbering {
-	std::vector<int32_t> perm[2], inv[2];
-};
-
+ * pass and the two row_ptr arrays have been read the context is untouched; from there on (matrix_begin) a failure leaves it
+ * without a matrix.  perm: NULL for a plain build; an ordered build hands over the numbering i, j are already in, perm[0] of
+ * M's rows and perm[1] of its columns (both empty: the identity, the order of a matrix without entries). */
 static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
-			int idx_bytes, const void *x, int val_bytes, int right, DevmatNumbering *numbering)
+			int idx_bytes, const void *x, int val_bytes, int right, std::vector<int32_t> *perm)
 {
+	enum { COUNT0 = 0, COUNT1, SCAN1, SCATTER0, SCATTER1, PALETTE1, PACK1 };
 	DevmatTmp tmp;
 	hipStream_t st = c->stream;
-	DevmatTrace trace(st);
+	StageTrace trace(st);
+	struct Line {	/* the build's line: by whichever exit, once the build got past the scatter */
+		StageTrace &tr;
+		~Line()
+		{
+			if (tr.reached(SCATTER1) && hipStreamSynchronize(tr.st) == hipSuccess)
+				fprintf(stderr, "blz device build: check+count %.3f ms, scan %.3f ms, scatter %.3f ms, palette %.3f ms, pack %.3f ms\n",
+					tr.ms(COUNT0, COUNT1), tr.ms(COUNT1, SCAN1), tr.ms(SCATTER0, SCATTER1), tr.ms(SCATTER1, PALETTE1),
+					tr.ms(PALETTE1, PACK1));
+		}
+	} line{ trace };
 	const int64_t rows_t[2] = { nrows, ncols };	/* rows of CSR(M), of CSR(M^T) */
 	u32 *rp[2] = { nullptr, nullptr };
 	unsigned long long *counts = nullptr;
@@ -3604,9 +3651,9 @@ static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncol
 	}
 	HIPCHK(tmp.alloc((void **)&counts, DEVMAT_COUNTS * sizeof(unsigned long long)));
 	HIPCHK(hipMemsetAsync(counts, 0, DEVMAT_COUNTS * sizeof(unsigned long long), st));
-	trace.mark(DevmatTrace::COUNT0);
+	trace.mark(COUNT0);
 	HIPCHK(launch_devmat_count(c->cfg, idx_bytes, val_bytes, i, j, x, nnz, nrows, ncols, rp[0], rp[1], counts, st));
-	trace.mark(DevmatTrace::COUNT1);
+	trace.mark(COUNT1);
 	unsigned long long hc[DEVMAT_COUNTS];
 	HIPCHK(hipStreamSynchronize(st));
 	HIPCHK(hipMemcpy(hc, counts, sizeof hc, hipMemcpyDeviceToHost));
@@ -3621,7 +3668,7 @@ static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncol
 		HIPCHK(launch_devmat_scan(rp[t], rows_t[t] + 1, sums, st));
 		hrp[t].resize((size_t)rows_t[t] + 1);
 	}
-	trace.mark(DevmatTrace::SCAN1);
+	trace.mark(SCAN1);
 	HIPCHK(hipStreamSynchronize(st));
 	for (int t = 0; t < 2; t++) {
 		HIPCHK(hipMemcpy(hrp[t].data(), rp[t], hrp[t].size() * sizeof(u32), hipMemcpyDeviceToHost));
@@ -3632,49 +3679,19 @@ static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncol
 	/* the choices the host path makes from the values (csr_from_coo_window, upload_csr) */
 	const bool pattern = val_bytes == 0 || hc[DEVMAT_NOT_ONE] == 0;
 	const bool wide = !pattern && hc[DEVMAT_HIGH] != 0 && c->cfg.word == 8;
-	if (wide)
-		for (int t = 0; t < 2; t++)
-			for (int64_t r = 0; r < rows_t[t]; r++)
-				if (hrp[t][(size_t)r + 1] - hrp[t][(size_t)r] > (1u << 30))
-					return blz_fail(BLZ_EINVAL, "a row of a wide slab has more than 2^30 entries: its unreduced sum is not "
-							"bounded (csrc/modp.h)");
+	for (int t = 0; t < 2 && wide; t++) {
+		const int rcw = wide_refuse_long_row(hrp[t].data(), rows_t[t]);
+		if (rcw != BLZ_OK)
+			return rcw;
+	}
 
-	/* ---- the matrix that was resident goes; the context is that of BLZ_NO_REORDER=1 after blz_set_matrix(M, right, 0, 1) ---- */
-	matrix_reset(c, right ? 1 : 0, 0, 1);
-	c->have_matrix = false;
-	c->device_built = false;
-	c->device_order = false;
+	/* ---- the matrix that was resident goes; the context is that of BLZ_NO_REORDER=1 after blz_set_matrix(M, right, 0, 1),
+	 * under the numbering the ordered build hands over ---- */
+	MatrixShape S = { right ? 1 : 0, 0, 1, 1, nrows, ncols, { nullptr, nullptr }, { 0, 0 }, {}, { 0.0, 0.0 }, { 1.0, 1.0 }, 0 };
+	for (int q = 0; q < 2 && perm; q++)
+		S.perm[q] = std::move(perm[q]);
+	matrix_begin(c, S);
 	c->values_wide = wide;
-	c->glob_rows[0] = right ? ncols : nrows;
-	c->glob_rows[1] = right ? nrows : ncols;
-	c->row_side[0] = right ? 1 : 0;
-	c->row_side[1] = right ? 0 : 1;
-	for (int sd = 0; sd < 2; sd++) {
-		c->perm[sd].clear();
-		c->inv[sd].clear();
-		c->bounds[sd].assign({ (int64_t)0, c->glob_rows[sd] });
-		c->stride[sd] = c->glob_rows[sd];
-		c->first[sd] = 0;
-		c->count[sd] = c->glob_rows[sd];
-	}
-	if (numbering) {
-		/* i, j are in the new numbering already; M's rows live on side `right`, its columns on the other (set_matrix_prepared) */
-		const int rs = right ? 1 : 0;
-		for (int q = 0; q < 2; q++) {
-			c->perm[q ? 1 - rs : rs] = std::move(numbering->perm[q]);
-			c->inv[q ? 1 - rs : rs] = std::move(numbering->inv[q]);
-		}
-	}
-	c->hot_share[0] = c->hot_share[1] = 0.0;
-	c->locality[0] = c->locality[1] = 1.0;
-	c->order_kind = 0;
-	for (int t = 0; t < 2; t++) {
-		for (auto &A : c->csr[t])
-			free_csr(A);
-		c->csr[t].assign((size_t)1, DevCsr{});
-		free_csr(c->csr_short[t]);
-		c->short_side[t] = false;
-	}
 	u32 *cur[2] = { nullptr, nullptr };
 	for (int t = 0; t < 2; t++) {
 		DevCsr &D = c->csr[t][0];
@@ -3685,26 +3702,20 @@ static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncol
 		D.locality = 1.0;
 		D.row_ptr = rp[t];
 		tmp.keep(rp[t]);
-		HIPCHK(hipMalloc(&D.col_idx, (size_t)(nnz + BLZ_STREAM_PAD) * sizeof(int)));
-		HIPCHK(hipMemsetAsync(D.col_idx + nnz, 0, BLZ_STREAM_PAD * sizeof(int), st));
-		if (!pattern) {
-			HIPCHK(hipMalloc(&D.val, (size_t)(nnz + BLZ_STREAM_PAD) * sizeof(u32)));
-			HIPCHK(hipMemsetAsync(D.val + nnz, 0, BLZ_STREAM_PAD * sizeof(u32), st));
-			if (wide) {
-				HIPCHK(hipMalloc(&D.val_hi, (size_t)(nnz + BLZ_STREAM_PAD) * sizeof(u32)));
-				HIPCHK(hipMemsetAsync(D.val_hi + nnz, 0, BLZ_STREAM_PAD * sizeof(u32), st));
-			}
-		}
+		/* (the value arrays of a slab that turns out packed go again after the pack) */
+		const int rca = alloc_stream_arrays(D, nnz, !pattern, wide, st);
+		if (rca != BLZ_OK)
+			return rca;
 		/* the cursors: a transient copy of the row pointers */
 		HIPCHK(tmp.alloc((void **)&cur[t], (size_t)std::max<int64_t>(rows_t[t], 1) * sizeof(u32)));
 		HIPCHK(hipMemcpyAsync(cur[t], rp[t], (size_t)rows_t[t] * sizeof(u32), hipMemcpyDeviceToDevice, st));
 	}
 	{
 		DevCsr &A = c->csr[0][0], &B = c->csr[1][0];
-		trace.mark(DevmatTrace::SCATTER0);
+		trace.mark(SCATTER0);
 		HIPCHK(launch_devmat_scatter(c->cfg, idx_bytes, val_bytes, i, j, x, nnz, nrows, ncols, cur[0], cur[1], A.col_idx, A.val,
 					     A.val_hi, B.col_idx, B.val, B.val_hi, st));
-		trace.mark(DevmatTrace::SCATTER1);
+		trace.mark(SCATTER1);
 	}
 	/* Packed stream, by upload_csr's rule: at most 256 distinct values and fewer than 2^24 columns, unless BLZ_NO_PACK.  Both
 	 * slabs hold the same values: one palette, made from CSR(M), ascending, serves both. */
@@ -3720,7 +3731,7 @@ static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncol
 		HIPCHK(hipMemsetAsync(table, 0xFF, DEVMAT_PAL_SLOTS * sizeof(unsigned long long), st));
 		HIPCHK(hipMemsetAsync(pcount, 0, sizeof(unsigned int), st));
 		HIPCHK(launch_devmat_palette(c->cfg, c->csr[0][0].val, c->csr[0][0].val_hi, nnz, table, pcount, keys, st));
-		trace.mark(DevmatTrace::PALETTE1);
+		trace.mark(PALETTE1);
 		HIPCHK(hipStreamSynchronize(st));
 		HIPCHK(hipMemcpy(&hcount, pcount, sizeof hcount, hipMemcpyDeviceToHost));
 		if (hcount >= 1 && hcount <= DEVMAT_PAL_MAX) {
@@ -3742,7 +3753,7 @@ static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncol
 				HIPCHK(hipMemcpy(D.palette, pal.data(), pal.size() * sizeof(u32), hipMemcpyHostToDevice));
 				HIPCHK(launch_devmat_pack(c->cfg, D.col_idx, D.val, D.val_hi, nnz, keys, (int)hcount, st));
 			}
-			trace.mark(DevmatTrace::PACK1);
+			trace.mark(PACK1);
 			HIPCHK(hipStreamSynchronize(st));
 			for (int t = 0; t < 2; t++) {
 				if (!packable[t])
@@ -3758,8 +3769,7 @@ static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncol
 	}
 	HIPCHK(hipStreamSynchronize(st));
 	for (int t = 0; t < 2; t++) {
-		/* product `right` is the second one of the iteration: its launch carries the inner products where that form exists */
-		const bool dot_slab = t == (right ? 1 : 0) && c->fuse_dot && spmv_dot_supported(c->cfg);
+		const bool dot_slab = carries_dots(c, t);
 		const int rc = plan_csr(c, hrp[t].data(), c->csr[t][0], 0, dot_slab);
 		if (rc != BLZ_OK)
 			return rc;
@@ -3767,55 +3777,9 @@ static int devmat_build(blz_ctx *c, const char *who, int64_t nrows, int64_t ncol
 	}
 	const int rc = matrix_blocks(c, 1, 1);
 	c->device_built = rc == BLZ_OK;
-	c->device_order = c->device_built && numbering != nullptr;
+	c->device_order = c->device_built && perm != nullptr;
 	return rc;
 }
-
-static int devmat_build_plain(blz_ctx *c, const char *who, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
-			      int idx_bytes, const void *x, int val_bytes, int right)
-{
-	return devmat_build(c, who, nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right, nullptr);
-}
-
-/* BLZ_DEVMAT_TRACE=1: the passes of the renumbering, one line on stderr in front of the build's own */
-struct DevorderTrace {
-	enum { BEGIN = 0, MIN0, SORT0, MIN1, SORT1, RELABEL, MARKS };
-	bool on = false;
-	hipStream_t st = nullptr;
-	hipEvent_t ev[MARKS] = {};
-	bool set[MARKS] = {};
-	explicit DevorderTrace(hipStream_t s) : st(s)
-	{
-		const char *e = getenv("BLZ_DEVMAT_TRACE");
-		on = e && e[0] == '1';
-	}
-	void mark(int k)
-	{
-		if (on && !set[k] && hipEventCreate(&ev[k]) == hipSuccess) {
-			(void)hipEventRecord(ev[k], st);
-			set[k] = true;
-		}
-	}
-	float ms(int a, int b)
-	{
-		float t = 0.0f;
-		if (!set[a] || !set[b] || hipEventElapsedTime(&t, ev[a], ev[b]) != hipSuccess)
-			return 0.0f;
-		return t;
-	}
-	void report()	/* (the stream has been synchronised) */
-	{
-		if (on && set[RELABEL])
-			fprintf(stderr, "blz device order: row keys %.3f ms, row sort %.3f ms, column keys %.3f ms, column sort %.3f ms, "
-				"relabel %.3f ms\n", ms(BEGIN, MIN0), ms(MIN0, SORT0), ms(SORT0, MIN1), ms(MIN1, SORT1), ms(SORT1, RELABEL));
-	}
-	~DevorderTrace()
-	{
-		for (int k = 0; k < MARKS; k++)
-			if (set[k])
-				hipEventDestroy(ev[k]);
-	}
-};
 
 /* The ordered build: blz_reorder's numbering made on the device (csrc/blz_devorder.hip), the triplets
  * relabelled into int32 copies, then devmat_build on those.  Nothing here touches the context: the resident matrix goes only
@@ -3823,13 +3787,13 @@ struct DevorderTrace {
 static int devmat_build_ordered(blz_ctx *c, const char *who, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
 				int idx_bytes, const void *x, int val_bytes, int right)
 {
-	if (nnz == 0) {		/* nothing to order by: the identity, as blz_prepare leaves a matrix without entries */
-		DevmatNumbering identity;
-		return devmat_build(c, who, nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right, &identity);
-	}
+	std::vector<int32_t> num[2];	/* the new index of every row, of every column */
+	if (nnz == 0)		/* nothing to order by: the identity, as blz_prepare leaves a matrix without entries */
+		return devmat_build(c, who, nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right, num);
+	enum { BEGIN = 0, MIN0, SORT0, MIN1, SORT1, RELABEL };
 	DevmatTmp tmp;
 	hipStream_t st = c->stream;
-	DevorderTrace trace(st);
+	StageTrace trace(st);
 	const int64_t longer = std::max(nrows, ncols), dims[2] = { nrows, ncols };
 	int32_t *key = nullptr, *perm[2] = { nullptr, nullptr }, *bkey[2], *bitem[2], *ni = nullptr, *nj = nullptr;
 	u32 *counters = nullptr, *sums = nullptr;
@@ -3843,32 +3807,34 @@ static int devmat_build_ordered(blz_ctx *c, const char *who, int64_t nrows, int6
 	HIPCHK(tmp.alloc((void **)&sums, (size_t)devmat_scan_tiles(devorder_sort_counters(longer)) * sizeof(u32)));
 	HIPCHK(tmp.alloc((void **)&ni, (size_t)nnz * sizeof(int32_t)));
 	HIPCHK(tmp.alloc((void **)&nj, (size_t)nnz * sizeof(int32_t)));
-	trace.mark(DevorderTrace::BEGIN);
+	trace.mark(BEGIN);
 	/* rows by smallest column (rows without entries: ncols, last), then columns by smallest NEW row */
 	for (int q = 0; q < 2; q++) {
 		HIPCHK(launch_devorder_fill(c->cfg, key, dims[q], (int32_t)dims[1 - q], st));
 		HIPCHK(launch_devorder_min(c->cfg, idx_bytes, i, j, nnz, nrows, ncols, q ? perm[0] : nullptr, key, q, st));
-		trace.mark(q ? DevorderTrace::MIN1 : DevorderTrace::MIN0);
+		trace.mark(q ? MIN1 : MIN0);
 		HIPCHK(launch_devorder_sort(c->cfg, key, dims[q], dims[1 - q], perm[q], bkey, bitem, counters, sums, st));
-		trace.mark(q ? DevorderTrace::SORT1 : DevorderTrace::SORT0);
+		trace.mark(q ? SORT1 : SORT0);
 	}
 	HIPCHK(launch_devorder_relabel(c->cfg, idx_bytes, i, j, nnz, nrows, ncols, perm[0], perm[1], ni, nj, st));
-	trace.mark(DevorderTrace::RELABEL);
+	trace.mark(RELABEL);
 	HIPCHK(hipStreamSynchronize(st));
-	trace.report();
+	if (trace.reached(RELABEL))
+		fprintf(stderr, "blz device order: row keys %.3f ms, row sort %.3f ms, column keys %.3f ms, column sort %.3f ms, "
+			"relabel %.3f ms\n", trace.ms(BEGIN, MIN0), trace.ms(MIN0, SORT0), trace.ms(SORT0, MIN1), trace.ms(MIN1, SORT1),
+			trace.ms(SORT1, RELABEL));
 	/* the numbering on the host, once: the host blocks, the right-hand sides and the checkpoints go through it */
-	DevmatNumbering num;
 	for (int q = 0; q < 2; q++) {
-		num.perm[q].resize((size_t)dims[q]);
-		num.inv[q].assign((size_t)dims[q], (int32_t)-1);
+		num[q].resize((size_t)dims[q]);
 		if (dims[q] > 0)
-			HIPCHK(hipMemcpy(num.perm[q].data(), perm[q], (size_t)dims[q] * sizeof(int32_t), hipMemcpyDeviceToHost));
+			HIPCHK(hipMemcpy(num[q].data(), perm[q], (size_t)dims[q] * sizeof(int32_t), hipMemcpyDeviceToHost));
+		std::vector<bool> taken((size_t)dims[q], false);
 		for (int64_t r = 0; r < dims[q]; r++) {
-			const int64_t to = num.perm[q][(size_t)r];
-			if (to < 0 || to >= dims[q] || num.inv[q][(size_t)to] >= 0)
+			const int64_t to = num[q][(size_t)r];
+			if (to < 0 || to >= dims[q] || taken[(size_t)to])
 				return blz_fail(BLZ_EHIP, "%s: the device sort of the %s did not return a permutation (at %lld)", who,
 						q ? "columns" : "rows", (long long)r);
-			num.inv[q][(size_t)to] = (int32_t)r;
+			taken[(size_t)to] = true;
 		}
 	}
 	/* the transients of the sort go before the build allocates the two CSRs */
@@ -3877,7 +3843,7 @@ static int devmat_build_ordered(blz_ctx *c, const char *who, int64_t nrows, int6
 		tmp.keep(p);
 		hipFree(p);
 	}
-	return devmat_build(c, who, nrows, ncols, nnz, ni, nj, 4, x, val_bytes, right, &num);
+	return devmat_build(c, who, nrows, ncols, nnz, ni, nj, 4, x, val_bytes, right, num);
 }
 
 static int devmat_refuse_order(const char *who, int order)
@@ -3905,7 +3871,9 @@ static int devmat_set_device(blz_ctx *c, const char *who, int64_t nrows, int64_t
 		return rc;
 	if ((rc = devio_wait_caller(c, (hipStream_t)stream)) != BLZ_OK)
 		return rc;
-	return (order ? devmat_build_ordered : devmat_build_plain)(c, who, nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right);
+	if (order)
+		return devmat_build_ordered(c, who, nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right);
+	return devmat_build(c, who, nrows, ncols, nnz, i, j, idx_bytes, x, val_bytes, right, nullptr);
 }
 
 extern "C" int blz_set_matrix_device(blz_ctx *c, int64_t nrows, int64_t ncols, int64_t nnz, const void *i, const void *j,
@@ -3944,7 +3912,9 @@ static int devmat_set_upload(blz_ctx *c, const char *who, const blz_coo *M, int 
 		if (bytes)
 			HIPCHK(hipMemcpy(dev[q], host[q], bytes, hipMemcpyHostToDevice));
 	}
-	return (order ? devmat_build_ordered : devmat_build_plain)(c, who, M->nrows, M->ncols, M->nnz, dev[0], dev[1], 4, dev[2], 4, right);
+	if (order)
+		return devmat_build_ordered(c, who, M->nrows, M->ncols, M->nnz, dev[0], dev[1], 4, dev[2], 4, right);
+	return devmat_build(c, who, M->nrows, M->ncols, M->nnz, dev[0], dev[1], 4, dev[2], 4, right, nullptr);
 }
 
 extern "C" int blz_set_matrix_upload(blz_ctx *c, const blz_coo *M, int right)
