@@ -42,6 +42,7 @@
 #include "blz_devfuse.h"
 #include "blz_devrank.h"
 #include "blz_devw32.h"
+#include "blz_devmfma.h"
 #include "blz_devmat.h"
 #include "blz_devorder.h"
 #include "blz_devrhs.h"
@@ -289,6 +290,11 @@ struct blz_ctx {
 	u64 *devalg_partial = nullptr;
 	/* fused device calls (blz_dot_pair_device): dev_dot2_max_blocks() partial rows of 2 * un * un words, allocated on first use */
 	u64 *devfuse_partial = nullptr;
+	/* device block algebra on the matrix cores (blz_devmfma.hip): the rows from which each (call, width) takes that form
+	 * (BLZ_DEV_MFMA_MIN_ROWS, or the measured defaults), and the digit image of a recombination's coefficients,
+	 * dm_image_bytes_max() = 132 096 bytes, allocated on first use.  The inner products use the partial rows above. */
+	int64_t devmfma_min_rows[DM_NOPS][2] = {};
+	unsigned char *devmfma_img = nullptr;
 	/* device small algebra (blz_rref_device): dev_rref_stack_rows() partial echelon rows of un words and [rank-n flag, rows
 	 * stacked], allocated on first use */
 	u64 *devsmall_stack = nullptr;
@@ -486,6 +492,11 @@ extern "C" int blz_create(blz_ctx **out, int device, uint64_t prime, int n)
 		c->cfg.mfma_stage8 = s8 && s8[0] == '1';
 		const char *mr = getenv("BLZ_MFMA_MIN_ROWS");
 		c->cfg.mfma_min_rows = mr ? atoll(mr) : (n == 16 ? 100000 : 500000);
+		/* the device block algebra's own switch: one row count for every call kind and width, 0 = always */
+		const char *dmr = getenv("BLZ_DEV_MFMA_MIN_ROWS");
+		for (int op = 0; op < DM_NOPS; op++)
+			for (int w = 0; w < 2; w++)
+				c->devmfma_min_rows[op][w] = dmr ? (int64_t)atoll(dmr) : dm_default_min_rows(op, w ? 16 : 8);
 		c->cfg.mfma_img = nullptr;
 		HIPCHK(hipMalloc(&c->cfg.mfma_img, ortho_mfma_image_bytes()));
 	}
@@ -571,6 +582,7 @@ extern "C" void blz_destroy(blz_ctx *c)
 	if (c->bad_dev) hipFree(c->bad_dev);
 	if (c->devalg_partial) hipFree(c->devalg_partial);
 	if (c->devfuse_partial) hipFree(c->devfuse_partial);
+	if (c->devmfma_img) hipFree(c->devmfma_img);
 	if (c->devsmall_stack) hipFree(c->devsmall_stack);
 	if (c->devsmall_ctl) hipFree(c->devsmall_ctl);
 	if (c->devrank_send) hipFree(c->devrank_send);
@@ -4098,6 +4110,47 @@ extern "C" int blz_apply_release(blz_ctx *c)
 /* ---- device block algebra: X^T * Y and sum_t X_t * A_t on caller-owned device memory (kernels: blz_devalg.hip; DESIGN.md
  * section 16).  No matrix is needed and nothing of a solve is read or written: the only state is the scratch of the dot. ---- */
 
+/* The ONE decision whether a 64-bit call takes the matrix-core form (blz_devmfma_plan.h): the launch
+ * sites below and blz_devalg_plan ask here.  aligned16: every tall block's base is 16-byte aligned and every ld even. */
+static int devmfma_decide(const blz_ctx *c, int op, int64_t rows, int nterms, bool aligned16, dm_plan *pl)
+{
+	dm_env e;
+	e.mfma = c->cfg.mfma;
+	e.word_bytes = c->cfg.word;
+	e.p_is_m61 = c->cfg.mers == 61;
+	e.n = c->un;
+	e.num_cu = c->cfg.num_cu;
+	memcpy(e.min_rows, c->devmfma_min_rows, sizeof e.min_rows);
+	return dm_decide(&e, op, rows, nterms, aligned16 ? 1 : 0, pl);
+}
+
+static bool devmfma_aligned(const void *b, int64_t ld)
+{
+	return ((uintptr_t)b & 15) == 0 && (ld & 1) == 0;
+}
+
+extern "C" int blz_devalg_plan(const blz_ctx *c, int op, int64_t rows, int nterms, int aligned16, struct blz_devalg_plan *out)
+{
+	if (!c || !out)
+		return blz_fail(BLZ_EINVAL, "blz_devalg_plan: no context or out is NULL");
+	if (op != BLZ_DEVOP_DOT && op != BLZ_DEVOP_DOT_PAIR && op != BLZ_DEVOP_COMBINE && op != BLZ_DEVOP_COMBINE_PAIR)
+		return blz_fail(BLZ_EINVAL, "blz_devalg_plan: op = %d is none of BLZ_DEVOP_DOT, BLZ_DEVOP_DOT_PAIR, BLZ_DEVOP_COMBINE, "
+				"BLZ_DEVOP_COMBINE_PAIR", op);
+	if (nterms < 1 || nterms > BLZ_MAX_TERMS)
+		return blz_fail(BLZ_EINVAL, "blz_devalg_plan: nterms = %d is outside 1..%d", nterms, BLZ_MAX_TERMS);
+	dm_plan pl;
+	if (devmfma_decide(c, op, rows, nterms, aligned16 != 0, &pl) != 0)
+		return blz_fail(BLZ_EINVAL, "blz_devalg_plan: op = %d, nterms = %d", op, nterms);
+	memset(out, 0, sizeof *out);
+	out->form = pl.form;
+	out->min_rows = pl.min_rows;
+	out->tile_rows = pl.tile_rows;
+	out->wavefronts = pl.wavefronts;
+	out->fold_tiles = pl.fold_tiles;
+	out->lds_bytes = pl.lds_bytes;
+	return BLZ_OK;
+}
+
 /* the inner products of both arities and both word widths: nx = 1 writes n * n words, nx = 2 two contiguous panels (the fused
  * call of DESIGN.md section 18, in its own kernel and with a scratch of its own) */
 template <typename W>
@@ -4144,12 +4197,23 @@ static int devalg_dot(blz_ctx *c, const char *who, int64_t rows, int nx, const W
 		/* on ranks: this rank's residues into the send buffer, their sums over the ranks (both panels through one all-reduce),
 		 * the sums' residues into c */
 		u64 *dst = collective ? c->devrank_send : out;
-		if constexpr (sizeof(W) == 4)
+		if constexpr (sizeof(W) == 4) {
 			HIPCHK(launch_w32_dot(c->cfg, n, rows, nx, x, ldl, y, ldy, *partial, dst, c->stream));
-		else if (nx == 1)
-			HIPCHK(launch_dev_dot(c->cfg, n, rows, x[0], ldl[0], y, ldy, *partial, dst, c->stream));
-		else
-			HIPCHK(launch_dev_dot2(c->cfg, n, rows, x[0], ldl[0], x[1], ldl[1], y, ldy, *partial, dst, c->stream));
+		} else {
+			dm_plan pl;
+			bool al = devmfma_aligned(y, ldy);
+			for (int k = 0; k < nx; k++)
+				al = al && devmfma_aligned(x[k], ldx[k]);
+			if (devmfma_decide(c, nx == 1 ? DM_OP_DOT : DM_OP_DOT_PAIR, rows, 1, al, &pl) != 0)
+				return blz_fail(BLZ_EINVAL,"%s: no plan", who);
+			if (pl.form == 1)	/* (the scratch of either arity holds at least dev_dot_max_blocks() of its rows) */
+				HIPCHK(launch_devmfma_dot(pl, n, rows, nx, x[0], ldl[0], nx == 2 ? x[1] : nullptr, ldl[nx - 1], y, ldy,
+							  *partial, dev_dot_max_blocks(c->cfg, n), dst, c->stream));
+			else if (nx == 1)
+				HIPCHK(launch_dev_dot(c->cfg, n, rows, x[0], ldl[0], y, ldy, *partial, dst, c->stream));
+			else
+				HIPCHK(launch_dev_dot2(c->cfg, n, rows, x[0], ldl[0], x[1], ldl[1], y, ldy, *partial, dst, c->stream));
+		}
 		if (collective && (rc_ = devrank_dot_finish(c, out, nx * n * n)) != BLZ_OK)
 			return rc_;
 		return devio_leave(c, caller);
@@ -4238,12 +4302,28 @@ static int devalg_combine(blz_ctx *c, const char *who, int64_t rows, int nterms,
 	hipStream_t caller = (hipStream_t)stream;
 	if ((rc = devio_wait_caller(c, caller)) != BLZ_OK)
 		return rc;
-	if constexpr (sizeof(W) == 4)
+	if constexpr (sizeof(W) == 4) {
 		HIPCHK(launch_w32_combine(c->cfg, n, rows, nterms, x, ldl, nz, a0, a1, z0, ldz0, z1, ldz1, c->stream));
-	else if (nz == 1)
-		HIPCHK(launch_dev_combine(c->cfg, n, rows, nterms, x, ldl, a0, z0, ldz0, c->stream));
-	else
-		HIPCHK(launch_dev_combine2(c->cfg, n, rows, nterms, x, ldl, a0, a1, z0, ldz0, z1, ldz1, c->stream));
+	} else {
+		dm_plan pl;
+		bool al = true;
+		for (int o = 0; o < nz; o++)
+			al = al && devmfma_aligned(z[o], ldz[o]);
+		for (int t = 0; t < nterms; t++)
+			al = al && devmfma_aligned(x[t], ldx[t]);
+		if (devmfma_decide(c, nz == 1 ? DM_OP_COMBINE : DM_OP_COMBINE_PAIR, rows, nterms, al, &pl) != 0)
+			return blz_fail(BLZ_EINVAL,"%s: no plan", who);
+		if (pl.form == 1) {
+			if (!c->devmfma_img)
+				HIPCHK(hipMalloc((void **)&c->devmfma_img, (size_t)dm_image_bytes_max()));
+			HIPCHK(launch_devmfma_combine(pl, n, rows, nterms, x, ldl, a0, nz == 2 ? a1 : nullptr, z0, ldz0, z1, ldz1,
+						      c->devmfma_img, c->stream));
+		} else if (nz == 1) {
+			HIPCHK(launch_dev_combine(c->cfg, n, rows, nterms, x, ldl, a0, z0, ldz0, c->stream));
+		} else {
+			HIPCHK(launch_dev_combine2(c->cfg, n, rows, nterms, x, ldl, a0, a1, z0, ldz0, z1, ldz1, c->stream));
+		}
+	}
 	return devio_leave(c, caller);
 }
 

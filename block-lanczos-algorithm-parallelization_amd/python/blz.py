@@ -58,6 +58,15 @@ class Plan(C.Structure):
 FORMS = ("spmv", "staged", "panel")
 
 
+class DevalgPlan(C.Structure):
+    """struct blz_devalg_plan of include/blz.h."""
+    _fields_ = [(k, C.c_int32) for k in ("form", "tile_rows", "wavefronts", "fold_tiles")] + \
+               [(k, C.c_int64) for k in ("min_rows", "lds_bytes")]
+
+
+DEVOP_DOT, DEVOP_DOT_PAIR, DEVOP_COMBINE, DEVOP_COMBINE_PAIR = range(4)     # BLZ_DEVOP_* of include/blz.h
+
+
 def lib():
     """Load libblz_hip.so.  Raises if it has not been built: there is no Python/CPU substitute."""
     global _lib
@@ -1073,6 +1082,16 @@ class Context:
                 val["form"] = FORMS[val["form"]]
             res[name] = val
         return res
+
+    def devalg_plan(self, op, rows, nterms=1, aligned=True):
+        """blz_devalg_plan(): which kernels the device block algebra call `op` (DEVOP_DOT, DEVOP_DOT_PAIR, DEVOP_COMBINE,
+        DEVOP_COMBINE_PAIR) will run for `rows` rows and `nterms` terms, on blocks that all have a 16-byte aligned base and an
+        even ld (aligned) or not, as a dict: form (0 vector ALU, 1 matrix cores), min_rows, tile_rows, wavefronts, fold_tiles,
+        lds_bytes.  Nothing is launched; no matrix is needed."""
+        out = DevalgPlan()
+        check(lib().blz_devalg_plan(self.h, C.c_int(int(op)), C.c_int64(int(rows)), C.c_int(int(nterms)),
+                                    C.c_int(1 if aligned else 0), C.byref(out)))
+        return {name: int(getattr(out, name)) for name, _ in DevalgPlan._fields_}
 
     def owner_of_row(self, block, row):
         return int(lib().blz_owner_of_row(self.h, C.c_int(block), C.c_int64(row)))

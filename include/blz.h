@@ -559,6 +559,22 @@ typedef struct blz_plan {
 } blz_plan;
 int blz_slab_plan(const blz_ctx *c, int transpose, int piece, blz_plan *out);
 
+/* Read-only view of the plan of one device block algebra call (tests): which kernels blz_dot_device, blz_dot_pair_device,
+ * blz_combine_device or blz_combine_pair_device WILL run for `rows` rows (and `nterms` terms of a recombination; 1 for an
+ * inner product) on blocks that all have a 16-byte aligned base and an even ld (aligned16 != 0) or not -- taken from the same
+ * function the launches decide with.  Nothing is launched, nothing changes and no matrix is needed.  An op that is none of the
+ * four, or nterms outside 1..BLZ_MAX_TERMS, is BLZ_EINVAL.  (The structure has the function's name: write `struct`.) */
+enum { BLZ_DEVOP_DOT = 0, BLZ_DEVOP_DOT_PAIR = 1, BLZ_DEVOP_COMBINE = 2, BLZ_DEVOP_COMBINE_PAIR = 3 };
+struct blz_devalg_plan {
+	int32_t form;			/* 0: the vector-ALU kernels; 1: the matrix cores (p = 2^61 - 1, n = 8 or 16 only) */
+	int32_t tile_rows;		/* form 1: rows of one MFMA tile (16 in a recombination, 64 in an inner product) */
+	int32_t wavefronts;		/* form 1: wavefronts the launch starts; they take the tiles in turn */
+	int32_t fold_tiles;		/* form 1, inner products: tiles between two folds of the int32 accumulators; else 0 */
+	int64_t min_rows;		/* the threshold in force for this call kind and width (INT64_MAX: never by default) */
+	int64_t lds_bytes;		/* form 1: LDS of a workgroup (a recombination: the coefficients' digit image) */
+};
+int blz_devalg_plan(const blz_ctx *c, int op, int64_t rows, int nterms, int aligned16, struct blz_devalg_plan *out);
+
 /* The solver's numbering of one side (tests): perm[r] = the new index of original row r of `block`'s side, blz_rows(ctx, block)
  * words.  Returns 1 when a numbering is resident and 0 when it is the identity (perm is then 0, 1, 2, ...); a negative error
  * code for a bad argument or a context that holds one rank of several.  Host-built and device-built matrices alike. */
@@ -655,7 +671,16 @@ int blz_apply_release(blz_ctx *ctx);
  *                     z[r*ldz + j] = sum_t sum_i x[t][r*ldx[t] + i] * a[t][i*n + j].  z may BE one or more of the x[t] -- the
  *                     same pointer and the same stride: the in-place form, exact; otherwise z must overlap no x[t].  z must
  *                     overlap no a[t].  rows == 0: z is not touched.
- * Limits: one rank; vector-ALU kernels only (no matrix-core form at p = 2^61 - 1 yet); residues are not validated. */
+ * Matrix cores: at p = 2^61 - 1 with 8-byte words and n = 8 or 16 both calls run as exact integer contractions of base-256
+ * digits on v_mfma_i32_16x16x64_i8 (csrc/blz_devmfma.hip) -- the same words -- when BLZ_NO_MFMA is not 1,
+ * every tall block of the call has a 16-byte aligned base and an even ld, and rows reaches the threshold of the call kind and
+ * width: blz_dot_device 65 536 rows at n = 8 and at n = 16, blz_combine_device 1 048 576 rows at n = 8 and 65 536 at n = 16
+ * (one MI355X, profiles/device_mfma_cost.txt).  BLZ_DEV_MFMA_MIN_ROWS=k, read at blz_create, sets every threshold to k (0:
+ * always).  Anything else runs the vector-ALU kernels as before.  blz_combine_device keeps the digit image of its
+ * coefficients in a scratch of the context's own: 132 096 bytes (the largest image: two outputs, four terms, n = 16),
+ * allocated on first use and freed by blz_destroy; the inner products add no scratch to the partial rows above.
+ * blz_devalg_plan reports the decision.
+ * Limits: one rank; residues are not validated. */
 #define BLZ_MAX_TERMS 4
 int blz_dot_device(blz_ctx *ctx, int64_t rows, const uint64_t *x, int64_t ldx, const uint64_t *y, int64_t ldy, uint64_t *c,
 		   void *stream);
@@ -746,7 +771,11 @@ int blz_rref_device(blz_ctx *ctx, int64_t rows, const uint64_t *x, int64_t ldx, 
  *                          z1 overlap each other nowhere and neither overlaps a coefficient matrix.  rows == 0: nothing is
  *                          touched.  One launch at every width and panel count.  The update of :478-491 is one call: terms
  *                          (Av, coef[V_AV], NULL), (v, coef[V_V], coef[P_V]), (p, coef[V_P], coef[P_P]), z0 = v, z1 = p.
- * Limits: one rank; no capturing stream; residues are not validated; vector-ALU kernels only. */
+ * Matrix cores: blz_dot_pair_device and blz_combine_pair_device take the matrix-core forms under the conditions stated at
+ * blz_combine_device (p = 2^61 - 1, n = 8 or 16, 16-byte aligned blocks of even ld, BLZ_NO_MFMA not 1): blz_dot_pair_device from
+ * 65 536 rows at either width, blz_combine_pair_device from 262 144 rows at n = 8 and 65 536 at n = 16 (BLZ_DEV_MFMA_MIN_ROWS
+ * overrides); at n = 8 the pair's outputs share one 16-column tile.  The scratch is that of the unpaired calls.
+ * Limits: one rank; no capturing stream; residues are not validated. */
 int blz_apply_pair_device(blz_ctx *ctx, int transpose_first, const uint64_t *x, int64_t ldx, uint64_t *y, int64_t ldy,
 			  uint64_t *z, int64_t ldz, void *stream);
 int blz_dot_pair_device(blz_ctx *ctx, int64_t rows, const uint64_t *x0, int64_t ldx0, const uint64_t *x1, int64_t ldx1,
