@@ -39,7 +39,6 @@
 #include "blz_devio.h"
 #include "blz_devalg.h"
 #include "blz_devsmall.h"
-#include "blz_devfuse.h"
 #include "blz_devrank.h"
 #include "blz_devw32.h"
 #include "blz_devmfma.h"
@@ -288,7 +287,7 @@ struct blz_ctx {
 	DevCtl *apply_ctl = nullptr;			/* control words of blz_apply_device's products: the stop flag never up */
 	/* device block algebra (blz_dot_device): dev_dot_max_blocks() partial rows of un * un words, allocated on first use */
 	u64 *devalg_partial = nullptr;
-	/* fused device calls (blz_dot_pair_device): dev_dot2_max_blocks() partial rows of 2 * un * un words, allocated on first use */
+	/* fused device calls (blz_dot_pair_device): dev_dot_max_blocks() partial rows of 2 * un * un words, allocated on first use */
 	u64 *devfuse_partial = nullptr;
 	/* device block algebra on the matrix cores (blz_devmfma.hip): the rows from which each (call, width) takes that form
 	 * (BLZ_DEV_MFMA_MIN_ROWS, or the measured defaults), and the digit image of a recombination's coefficients,
@@ -4186,8 +4185,7 @@ static int devalg_dot(blz_ctx *c, const char *who, int64_t rows, int nx, const W
 	auto enqueue = [&]() -> int {
 		u64 **partial = nx == 1 ? &c->devalg_partial : &c->devfuse_partial;
 		if (!*partial)
-			HIPCHK(hipMalloc((void **)partial, nx == 1 ? (size_t)dev_dot_max_blocks(c->cfg, n) * n * n * sizeof(u64)
-								   : (size_t)dev_dot2_max_blocks(c->cfg, n) * 2 * n * n * sizeof(u64)));
+			HIPCHK(hipMalloc((void **)partial, (size_t)dev_dot_max_blocks(c->cfg, n) * nx * n * n * sizeof(u64)));
 		int rc_ = collective ? devrank_dot_buffers(c) : BLZ_OK;
 		if (rc_ != BLZ_OK)
 			return rc_;
@@ -4209,10 +4207,8 @@ static int devalg_dot(blz_ctx *c, const char *who, int64_t rows, int nx, const W
 			if (pl.form == 1)	/* (the scratch of either arity holds at least dev_dot_max_blocks() of its rows) */
 				HIPCHK(launch_devmfma_dot(pl, n, rows, nx, x[0], ldl[0], nx == 2 ? x[1] : nullptr, ldl[nx - 1], y, ldy,
 							  *partial, dev_dot_max_blocks(c->cfg, n), dst, c->stream));
-			else if (nx == 1)
-				HIPCHK(launch_dev_dot(c->cfg, n, rows, x[0], ldl[0], y, ldy, *partial, dst, c->stream));
 			else
-				HIPCHK(launch_dev_dot2(c->cfg, n, rows, x[0], ldl[0], x[1], ldl[1], y, ldy, *partial, dst, c->stream));
+				HIPCHK(launch_dev_dot(c->cfg, n, rows, nx, x, ldl, y, ldy, *partial, dst, c->stream));
 		}
 		if (collective && (rc_ = devrank_dot_finish(c, out, nx * n * n)) != BLZ_OK)
 			return rc_;
@@ -4318,10 +4314,8 @@ static int devalg_combine(blz_ctx *c, const char *who, int64_t rows, int nterms,
 				HIPCHK(hipMalloc((void **)&c->devmfma_img, (size_t)dm_image_bytes_max()));
 			HIPCHK(launch_devmfma_combine(pl, n, rows, nterms, x, ldl, a0, nz == 2 ? a1 : nullptr, z0, ldz0, z1, ldz1,
 						      c->devmfma_img, c->stream));
-		} else if (nz == 1) {
-			HIPCHK(launch_dev_combine(c->cfg, n, rows, nterms, x, ldl, a0, z0, ldz0, c->stream));
 		} else {
-			HIPCHK(launch_dev_combine2(c->cfg, n, rows, nterms, x, ldl, a0, a1, z0, ldz0, z1, ldz1, c->stream));
+			HIPCHK(launch_dev_combine(c->cfg, n, rows, nterms, x, ldl, nz, a0, a1, z0, ldz0, z1, ldz1, c->stream));
 		}
 	}
 	return devio_leave(c, caller);
@@ -4334,7 +4328,7 @@ extern "C" int blz_combine_device(blz_ctx *c, int64_t rows, int nterms, const ui
 }
 
 /* ---- fused device calls: z = op2 (op1 x), two inner products against one block, two recombinations of shared inputs, each in
- * one call and one pass (kernels: blz_devfuse.hip).  Nothing of a solve is read or written: the state is
+ * one call and one pass (kernels: blz_devalg.hip).  Nothing of a solve is read or written: the state is
  * the scratch slabs and control words of blz_apply_device and a scratch of blz_dot_pair_device's own. ---- */
 
 template <typename W>

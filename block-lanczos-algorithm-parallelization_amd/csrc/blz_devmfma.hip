@@ -2,7 +2,7 @@
  * blz_devmfma.hip -- the device block algebra on the matrix cores: blz_dot_device, blz_dot_pair_device, blz_combine_device and
  * blz_combine_pair_device at p = 2^61 - 1, n = 8 or 16, on a caller's strided u64 rows.  Exact integer
  * contractions of base-256 digits on v_mfma_i32_16x16x64_i8; the words written are the ones the vector-ALU kernels of
- * blz_devalg.hip / blz_devfuse.hip write.  Which form a call takes is decided in blz_devmfma_plan.h.
+ * blz_devalg.hip write.  Which form a call takes is decided in blz_devmfma_plan.h.
  *
  * k_dm_combine: Z = sum_t X_t * A_t, the scheme of k_ortho_mfma (header comment of blz_dense_mfma.hip) without its non-product
  * term and with the rows at the caller's stride.
@@ -27,9 +27,10 @@
  * 2^30 and are folded every DM_DOT_FOLD_TILES tiles of 64 rows, before they can leave [2^29, 3 * 2^29].
  * n = 16: operands X_p and Y, one product per left block.  n = 8, one left block: ONE operand [X | Y], whose product with
  * itself holds X^T Y in its upper right 8 x 8; n = 8, two: [X0 | X1] against [Y | Y], X0^T Y above X1^T Y in columns 0..7.
- * Every workgroup writes one partial row; k_dm_dot_finalize adds them mod p (as k_dev_dot_finalize does).
+ * Every workgroup writes one partial row; launch_dev_dot_finalize (blz_devalg.h) adds them mod p.
  */
 #include "blz_devmfma.h"
+#include "blz_devhelp.h"
 #include "ortho_img.h"
 
 #include <type_traits>
@@ -192,25 +193,28 @@ k_dm_combine(DmCombineArgs g, int pair, long long rows, const unsigned char *__r
 	}
 }
 
+/* (the image of an instantiation has one size: its LDS is the most it can ask for) */
 template <int NT, int NTERMS, int SETS>
-void combine_go(const dm_plan &pl, const DmCombineArgs &g, int pair, long long rows, const unsigned char *img, hipStream_t s)
+hipError_t combine_go(const dm_plan &pl, const DmCombineArgs &g, int pair, long long rows, const unsigned char *img, hipStream_t s)
 {
-	const void *fn = (const void *)k_dm_combine<NT, NTERMS, SETS>;
-	if (pl.lds_bytes > 48 * 1024)
-		(void)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds_bytes);
+	const hipError_t e = dev_lds_limit<&k_dm_combine<NT, NTERMS, SETS>>((size_t)pl.lds_bytes,
+									     (size_t)dm_image_bytes(SETS, dm_combine_ksteps(NT, NTERMS)));
+	if (e != hipSuccess)
+		return e;
 	hipLaunchKernelGGL((k_dm_combine<NT, NTERMS, SETS>), dim3((unsigned)pl.blocks), dim3((unsigned)pl.threads), (size_t)pl.lds_bytes, s,
 			   g, pair, rows, img);
+	return hipGetLastError();
 }
 
 template <int NT, int SETS>
-void combine_terms(int nterms, const dm_plan &pl, const DmCombineArgs &g, int pair, long long rows, const unsigned char *img,
-		   hipStream_t s)
+hipError_t combine_terms(int nterms, const dm_plan &pl, const DmCombineArgs &g, int pair, long long rows, const unsigned char *img,
+			 hipStream_t s)
 {
 	switch (nterms) {
-	case 1: combine_go<NT, 1, SETS>(pl, g, pair, rows, img, s); break;
-	case 2: combine_go<NT, 2, SETS>(pl, g, pair, rows, img, s); break;
-	case 3: combine_go<NT, 3, SETS>(pl, g, pair, rows, img, s); break;
-	default: combine_go<NT, 4, SETS>(pl, g, pair, rows, img, s); break;
+	case 1: return combine_go<NT, 1, SETS>(pl, g, pair, rows, img, s);
+	case 2: return combine_go<NT, 2, SETS>(pl, g, pair, rows, img, s);
+	case 3: return combine_go<NT, 3, SETS>(pl, g, pair, rows, img, s);
+	default: return combine_go<NT, 4, SETS>(pl, g, pair, rows, img, s);
 	}
 }
 
@@ -430,27 +434,6 @@ k_dm_dot(const u64 *__restrict__ x0, long long ldx0, const u64 *__restrict__ x1,
 	}
 }
 
-/* out[e] = sum_b partial[b][e] mod p, e < words: k_dev_dot_finalize of blz_devalg.hip (which is local to that file).  A
- * workgroup owns 8 adjacent words, a thread is (row lane, word). */
-__global__ void __launch_bounds__(256)
-k_dm_dot_finalize(const u64 *__restrict__ partial, int nblocks, int words, u64 *__restrict__ out)
-{
-	__shared__ u64 red[256];
-	const int wl = threadIdx.x & 7, rl = threadIdx.x >> 3, e = blockIdx.x * 8 + wl;
-	u64 s = 0;
-	if (e < words)
-		for (int b = rl; b < nblocks; b += 32)
-			s = addmod(s, partial[(size_t)b * words + e], P61);
-	red[threadIdx.x] = s;
-	__syncthreads();
-	if (threadIdx.x < 8 && e < words) {
-		u64 tsum = 0;
-		for (int r = 0; r < 32; r++)
-			tsum = addmod(tsum, red[r * 8 + threadIdx.x], P61);
-		out[e] = tsum;
-	}
-}
-
 }  // namespace
 
 hipError_t launch_devmfma_dot(const dm_plan &pl, int n, long long rows, int nx, const u64 *x0, long long ldx0, const u64 *x1,
@@ -473,9 +456,7 @@ hipError_t launch_devmfma_dot(const dm_plan &pl, int n, long long rows, int nx, 
 		hipLaunchKernelGGL((k_dm_dot<8, 1>), grid, block, 0, s, x0, ldx0, x1, ldx1, y, ldy, rows, same01, same0y, same1y, partial);
 	else
 		hipLaunchKernelGGL((k_dm_dot<8, 2>), grid, block, 0, s, x0, ldx0, x1, ldx1, y, ldy, rows, same01, same0y, same1y, partial);
-	const int words = nx * n * n;
-	hipLaunchKernelGGL(k_dm_dot_finalize, dim3((unsigned)((words + 7) / 8)), dim3(256), 0, s, partial, pl.blocks, words, out);
-	return hipGetLastError();
+	return launch_dev_dot_finalize(partial, pl.blocks, nx * n * n, P61, out, s);
 }
 
 hipError_t launch_devmfma_combine(const dm_plan &pl, int n, long long rows, int nterms, const u64 *const *x, const long long *ldx,
@@ -502,12 +483,9 @@ hipError_t launch_devmfma_combine(const dm_plan &pl, int n, long long rows, int 
 	if (n == 16) {
 		hipLaunchKernelGGL((k_dm_prep<16>), dim3(prep_grid), dim3(256), 0, s, g, pl.sets, pl.ksteps, img);
 		if (pl.sets == 2)
-			combine_terms<16, 2>(nterms, pl, g, pair, rows, img, s);
-		else
-			combine_terms<16, 1>(nterms, pl, g, pair, rows, img, s);
-	} else {
-		hipLaunchKernelGGL((k_dm_prep<8>), dim3(prep_grid), dim3(256), 0, s, g, pl.sets, pl.ksteps, img);
-		combine_terms<8, 1>(nterms, pl, g, pair, rows, img, s);
+			return combine_terms<16, 2>(nterms, pl, g, pair, rows, img, s);
+		return combine_terms<16, 1>(nterms, pl, g, pair, rows, img, s);
 	}
-	return hipGetLastError();
+	hipLaunchKernelGGL((k_dm_prep<8>), dim3(prep_grid), dim3(256), 0, s, g, pl.sets, pl.ksteps, img);
+	return combine_terms<8, 1>(nterms, pl, g, pair, rows, img, s);
 }

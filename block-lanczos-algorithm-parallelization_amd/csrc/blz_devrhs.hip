@@ -14,6 +14,7 @@
  * blocks pay (blz_devio.hip).  Grid-stride over the flat index; plain stores.
  */
 #include "blz_devrhs.h"
+#include "blz_devhelp.h"
 
 namespace {
 
@@ -72,14 +73,6 @@ inline unsigned grid_for(const KernelCfg &c, long long total)
 {
 	const long long want = (total + BLOCK - 1) / BLOCK, cap = (long long)c.num_cu * 8;
 	return (unsigned)(want < cap ? want : cap);
-}
-
-inline int log2_ceil(int units)
-{
-	int lg = 0;
-	while ((1 << lg) < units)
-		lg++;
-	return lg;
 }
 
 }  // namespace

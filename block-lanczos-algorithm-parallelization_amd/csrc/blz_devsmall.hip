@@ -27,6 +27,7 @@
  * reaches rank n raises a flag every workgroup reads once per tile -- a block of full rank is not read whole.
  */
 #include "blz_devsmall.h"
+#include "blz_devhelp.h"
 
 #include <algorithm>
 
@@ -34,11 +35,6 @@ namespace {
 
 constexpr int BLOCK = 256;
 constexpr int MAXN = 64;
-
-__device__ __forceinline__ u64 shfl64(u64 v, int src)
-{
-	return (u64)__shfl((unsigned long long)v, src, 64);
-}
 
 MODP_DEV u64 submod(u64 a, u64 b, u64 p) { return a >= b ? a - b : a + (p - b); }
 
@@ -487,12 +483,14 @@ int partial_blocks(const KernelCfg &c, long long rows, int n)
 }
 
 template <int MERS>
-void chain_go(unsigned threads, size_t lds, hipStream_t s, const u64 *vtav, const u64 *vtaav, u64 *winv, u64 *d, u64 *coef, u64 *npiv,
-	      int n, int lg, const ModP &m)
+hipError_t chain_go(unsigned threads, size_t lds, hipStream_t s, const u64 *vtav, const u64 *vtaav, u64 *winv, u64 *d, u64 *coef,
+		    u64 *npiv, int n, int lg, const ModP &m)
 {
-	if (lds > 48 * 1024)
-		(void)hipFuncSetAttribute((const void *)k_dev_chain<MERS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+	const hipError_t e = dev_lds_limit<&k_dev_chain<MERS>>(lds, chain_lds_words(MAXN, true) * sizeof(u64));
+	if (e != hipSuccess)
+		return e;
 	hipLaunchKernelGGL((k_dev_chain<MERS>), dim3(1), dim3(threads), lds, s, vtav, vtaav, winv, d, coef, npiv, n, lg, m);
+	return hipGetLastError();
 }
 
 template <int MERS>
@@ -513,18 +511,14 @@ hipError_t launch_dev_chain(const KernelCfg &c, int n, const u64 *vtav, const u6
 {
 	if (n < 1 || n > MAXN || !vtav || (coef ? !vtaav : (!winv || !d)))
 		return hipErrorInvalidValue;
-	int lg = 0;
-	while ((1 << lg) < n)
-		lg++;
+	const int lg = log2_ceil(n);
 	const unsigned threads = (unsigned)std::min(1024, std::max(64, 1 << (2 * lg)));
 	const size_t lds = chain_lds_words(n, coef != nullptr) * sizeof(u64);
 	if (c.mers == 61)
-		chain_go<61>(threads, lds, s, vtav, vtaav, winv, d, coef, npiv, n, lg, c.m);
-	else if (c.mers == 31)
-		chain_go<31>(threads, lds, s, vtav, vtaav, winv, d, coef, npiv, n, lg, c.m);
-	else
-		chain_go<0>(threads, lds, s, vtav, vtaav, winv, d, coef, npiv, n, lg, c.m);
-	return hipGetLastError();
+		return chain_go<61>(threads, lds, s, vtav, vtaav, winv, d, coef, npiv, n, lg, c.m);
+	if (c.mers == 31)
+		return chain_go<31>(threads, lds, s, vtav, vtaav, winv, d, coef, npiv, n, lg, c.m);
+	return chain_go<0>(threads, lds, s, vtav, vtaav, winv, d, coef, npiv, n, lg, c.m);
 }
 
 long long dev_rref_stack_rows(const KernelCfg &c, int n)

@@ -1,7 +1,7 @@
 /* blz_devw32.h -- launchers of the 32-bit device-block kernels (blz_devw32.hip): the device-block family on a caller's blocks
  * of uint32_t words -- rows x n residues below p < 2^32, row stride ld counted in 32-bit words, the words n .. ld-1 of a row
  * never read or written.  The n x n operands (results of the inner products, coefficients of the recombinations) are
- * contiguous u64 words, as in blz_devalg.h and blz_devfuse.h.  Only contexts of 4-byte words (c.word == 4) come here.
+ * contiguous u64 words, as in blz_devalg.h.  Only contexts of 4-byte words (c.word == 4) come here.
  * C++ side only; not part of the C ABI. */
 #ifndef BLZ_DEVW32_H
 #define BLZ_DEVW32_H
@@ -26,10 +26,9 @@ hipError_t launch_w32_export(const KernelCfg &c, u32 *caller, long long ld, cons
 			     int un, hipStream_t s);
 
 /* out[k * n * n + i * n + j] = sum_r x[k][r * ldx[k] + i] * y[r * ldy + j] mod p for k < nx, nx = 1 (blz_dot_device32) or 2
- * (blz_dot_pair_device32).  Blocks that are the same pointer with the same stride are staged once.  Every workgroup writes
- * ONE row of nx * n * n canonical u64 residues to `partial` -- room for dev_dot_max_blocks() rows of n * n words at nx = 1,
- * dev_dot2_max_blocks() rows of 2 * n * n at nx = 2: the scratch of the 64-bit namesakes -- and a second launch adds the rows
- * mod p into `out`.  rows == 0: out = 0. */
+ * (blz_dot_pair_device32).  Blocks that are the same pointer with the same stride are staged once (dev_same_blocks).  Every
+ * workgroup writes ONE row of nx * n * n canonical u64 residues to `partial` -- room for dev_dot_max_blocks() rows of them: the
+ * scratch of the 64-bit namesakes -- and launch_dev_dot_finalize adds the rows mod p into `out`.  rows == 0: out = 0. */
 hipError_t launch_w32_dot(const KernelCfg &c, int n, long long rows, int nx, const u32 *const *x, const long long *ldx,
 			  const u32 *y, long long ldy, u64 *partial, u64 *out, hipStream_t s);
 

@@ -21,7 +21,7 @@
  * into registers (8 words per thread and block) before the current one is multiplied.  A thread owns a TT x TT tile of every
  * C_k: TT = 4 for n > 16 (two 16-byte LDS reads per 16 products), 2 for n <= 16, 1 at n = 1; where (pitch / TT)^2 is less than
  * 256 the threads also split the tile's rows into slices, which are added in LDS at the end (as u32 residues).  Each workgroup
- * writes ONE row of canonical u64 residues to the scratch of the 64-bit namesake and k_w32_sum_rows adds the rows mod p: no
+ * writes ONE row of canonical u64 residues to the scratch of the 64-bit namesake and k_dev_dot_finalize adds the rows mod p: no
  * atomics.  AccS takes 2^32 products of residues below 2^32; a counter reduces it every 2^31.
  *
  * k_w32_combine.  The coefficient matrices are narrowed to u32 on their way into LDS ([output][term][n * n]: 64 KB for four
@@ -30,9 +30,7 @@
  * what makes an output that IS one of the X_t safe.  A sum has at most 4 * 64 products: no cadence is needed.
  */
 #include "blz_devw32.h"
-#include "blz_devfuse.h"
-
-#include <atomic>
+#include "blz_devhelp.h"
 
 namespace {
 
@@ -255,27 +253,6 @@ __global__ void __launch_bounds__(BLOCK) k_w32_dot(DotArgs g, long long rows, in
 	}
 }
 
-/* out[e] = sum_b partial[b][e] mod p, e < words.  A workgroup owns 8 adjacent words, a thread is (row lane, word).
- * nblocks == 0: zeros. */
-__global__ void __launch_bounds__(BLOCK)
-k_w32_sum_rows(const u64 *__restrict__ partial, int nblocks, int words, u64 p, u64 *__restrict__ out)
-{
-	__shared__ u64 red[BLOCK];
-	const int wl = threadIdx.x & 7, rl = threadIdx.x >> 3, e = blockIdx.x * 8 + wl;
-	u64 s = 0;
-	if (e < words)
-		for (int b = rl; b < nblocks; b += BLOCK / 8)
-			s = addmod(s, partial[(size_t)b * words + e], p);
-	red[threadIdx.x] = s;
-	__syncthreads();
-	if (threadIdx.x < 8 && e < words) {
-		u64 tsum = 0;
-		for (int r = 0; r < BLOCK / 8; r++)
-			tsum = addmod(tsum, red[r * 8 + threadIdx.x], p);
-		out[e] = tsum;
-	}
-}
-
 /* ---------------------------------------------------------------------------------------------------- recombinations */
 
 struct CombineArgs {
@@ -356,14 +333,6 @@ __global__ void __launch_bounds__(1024) k_w32_combine(CombineArgs g, int nterms,
 
 /* ---------------------------------------------------------------------------------------------------- launchers */
 
-inline int log2_ceil(int v)
-{
-	int lg = 0;
-	while ((1 << lg) < v)
-		lg++;
-	return lg;
-}
-
 /* lane group of a row (log2) and the grid: every CU a few workgroups, rows beyond them by the grid stride */
 struct Shape {
 	int lg;
@@ -398,29 +367,14 @@ void dot_tt(int v, unsigned grid, hipStream_t s, const DotArgs &g, long long row
 		dot_v<4, NB>(v, grid, s, g, rows, n, lg, m, partial);
 }
 
-constexpr int MAX_DEVICES = 64;
-
-/* Above 48 KB of dynamic LDS the kernel must be told its limit: once per instantiation and device, to the most the
- * instantiation can ask for (NZ outputs x four terms x 64 x 64 u32 words), and a failure is the launcher's error. */
+/* the most LDS an instantiation can ask for: NZ outputs x four terms x 64 x 64 u32 words */
 template <int V, int NZ>
 hipError_t combine_go(unsigned grid, unsigned block, size_t lds, hipStream_t s, const CombineArgs &g, int nterms, long long rows,
 		      int n, int lg, const ModP &m)
 {
-	if (lds > 48 * 1024) {
-		static std::atomic<bool> told[MAX_DEVICES];
-		int dev = 0;
-		hipError_t e = hipGetDevice(&dev);
-		if (e != hipSuccess)
-			return e;
-		if (dev < 0 || dev >= MAX_DEVICES || !told[dev].load()) {
-			e = hipFuncSetAttribute((const void *)k_w32_combine<V, NZ>, hipFuncAttributeMaxDynamicSharedMemorySize,
-						NZ * DEVALG_MAX_TERMS * 64 * 64 * (int)sizeof(u32));
-			if (e != hipSuccess)
-				return e;
-			if (dev >= 0 && dev < MAX_DEVICES)
-				told[dev].store(true);
-		}
-	}
+	const hipError_t e = dev_lds_limit<&k_w32_combine<V, NZ>>(lds, NZ * DEVALG_MAX_TERMS * 64 * 64 * sizeof(u32));
+	if (e != hipSuccess)
+		return e;
 	hipLaunchKernelGGL((k_w32_combine<V, NZ>), dim3(grid), dim3(block), lds, s, g, nterms, rows, n, lg, m);
 	return hipGetLastError();
 }
@@ -511,28 +465,25 @@ hipError_t launch_w32_dot(const KernelCfg &c, int n, long long rows, int nx, con
 	if (n < 1 || n > 64 || rows < 0 || nx < 1 || nx > 2 || c.m.p >= (1ull << 32))
 		return hipErrorInvalidValue;
 	const int lg = log2_ceil(n), TR = W32_TILE_WORDS >> lg, words = nx * n * n, nb = nx + 1;
-	const long long ntiles = (rows + TR - 1) / TR, cap = nx == 1 ? dev_dot_max_blocks(c, n) : dev_dot2_max_blocks(c, n);
+	const long long ntiles = (rows + TR - 1) / TR, cap = dev_dot_max_blocks(c, n);
 	const unsigned grid = (unsigned)(ntiles < cap ? ntiles : cap);
 	if (grid) {
 		DotArgs g{};
+		const void *ptr[MAXB];
 		int v = 4;
 		for (int b = 0; b < nb; b++) {
-			g.b[b] = b < nx ? x[b] : y;
+			ptr[b] = g.b[b] = b < nx ? x[b] : y;
 			g.ld[b] = b < nx ? ldx[b] : ldy;
-			g.slot[b] = b;
-			for (int e = b - 1; e >= 0; e--)
-				if (g.b[e] == g.b[b] && g.ld[e] == g.ld[b])
-					g.slot[b] = e;
 			const int w = dev_w32_width(g.b[b], g.ld[b], n);
 			v = w < v ? w : v;
 		}
+		dev_same_blocks(nb, ptr, g.ld, g.slot);
 		if (nx == 1)
 			dot_tt<2>(v, grid, s, g, rows, n, lg, c.m, partial);
 		else
 			dot_tt<3>(v, grid, s, g, rows, n, lg, c.m, partial);
 	}
-	hipLaunchKernelGGL(k_w32_sum_rows, dim3((unsigned)((words + 7) / 8)), dim3(BLOCK), 0, s, partial, (int)grid, words, c.m.p, out);
-	return hipGetLastError();
+	return launch_dev_dot_finalize(partial, (int)grid, words, c.m.p, out, s);
 }
 
 hipError_t launch_w32_combine(const KernelCfg &c, int n, long long rows, int nterms, const u32 *const *x, const long long *ldx,

@@ -5,9 +5,9 @@ torch or the library.
 
     reduce_model, sum_model      reduce128<0> and the `++cnt == chunk` loop of the kernels (csrc/modp.h)
     dot_shape ... dot_form       launch_dev_dot, dev_dot_max_blocks, k_dev_dot (csrc/blz_devalg.hip)
-    dot2_fused, dot2_form        dev_dot2_fused, launch_dev_dot2 (csrc/blz_devfuse.hip)
-    combine_form                 launch_dev_combine (csrc/blz_devalg.hip)
-    combine2_form                launch_dev_combine2, combine2_v (csrc/blz_devfuse.hip)
+    dot2_fused, dot2_form        dot_pair_fused, launch_dev_dot at nx = 2 (csrc/blz_devalg.hip)
+    combine_form                 launch_dev_combine at nz = 1 (csrc/blz_devalg.hip)
+    combine2_form                launch_dev_combine at nz = 2: combine2, combine_shape (csrc/blz_devalg.hip)
     chain_threads, rref_group    launch_dev_chain, group_of (csrc/blz_devsmall.hip)
 """
 import itertools
@@ -80,7 +80,7 @@ def sum_model(count, p, limit, start=0, term=None):
     return reduce_model(acc, p)
 
 
-# ------------------------------------------------------------------------------------------------ k_dev_dot, k_dev_dot2
+# ------------------------------------------------------------------------------------------------ k_dev_dot (NX = 1, 2)
 
 
 def log2_ceil(v):
@@ -136,7 +136,7 @@ def dot_rows_past_chunk(p, n, cus):
 
 
 def pair_ok(n, pad):
-    """16-byte lane accesses (pair_ok of both files) for a torch allocation, which is 16-byte aligned: even width and stride"""
+    """16-byte lane accesses (pair_ok of csrc/blz_devalg.hip) for a torch allocation, which is 16-byte aligned: even width and stride"""
     return n % 2 == 0 and (n + pad) % 2 == 0
 
 
@@ -150,7 +150,7 @@ def dot_form(p, n, vec2):
 
 
 def dot2_fused(p, n):
-    """dev_dot2_fused: one k_dev_dot2 launch, or (Barrett at n > 32) launch_dev_dot twice"""
+    """dot_pair_fused: one k_dev_dot<..., NX = 2> launch, or (Barrett at n > 32) the nx = 1 form twice"""
     return n <= 32 or p < 1 << 32 or p == P61
 
 
@@ -166,7 +166,7 @@ Combine2Form = namedtuple("Combine2Form", "acc threads lg in_lds dropped_vec2")
 
 
 def combine_form(p, n, nterms, vec2):
-    """launch_dev_combine: 1024 threads where the coefficient matrices take more than 40 KB of LDS, lane groups of
+    """launch_dev_combine at nz = 1: 1024 threads where the coefficient matrices take more than 40 KB of LDS, lane groups of
     2^lg lanes, lg from n / 2 in the 16-byte lane form"""
     v2 = vec2 and n % 2 == 0
     threads = 1024 if nterms * n * n * 8 > 40 * 1024 else 256
@@ -174,8 +174,8 @@ def combine_form(p, n, nterms, vec2):
 
 
 def combine2_form(p, n, masks, vec2):
-    """launch_dev_combine2: a term's panels go into LDS together while they fit 160 KB (in_lds[t]), else the term reads
-    them from global memory; 1024 threads past 40 KB of LDS; combine2_v has no 1024-thread 16-byte lane form for the
+    """launch_dev_combine at nz = 2: a term's panels go into LDS together while they fit 160 KB (in_lds[t]), else the term reads
+    them from global memory; 1024 threads past 40 KB of LDS; k_dev_combine2 has no 1024-thread 16-byte lane form for the
     128-bit accumulators, so that launch drops the lanes (dropped_vec2)"""
     v2 = vec2 and n % 2 == 0
     room, used, in_lds = (160 * 1024) // (n * n * 8), 0, []

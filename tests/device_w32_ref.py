@@ -60,7 +60,7 @@ def dot_slices(n):
 
 
 def dot_max_blocks(n, num_cu):
-    """dev_dot_max_blocks() = dev_dot2_max_blocks(): the grid's cap and the partial rows of the scratch, one panel or two"""
+    """dev_dot_max_blocks(): the grid's cap and the partial rows of the scratch, one panel or two"""
     return max(1, min((8 << 20) // (n * n * 8), num_cu * 4))
 
 

@@ -1,9 +1,9 @@
 """The part of tests/test_gpu_device_exact.py that needs no GPU: device_exact.py restates on integers what the launchers of
-csrc/blz_devalg.hip, blz_devsmall.hip and blz_devfuse.hip decide, and the GPU file takes its shapes from it.  Held here:
+csrc/blz_devalg.hip and blz_devsmall.hip decide, and the GPU file takes its shapes from it.  Held here:
 
   - reduce_model IS the reducer where csrc/modp.h says it is exact, and the all-(p-1) inputs of the GPU file are where one
     product too many (57 bits) or two too many (58 ... 62 bits) is a wrong word -- so the GPU cases ask for chunk + 2;
-  - dot_rows_past_chunk gives every accumulator of k_dev_dot / k_dev_dot2 chunk + 2 products at 8, 256 and 304 compute units,
+  - dot_rows_past_chunk gives every accumulator of k_dev_dot (one product or two) chunk + 2 products at 8, 256 and 304 compute units,
     and no smaller row count of that shape does;
   - the case lists reach every instantiation the launchers can produce (the table of DESIGN.md, "Device block algebra at
     the bounds").

@@ -91,6 +91,17 @@ def sentinel_square(n):
     return torch.from_numpy(np.full((n, n), SENTINEL, dtype=np.uint64).view(np.int64)).to("cuda:0")
 
 
+def one_base_two_strides(rows, n, p, word=np.uint64):
+    """rows * 2n random residues, once as a block of stride n and once, from the SAME pointer, as one of stride 2n: two
+    blocks, not one.  (the two views, the words of each on the host); word: np.uint64, or np.uint32 for the 32-bit calls.
+    tests/test_gpu_device_fused.py and tests/test_gpu_device_w32.py take it from here."""
+    host = np.random.default_rng([11, rows, n]).integers(0, p, size=rows * 2 * n, dtype=word)
+    base = torch.from_numpy(host.view(np.int64 if word == np.uint64 else np.int32)).to("cuda:0")
+    near, far = base[:rows * n].view(rows, n), base.view(rows, 2 * n)[:, :n]
+    assert near.data_ptr() == far.data_ptr() and near.stride(0) == n and far.stride(0) == 2 * n
+    return near, far, host[:rows * n].reshape(rows, n), host.reshape(rows, 2 * n)[:, :n]
+
+
 # ------------------------------------------------------------------------------------------ 1. dot against exact integers
 
 
@@ -120,6 +131,12 @@ def test_dot_against_exact_integers(p, n):
                 assert np.array_equal(to_host(xv), X) and np.array_equal(to_host(yv), Y)
             fl = torch.from_numpy(flat(X).copy().view(np.int64)).to("cuda:0")       # the flat layout of a block
             assert np.array_equal(to_host(ctx.dot(fl, to_dev(Y)[0])), want)
+        if n in (3, 8) and p in (P16, P62):             # x and y the same pointer at strides n and 2n: NOT "x is y"
+            for rows in (37, 300):                      # one partial tile; several workgroups
+                xv, yv, X, Y = one_base_two_strides(rows, n, p)
+                want = np.array((obj(X).T @ obj(Y)) % p, dtype=np.uint64).reshape(n, n)      # Python integers
+                assert np.array_equal(to_host(ctx.dot(xv, yv)), want), (rows, "one pointer, two strides")
+                assert np.array_equal(to_host(ctx.dot(yv, xv)), want.T), (rows, "one pointer, two strides, swapped")
 
 
 # ------------------------------------------------------------------------------------------ 2. dot at scale

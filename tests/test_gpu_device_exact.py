@@ -1,4 +1,4 @@
-"""The device block algebra (csrc/blz_devalg.hip, blz_devsmall.hip, blz_devfuse.hip) against exact integers at every reducer
+"""The device block algebra (csrc/blz_devalg.hip, blz_devsmall.hip) against exact integers at every reducer
 class of csrc/modp.h and at the widths 1 ... 64: the ladder tests/test_gpu_exact.py holds the solver's own kernels to, for
 the calls on caller-owned blocks -- Context.dot, dot_pair, combine, combine_pair, semi_inverse_device, ortho_coeffs, rref.
 

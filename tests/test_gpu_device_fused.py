@@ -8,7 +8,7 @@ blz_combine_pair_device (Context.combine_pair) on caller-owned torch tensors, ag
   - an undisturbed twin for "the solve is left alone".
 
 Every comparison is equality of u64 words.  The reducer ladder -- every reducer class of csrc/modp.h, the widths between
-those of WIDTHS, sums past ModP::chunk in k_dev_dot2 and k_dev_combine2 -- is tests/test_gpu_device_exact.py, which imports the
+those of WIDTHS, sums past ModP::chunk in the paired k_dev_dot and k_dev_combine2 -- is tests/test_gpu_device_exact.py, which imports the
 helpers, MASKS and four_calls_against_twin from here.
 """
 import ctypes as C
@@ -19,6 +19,7 @@ import pytest
 import torch
 
 import blz
+from test_gpu_device_algebra import one_base_two_strides
 
 pytestmark = pytest.mark.gpu
 
@@ -149,6 +150,13 @@ def test_dot_pair_against_exact_integers_and_two_dots(p, n):
             # mixed strides: one block of each lane form
             c = to_host(ctx.dot_pair(to_dev(A, 3)[0], to_dev(B, 0)[0], to_dev(Y, 2)[0]))
             assert np.array_equal(c[0], two["A"]) and np.array_equal(c[1], two["B"]), (rows, "mixed")
+        # a sixth aliasing pattern: x0 = y = (base, stride n) are one block, x1 = (the same base, stride 2n) is another
+        if n in (3, 8) and p in (P16, P62):
+            for rows in (37, 300):                      # one partial tile; several workgroups
+                near, far, N, F = one_base_two_strides(rows, n, p)
+                got = to_host(ctx.dot_pair(near, far, near))
+                assert np.array_equal(got[0], gram_ref(N, N, p, n)), (rows, "one pointer, two strides", 0)     # Python integers
+                assert np.array_equal(got[1], gram_ref(F, N, p, n)), (rows, "one pointer, two strides", 1)
 
 
 @pytest.mark.parametrize("n", (1, 8, 64))

@@ -21,6 +21,7 @@ import torch
 import blz
 import device_w32_ref as ref
 import oracle as orc
+from test_gpu_device_algebra import one_base_two_strides
 
 pytestmark = pytest.mark.gpu
 
@@ -311,6 +312,14 @@ def test_dot_pair32_in_every_aliasing_pattern(p, n):
                     assert np.array_equal(host64(out), want), (rows, pat, k, "out")
                     for ch in "abc":
                         assert d[ch].rest_intact() and np.array_equal(d[ch].words(), W[ch])
+        # one pointer at two strides (n and 2n) is two blocks: dot32(x, y), and dot_pair32 with x0 = y one block, x1 another
+        if n in (3, 8) and p == P16:
+            for rows in (37, 300):                      # one partial tile; several workgroups
+                near, far, N, F = one_base_two_strides(rows, n, p, np.uint32)
+                assert np.array_equal(host64(ctx.dot32(near, far)), gram_ref(N, F, p, n)), (rows, "one pointer, two strides")
+                got = host64(ctx.dot_pair32(near, far, near))
+                assert np.array_equal(got[0], gram_ref(N, N, p, n)), (rows, "one pointer, two strides", 0)
+                assert np.array_equal(got[1], gram_ref(F, N, p, n)), (rows, "one pointer, two strides", 1)
 
 
 MASKS = {1: [((1, 1),)],                                # the mask list of tests/test_gpu_device_fused.py

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What the device block algebra costs on the matrix cores beside the vector-ALU kernels it replaces:
-two contexts in one process -- one created under BLZ_NO_MFMA=1, whose device calls run the kernels of blz_devalg.hip and
-blz_devfuse.hip (byte-identical to the commit before the matrix-core forms: the baseline), one created under
+two contexts in one process -- one created under BLZ_NO_MFMA=1, whose device calls run the vector-ALU kernels of blz_devalg.hip
+(the baseline), one created under
 BLZ_DEV_MFMA_MIN_ROWS=0, whose calls take the forms of blz_devmfma.hip at every row count -- the same calls on the same blocks,
 alternated.  HIP events on the caller's stream around ten calls back to back, five rounds; medians with min and max.
 
